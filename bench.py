@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — IQ MSamples/s through the demodulator chains on N MI355X GPUs, with the HBM roofline fraction
-of the dominant kernel and the CPU baseline timed beside it.
+of the dominant kernel and, with --full, the CPU baseline timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0|1|2|3|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0|1|2|3|4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, settles the clocks, warms up, times the K steps and prints the line.  Everything else the benchmark
+measures - the from-idle figure, the CPU baseline, the PCIe-inclusive host path, the rocprofv3 counter passes, the other
+BASELINE configurations as sub-lines and configs[0]'s parity check against the CPU chain - runs only with `--full`.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64).
 
 `python bench.py --gpus N` with N > 1 starts its own ranks (torch.distributed.run as a CHILD process, one rank per GPU
 over RCCL) when it was not itself started by a launcher, and relays rank 0's line and the exit code.
@@ -222,6 +227,34 @@ def host_path(eng, iq_dev, n, n_ch, reps=3):
     return {"value": round(n * n_ch / dt / 1e6, 1), "unit": "MSamples/s", "ms_per_step": round(1e3 * dt, 3),
             "GB_per_s_over_pcie": round(2.0625 * n * n_ch / dt / 1e9, 2),
             "what": "iqd_accept_iq from page-locked host buffers (upload, kernels, PCM download), %d calls" % reps}
+
+
+DUMP_MAX_PCM = 1 << 23          # PCM samples written in full (32 MB as float32); beyond that a fixed, seeded sample of
+DUMP_SAMPLE = 1 << 22           # this many (16 MB as float32 + 32 MB of float64 positions: the dump stays under 64 MB)
+
+
+def dump_outputs(out_dir, torch, pcm, small):
+    """--dump-outputs: what a caller of the timed path holds after the last step, as DIR/<name>.npy - `pcm` [channels][row]
+    (samples past a channel's count zeroed: they are not part of the result), `pcm_count`, `magnitude` [channels][blocks] and
+    `signal_present` [channels][blocks]; `small` is None under --no-magnitude, whose calls return the PCM only.  Exact values:
+    int16 / uint8 as float32, int32 / uint32 as float64.  A PCM of more than DUMP_MAX_PCM samples is written as DUMP_SAMPLE
+    samples at seeded positions (`pcm` flat, `pcm_index` their flat indices), so that two runs with the same arguments write
+    the same files."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_ch, row = pcm.shape
+    if small is not None:
+        cnt, mag, allowed = small
+        cols = torch.arange(row, device=pcm.device, dtype=torch.int64)
+        pcm = torch.where(cols.unsqueeze(0) < cnt.to(torch.int64).unsqueeze(1), pcm, torch.zeros_like(pcm))
+        np.save(os.path.join(out_dir, "pcm_count.npy"), cnt.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(out_dir, "magnitude.npy"), mag.view(n_ch, -1).cpu().numpy().view(np.uint32).astype(np.float64))
+        np.save(os.path.join(out_dir, "signal_present.npy"), allowed.view(n_ch, -1).cpu().numpy().astype(np.float32))
+    pcm = pcm.cpu().numpy()
+    if pcm.size > DUMP_MAX_PCM:
+        idx = np.sort(np.random.default_rng(20240601).choice(pcm.size, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(out_dir, "pcm_index.npy"), idx.astype(np.float64))
+        pcm = pcm.reshape(-1)[idx]
+    np.save(os.path.join(out_dir, "pcm.npy"), pcm.astype(np.float32))
 
 
 def profile_summary(tag):
@@ -474,9 +507,10 @@ def rank_body(args, rank, world, dev, make_engine, dist, torch, order_streams=No
                 order_streams(eng, False)   # and the engine's next step waits for the gatherer's copies out of pcm / cnt
 
     # From idle: what a default-length run measures on a device whose clocks have not settled - the W
-    # warm-up steps, then K steps on the host's clock - before the settle phase below.  Reported beside the settled figure.
+    # warm-up steps, then K steps on the host's clock - before the settle phase below.  Reported beside the settled figure
+    # (--full only).
     from_idle_ms = None
-    if getattr(args, "prewarm_ms", 0.0) > 0 and not getattr(args, "no_from_idle", False):
+    if getattr(args, "full", False) and getattr(args, "prewarm_ms", 0.0) > 0 and not getattr(args, "no_from_idle", False):
         eng.synchronize()
         time.sleep(0.25)                                  # (staging the input was load, too: let the device fall idle)
         for _ in range(args.warmup):
@@ -520,6 +554,8 @@ def rank_body(args, rank, world, dev, make_engine, dist, torch, order_streams=No
     elapsed = time.perf_counter() - t0
     k1 = eng.stats()
     eng.set_profiling(False)
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, torch, pcm.view(n_ch, -1), None if args.no_magnitude else outs[(step_no[0] - 1) & 1])
     per_rank_ms, rccl = None, None
     if dist is not None:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -573,7 +609,8 @@ def rank_body(args, rank, world, dev, make_engine, dist, torch, order_streams=No
                   "am": "d4_stream_kernel" if streamed else "am_chain_kernel",
                   "mixed": "mixed_stream_kernel"}.get("am" if args.mode in ("am", "lsb", "usb", "ssb_stress") else args.mode)
         live = None
-        if world == 1 and dev.type == "cuda" and not args.no_live_pmc and (timed_samples is not None or mixed_one or args.mode != "mixed"):
+        if (world == 1 and dev.type == "cuda" and getattr(args, "full", False) and not args.no_live_pmc
+                and (timed_samples is not None or mixed_one or args.mode != "mixed")):
             live = live_pmc(args.argv, needle, timed_samples or n * n_ch,   # (counters per launch of the dominant kernel)
                             passes=getattr(args, "pmc_passes", None) or ("fetch", "write", "sq1"))
         roof = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "kernel": timed, "kernel_ms": round(kern_ms, 4)}
@@ -658,9 +695,9 @@ def rank_body(args, rank, world, dev, make_engine, dist, torch, order_streams=No
             out["config"]["squelch"] = {"threshold_dbfs": GATE_THRESHOLD_DBFS if (args.squelch is None and args.mode == "ssb_stress") else args.squelch,
                                         "blocks_rejected_frac": round(1.0 - open_frac, 4),
                                         "pcm_samples_per_channel_mean": round(float(cnt.float().mean().item()), 1)}
-        if world == 1 and not args.no_host_path and dev.type == "cuda":
+        if world == 1 and getattr(args, "full", False) and not args.no_host_path and dev.type == "cuda":
             out["host_path"] = host_path(eng, iq, n, n_ch)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and getattr(args, "full", False) and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(period_u8, args.mode, all_cores=not args.cpu_one_core_only)
     eng.close()
     return out
@@ -669,8 +706,14 @@ def rank_body(args, rank, world, dev, make_engine, dist, torch, order_streams=No
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; configs[0]: 61)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the from-idle figure, the CPU baseline, the host path, "
+                         "the rocprofv3 counter passes, the other configurations (`other_configs`) and configs[0]'s CPU parity check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (PCM, counts, magnitudes, squelch flags) as "
+                         "DIR/<name>.npy in float32 / float64; a PCM larger than 2^23 samples is written as a fixed, seeded sample of 2^22")
     ap.add_argument("--prewarm-ms", type=float, default=100.0,
                     help="untimed load before the warm-up steps, so that the device's clocks have settled when the timed steps "
                          "start (DESIGN.md section 6: the step time falls by a tenth over the first 25 ms of load); 0 = none")
@@ -696,8 +739,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="diagnostic: time the steps without the engine's per-kernel HIP events (no roofline.kernel_ms then)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="the default run (configs[1]) also times configs[0], [2], [3], [4] and AM / USB at 4096 x 2^16 for a few steps each "
-                         "and reports them as `other_configs`; this flag skips that")
+                    help="with --full, the default workload (configs[1]) also times configs[0], [2], [3], [4] and AM / USB at 4096 x 2^16 for a "
+                         "few steps each and reports them as `other_configs`; this flag skips that")
     ap.add_argument("--pmc-passes", default=None, help=argparse.SUPPRESS)   # fetch,write[,sq1]: which counter passes live_pmc runs (the sub-lines: two)
     ap.add_argument("--force-launch", action="store_true",
                     help="start the ranks through bench.py's own launcher (torch.distributed.run as a child process) even for --gpus 1: "
@@ -709,9 +752,14 @@ def parse_args(argv=None):
         args.pmc_passes = tuple(x for x in args.pmc_passes.split(",") if x)
         i = args.argv.index("--pmc-passes")
         del args.argv[i:i + 2]
+    # (nor the dump: a counter pass must not overwrite the outputs of the run that started it)
+    args.argv = [a for i, a in enumerate(args.argv) if not a.startswith("--dump-outputs")
+                 and not (i > 0 and args.argv[i - 1] == "--dump-outputs")]
     preset = CONFIGS[1 if args.config is None else args.config]
-    if args.config == 0 and args.steps == 20 and args.warmup == 3:
-        args.steps, args.warmup = 61, 3          # 64 blocks = 2^20 samples, SURVEY 8(d) Config 1
+    if args.warmup is None:
+        args.warmup = 3
+    if args.steps is None:                       # configs[0]: 64 blocks = 2^20 samples, SURVEY 8(d) Config 1
+        args.steps = 61 if (args.config == 0 and args.warmup == 3) else 20
     custom = args.mode is not None or args.channels is not None or args.log2_samples is not None
     args.mode = args.mode or preset["mode"]
     args.channels = args.channels or preset["channels"]
@@ -751,8 +799,8 @@ def self_launch(argv, n_gpus):
     return p.returncode if (p.returncode != 0 or line is not None) else 1
 
 
-# What the default run times besides its headline: every other BASELINE configuration and the two single-family
-# AM / SSB workloads DESIGN.md quotes, each as a child process with a run's own settings, so that their figures come off the driver's own run.
+# What the default workload's --full run times besides its headline: every other BASELINE configuration and the two
+# single-family AM / SSB workloads DESIGN.md quotes, each as a child process with a run's own settings.
 OTHER_CONFIGS = (["--config", "0"], ["--config", "2"], ["--config", "3"], ["--config", "4"],
                  ["--mode", "am", "--channels", "4096", "--log2-samples", "16"],
                  ["--mode", "usb", "--channels", "4096", "--log2-samples", "16"])
@@ -761,7 +809,7 @@ SUB_KEYS = ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "config
 
 
 def other_configs(args):
-    """Sub-lines of the default run: each one is what `python bench.py <argv>` prints, cut down to SUB_KEYS - a CHILD process per
+    """Sub-lines of the default workload's --full run: each one is what `python bench.py <argv> --full` prints, cut down to SUB_KEYS - a CHILD process per
     configuration (the same rank_body, the engine's event timing, HBM traffic from two rocprofv3 --pmc passes of that very command:
     FETCH_SIZE, WRITE_SIZE), so that whatever happens in one of them costs a sub-line and never the headline."""
     import subprocess
@@ -769,7 +817,8 @@ def other_configs(args):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     for argv in OTHER_CONFIGS:
         t0 = time.perf_counter()
-        cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--no-other-configs", "--no-host-path", "--no-from-idle", "--pmc-passes", "fetch,write"]
+        cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--full", "--no-other-configs", "--no-host-path", "--no-from-idle",
+                                                                    "--pmc-passes", "fetch,write"]
         if argv != ["--config", "0"]:   # (configs[0]: its 64 blocks, with the CPU chain beside them - the parity check of that file)
             cmd += ["--steps", "20", "--warmup", "3", "--prewarm-ms", "100", "--no-cpu-baseline"]   # (the settings of a run of its own)
         if args.no_live_pmc:
@@ -793,7 +842,7 @@ def config0(args):
     """BASELINE configs[0]: one FM channel from a FILE through the C++ IqDataProcessor::acceptIqData in 32768-byte
     blocks (rtlsdrdiags_amd/bin/iqdemod_file: the reference's radioApp.cc / demod.cc shape), one block per call - the
     reference's real operating point (DataConsumer.cc:333-346).  A step is one block; the first `warmup` blocks of the
-    file are not timed.  The PCM is held to the CPU chain's, which is timed beside it on the same file."""
+    file are not timed.  With --full the PCM is held to the CPU chain's, which is timed beside it on the same file."""
     import subprocess
     import tempfile
     from rtlsdrdiags_amd import synth
@@ -831,7 +880,10 @@ def config0(args):
                      "note": "one 32 KiB block per call: latency-bound by construction (a 64 ms block every 64 ms is the "
                              "reference's operating point); the throughput roofline is configs[1]'s business"},
     }
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:          # (the PCM of the whole file: the last step's block is its tail)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pcm.npy"), pcm.astype(np.float32))
+    if args.full and not args.no_cpu_baseline:
         chain, kind = _cpu_chain("fm")
         t0 = time.perf_counter()
         ref, _, _ = chain.accept_stream(u8)
@@ -904,8 +956,8 @@ def main():
             ext.wait_stream(torch.cuda.current_stream())
 
     out = rank_body(args, rank, world, torch.device("cuda", local_rank), make_engine, dist, torch, order_streams)
-    # (the full default form only: a run trimmed with --no-cpu-baseline / --no-host-path is a measurement tool's, tools/*.sh)
-    if (out is not None and world == 1 and dist is None and args.is_default_workload
+    # (--full on the default workload only: a run trimmed with --no-cpu-baseline / --no-host-path is a measurement tool's)
+    if (out is not None and world == 1 and dist is None and args.is_default_workload and args.full
             and not (args.no_other_configs or args.no_cpu_baseline or args.no_host_path)):
         out["other_configs"] = other_configs(args)
     if out is not None:

@@ -117,15 +117,28 @@ def demod_tool(R):
     np.savez_compressed(os.path.join(OUT, "demod_tool.npz"), **out)
 
 
+def oracle_vs_ref(R):
+    """tests/test_oracle_vs_ref.py's cases as the reference computes them: <key>__n arrays <key>__0 .. for every case."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import test_oracle_vs_ref as T
+    out = {}
+    for key, case, args in T.CASES:
+        got = case(lambda agc=False: R.chain(agc=agc), *args)
+        out[key + "__n"] = np.array(len(got))
+        out.update({"%s__%d" % (key, i): np.asarray(a) for i, a in enumerate(got)})
+    np.savez_compressed(os.path.join(OUT, "oracle_vs_ref.npz"), **out)
+
+
 def main():
     R = B.Reference()
     if len(sys.argv) > 1:                    # only the named fixtures (python make_golden.py demod_entry capture)
         for name in sys.argv[1:]:
-            {"demod_entry": demod_entry, "capture": capture, "demod_tool": demod_tool}[name](R)
+            {"demod_entry": demod_entry, "capture": capture, "demod_tool": demod_tool, "oracle_vs_ref": oracle_vs_ref}[name](R)
         return
     demod_entry(R)
     capture(R)
     demod_tool(R)
+    oracle_vs_ref(R)
     blk = 16384
 
     # (i) modulated tone at -Fs/4 + noise, moderate amplitude

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -57,9 +58,10 @@ def test_mixed_configuration_line():
 
 
 def test_cpu_baseline_and_live_counters_present():
-    """The full default form on a small workload: cpu_baseline (the reference or its port, on this box's host cores) and the
+    """The --full form on a small workload: cpu_baseline (the reference or its port, on this box's host cores) and the
     counters collected by the run's own rocprofv3 passes (or a reason why not)."""
-    d = check_contract(run_bench("--steps", "3", "--warmup", "1", "--prewarm-ms", "10", "--log2-samples", "24", "--no-host-path"), 3, 1)
+    d = check_contract(run_bench("--steps", "3", "--warmup", "1", "--prewarm-ms", "10", "--log2-samples", "24", "--no-host-path",
+                                 "--full"), 3, 1)
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == "MSamples/s" and cb["sample"]
     r = d["roofline"]
@@ -93,11 +95,11 @@ def check_sub_line(s):
 
 
 def test_default_run_carries_every_other_configuration():
-    """`python bench.py --gpus 1 --steps K --warmup W`, the driver's own command: the headline line of configs[1] with its usual
-    fields, and `other_configs` - configs[0], [2], [3], [4] and AM / USB at 4096 x 2^16, a few steps each, a child process each
-     - each sub-line consistent in itself.  (Full size: this IS the driver's run, about three minutes.)"""
+    """`python bench.py --gpus 1 --steps K --warmup W --full`: the headline line of configs[1] with its usual fields, and
+    `other_configs` - configs[0], [2], [3], [4] and AM / USB at 4096 x 2^16, a few steps each, a child process each
+     - each sub-line consistent in itself.  (Full size, about three minutes.)"""
     import bench
-    d = check_contract(run_bench("--gpus", "1", "--steps", "6", "--warmup", "2", "--cpu-one-core-only", "--no-live-pmc"), 6, 2)
+    d = check_contract(run_bench("--gpus", "1", "--steps", "6", "--warmup", "2", "--cpu-one-core-only", "--no-live-pmc", "--full"), 6, 2)
     assert "wbfm_stream_kernel" in d["roofline"]["kernel"] and d["config"]["log2_samples_per_channel"] == 28
     subs = d["other_configs"]
     assert [s["argv"] for s in subs] == [" ".join(a) for a in bench.OTHER_CONFIGS]
@@ -106,6 +108,25 @@ def test_default_run_carries_every_other_configuration():
     by = {s["argv"]: s for s in subs}
     assert "mixed_stream_kernel" in by["--config 3"]["roofline"]["kernel"]
     assert by["--config 4"]["config"]["squelch"]["blocks_rejected_frac"] > 0.2
+
+
+def test_plain_run_is_lean_and_dumps_the_same_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the headline only (no CPU baseline, host path, counter passes
+    or sub-lines), exactly K timed steps; --dump-outputs writes the last step's PCM, counts, magnitudes and flags, identical
+    from run to run with the same arguments."""
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm-ms", "20", "--log2-samples", "24"]
+    dumps = []
+    for k in range(2):
+        d = check_contract(run_bench(*(argv + ["--dump-outputs", str(tmp_path / str(k))])), 3, 1)
+        assert not {"cpu_baseline", "host_path", "other_configs"} & set(d) and d["from_idle_ms_per_step"] is None
+        assert "counters_note" not in d["roofline"] and d["state_repairs"] == 0
+        got = {f[:-4]: np.load(str(tmp_path / str(k) / f)) for f in sorted(os.listdir(str(tmp_path / str(k))))}
+        assert set(got) == {"pcm", "pcm_count", "magnitude", "signal_present"}
+        assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+        assert got["pcm"].shape == (1, (1 << 24) // 32) and got["pcm_count"].tolist() == [(1 << 24) // 32]
+        assert np.any(got["pcm"] != 0) and got["magnitude"].shape == (1, (2 << 24) // 32768)
+        dumps.append(got)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
 
 
 # ---- the N > 1 code path on the hardware there is: one rank under a real launcher (VERDICT r5 item 5) ----------------------

@@ -174,16 +174,58 @@ def test_prewarm_runs_the_same_number_of_steps_on_every_rank():
     wall-clock loop would leave the ranks with different numbers of gather collectives."""
     import bench
     a = bench.parse_args(["--gpus", "2", "--steps", "2", "--warmup", "1", "--mode", "mixed", "--channels", "5", "--log2-samples", "12",
-                          "--gather", "--no-cpu-baseline", "--no-host-path", "--prewarm-ms", "0.1"])
+                          "--gather", "--no-cpu-baseline", "--no-host-path", "--prewarm-ms", "0.1", "--full"])
     eng = FakeEngine(5, 0, 0)
     out = bench.rank_body(a, 0, 1, torch.device("cpu"), lambda n_channels, flags: eng, None, torch)
-    # (W + K steps for the from-idle figure, the settle phase, then W + K again)
+    # (--full: W + K steps for the from-idle figure, the settle phase, then W + K again)
     assert eng.calls == (1 + 2) + 5 + 1 + 2 and "5 untimed steps" in out["config"]["prewarm"], (eng.calls, out["config"]["prewarm"])
     assert out["from_idle_ms_per_step"] is not None
     a.no_from_idle = True
     eng = FakeEngine(5, 0, 0)
     out = bench.rank_body(a, 0, 1, torch.device("cpu"), lambda n_channels, flags: eng, None, torch)
     assert eng.calls == 5 + 1 + 2 and out["from_idle_ms_per_step"] is None
+    a.no_from_idle, a.full = False, False     # a plain run: no from-idle figure, the same settle phase
+    eng = FakeEngine(5, 0, 0)
+    out = bench.rank_body(a, 0, 1, torch.device("cpu"), lambda n_channels, flags: eng, None, torch)
+    assert eng.calls == 5 + 1 + 2 and out["from_idle_ms_per_step"] is None
+
+
+def test_plain_run_times_only_the_headline_and_dumps_the_last_step(tmp_path, monkeypatch):
+    """`bench.py --steps K --warmup W` without --full: W warm-up steps and exactly K timed ones, no CPU baseline, no host path,
+    no counter passes; --dump-outputs writes the last step's PCM and counts as float arrays, the same for the same arguments."""
+    import bench
+    argv = ["--steps", "4", "--warmup", "2", "--mode", "mixed", "--channels", "5", "--log2-samples", "12", "--prewarm-ms", "0"]
+    dumps = []
+    for k in range(2):
+        a = bench.parse_args(argv + ["--dump-outputs", str(tmp_path / str(k))])
+        assert (a.steps, a.warmup, a.full) == (4, 2, False) and "--dump-outputs" not in a.argv
+        eng = FakeEngine(5, 0, 0)
+        out = bench.rank_body(a, 0, 1, torch.device("cpu"), lambda n_channels, flags: eng, None, torch)
+        assert eng.calls == 2 + 4 and out["steps"] == 4 and out["warmup"] == 2
+        assert not {"cpu_baseline", "host_path", "other_configs"} & set(out) and out["from_idle_ms_per_step"] is None
+        got = {f[:-4]: np.load(str(tmp_path / str(k) / f)) for f in sorted(os.listdir(str(tmp_path / str(k))))}
+        assert set(got) == {"pcm", "pcm_count", "magnitude", "signal_present"}
+        assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+        assert got["pcm"].shape == (5, (1 << 12) // 32) and np.array_equal(got["pcm_count"], np.full(5, (1 << 12) // 32))
+        assert np.array_equal(got["pcm"][:, 0], [1] * 5)          # (the stand-in writes the rotation selector there)
+        dumps.append(got)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    # a PCM past DUMP_MAX_PCM: a seeded sample with its positions, the same for the same arguments, under 64 MB at full size
+    assert 4 * bench.DUMP_MAX_PCM <= 48 << 20 and (4 + 8) * bench.DUMP_SAMPLE <= 48 << 20
+    monkeypatch.setattr(bench, "DUMP_MAX_PCM", 256)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    for k in (2, 3):
+        a = bench.parse_args(argv + ["--dump-outputs", str(tmp_path / str(k))])
+        bench.rank_body(a, 0, 1, torch.device("cpu"), lambda n_channels, flags: FakeEngine(5, 0, 0), None, torch)
+    got = [{f: np.load(str(tmp_path / str(k) / f)) for f in ("pcm.npy", "pcm_index.npy")} for k in (2, 3)]
+    idx, pcm = got[0]["pcm_index.npy"], got[0]["pcm.npy"]
+    assert pcm.shape == idx.shape == (100,) and pcm.dtype == np.float32 and idx.dtype == np.float64
+    assert np.all(np.diff(idx) > 0) and np.array_equal(pcm, dumps[0]["pcm"].reshape(-1)[idx.astype(np.int64)])
+    assert all(np.array_equal(got[0][f], got[1][f]) for f in got[0])
+    a = bench.parse_args(["--config", "0"])
+    assert (a.steps, a.warmup) == (61, 3)                          # configs[0]'s default: 64 blocks
+    a = bench.parse_args(["--config", "0", "--steps", "20", "--warmup", "3"])
+    assert (a.steps, a.warmup) == (20, 3)                          # an explicit --steps is what runs
 
 
 def test_presets_name_the_baseline_configurations():
