@@ -296,6 +296,65 @@ size_t iqd_resampler_out_count(const iqd_resampler_t *r, size_t n_in);
 int iqd_resampler_run(iqd_resampler_t *r, const void *in, size_t n_in, void *out);                 /* host pointers */
 int iqd_resampler_run_device(iqd_resampler_t *r, const void *in_dev, size_t n_in, void *out_dev);  /* queued on the engine's stream */
 
+/* Wideband channelizer: many engine channels cut out of one uint8 capture at M x 256 kS/s (an RTL-SDR at 2.048 MS/s is
+ * M = 8).  The reference gets its one channel from the RTL2832U's own down-converter (Radio tunes the dongle, the chip
+ * delivers 256 kS/s around that frequency); this is the same front for any number of channels of one receiver.  Every
+ * step after the phasor table is integer and fixed here, so results are exact, not within a tolerance:
+ *
+ *   sources   a call gives each of n_sources sources bytes_per_source bytes of interleaved offset-binary I/Q, layout
+ *             [n_sources][bytes_per_source]; x[n] = (I - 128) + j (Q - 128); n counts samples since create / reset;
+ *             x[n < 0] = 0 (zero history, like Decimator_int16).  bytes_per_source: a multiple of 64 M.
+ *   prototype h[0..K) int16 Q15 low-pass, 1 <= K <= 1024, |h[k]| <= 32639, 256 sum |h| <= 2^31 - 256 (else IQD_EINVAL).
+ *             taps == NULL: iqd_channelizer_default_taps(M).
+ *   phasor    P[i] = (lrint(32767 cos(2 pi i / 4096)), lrint(32767 sin(2 pi i / 4096))), i < 4096:
+ *             iqd_channelizer_phasor_table.
+ *   channel c source s_c, phase increment d_c (uint32), gain shift L_c in [0, 8].  Offset f_c = int32(d_c) / 2^32 Fs_wide.
+ *             Complex taps: i_k = (k d_c mod 2^32) >> 20, gr[k] = (h[k] Pc[i_k] + 2^14) >> 15,
+ *             gi[k] = (h[k] Ps[i_k] + 2^14) >> 15 (>> is an arithmetic shift throughout).
+ *   output m  n = m M + M - 1 (the decimator's emit point, Decimator_int16.cc:310-351), m counts since create / reset:
+ *             Ar = sum_k gr[k] xr[n-k] - gi[k] xi[n-k],  Ai = sum_k gr[k] xi[n-k] + gi[k] xr[n-k]   (exact in int32)
+ *             a = sat16((A + 128) >> 8) on each rail
+ *             (c, s) = P[(n d_c mod 2^32) >> 20]                   (e^{-j w n}: the channel to DC; no phase state)
+ *             rr = ar c + ai s,  ri = ai c - ar s,  y = sat8((r + 2^(21-L)) >> (22-L)),  byte = y + 128
+ *             L = 0 is unity gain (full-scale DC in, full scale out); every step of L adds 6 dB.
+ *   out       [n_channels][bytes_per_source / M] uint8: exactly the rows iqd_accept_iq_device reads.
+ *
+ * The reference tunes the dongle to station + Fs/4 (Radio.cc:617-618), and the engine's default rotation (+1) brings
+ * that back.  So a channel placed at station + 64 kHz feeds the default rotation exactly as the dongle would; a channel
+ * placed on the station itself wants iqd_set_rotation(..., 0).
+ *
+ * iqd_channelizer_set_channels takes effect at the next run and rebuilds only the named channels' taps (every channel
+ * starts on source 0, increment 0, L = 0).  Runs are queued on the engine's stream; run_device returns once queued, the
+ * host forms return when done.  iqd_accept_wideband: uploads only the wideband bytes, channelizes into rows the
+ * channelizer owns, runs iqd_accept_iq_device for engine channels [first_ch, first_ch + n_channels) and copies the
+ * results out (layouts of iqd_accept_iq; the rows, bytes_per_source / M, follow its block_bytes rule).
+ * Every out-of-range argument is IQD_EINVAL before anything is queued. */
+typedef struct iqd_channelizer_config {
+    uint32_t n_sources;     /* >= 1 */
+    uint32_t n_channels;    /* >= 1 */
+    uint32_t decimation;    /* M, 2..64 */
+    uint32_t n_taps;        /* K, 1..1024 (ignored when taps == NULL) */
+    const int16_t *taps;    /* h[0..K), Q15; NULL -> iqd_channelizer_default_taps(M) */
+    uint32_t reserved[4];   /* 0 */
+} iqd_channelizer_config;
+typedef struct iqd_channelizer iqd_channelizer_t;
+int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_channelizer_t **out);
+void iqd_channelizer_destroy(iqd_channelizer_t *z);   /* before its engine's iqd_destroy */
+int iqd_channelizer_reset(iqd_channelizer_t *z);
+int iqd_channelizer_set_channels(iqd_channelizer_t *z, uint32_t first, uint32_t n, const uint32_t *source,
+                                 const uint32_t *phase_inc, const uint8_t *gain_shift);
+/* wide_dev [n_sources][bytes_per_source] and out_dev [n_channels][bytes_per_source / M]: device memory, both 16-byte
+ * aligned (else IQD_EINVAL) - the kernel reads and writes whole 16-byte units. */
+int iqd_channelizer_run_device(iqd_channelizer_t *z, const void *wide_dev, size_t bytes_per_source, void *out_dev);
+int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_per_source, uint8_t *out);
+int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const uint8_t *wide, size_t bytes_per_source,
+                        int16_t *pcm, uint32_t *pcm_count, uint32_t *magnitude, uint8_t *signal_present);
+/* Host only, no GPU needed: the phasor table as (cos, sin) pairs, and the library's default prototype for M (odd length,
+ * symmetric, DC gain 32768, passband +-100 kHz at the output rate, >= 50 dB down from 156 kHz: a Kaiser-windowed sinc
+ * of 13 M + 1 taps).  default_taps returns the tap count (writing min(count, capacity) taps), or IQD_EINVAL. */
+int iqd_channelizer_phasor_table(int16_t out[8192]);
+int iqd_channelizer_default_taps(uint32_t decimation, int16_t *out, uint32_t capacity);
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

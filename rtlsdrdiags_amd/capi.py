@@ -6,6 +6,7 @@ this boundary: device buffers are passed as integer addresses.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -40,6 +41,11 @@ class AgcState(C.Structure):
                 ("normalized_level_dbfs", C.c_int32), ("signal_magnitude", C.c_uint32)]
 
 
+class ChannelizerConfig(C.Structure):
+    _fields_ = [("n_sources", C.c_uint32), ("n_channels", C.c_uint32), ("decimation", C.c_uint32),
+                ("n_taps", C.c_uint32), ("taps", C.c_void_p), ("reserved", C.c_uint32 * 4)]
+
+
 class IqdError(RuntimeError):
     def __init__(self, status, detail):
         super().__init__("libiqdemod: %s (%d): %s" % (_lib().iqd_strerror(status).decode(), status, detail))
@@ -59,6 +65,9 @@ EXPORTS = [
     "iqd_resampler_create", "iqd_resampler_destroy", "iqd_resampler_reset", "iqd_resampler_out_count",
     "iqd_resampler_run", "iqd_resampler_run_device", "iqd_gather_unique_id", "iqd_gather_create", "iqd_gather_pcm", "iqd_gather_destroy",
     "iqd_demod_accept", "iqd_demod_set_sideband", "iqd_get_device", "iqd_gather_info", "iqd_device_count",
+    "iqd_channelizer_create", "iqd_channelizer_destroy", "iqd_channelizer_reset", "iqd_channelizer_set_channels",
+    "iqd_channelizer_run_device", "iqd_channelizer_run", "iqd_accept_wideband", "iqd_channelizer_phasor_table",
+    "iqd_channelizer_default_taps",
 ]
 
 _LIB = None
@@ -132,6 +141,16 @@ def _lib():
     L.iqd_get_frequency_trace.argtypes = [vp, u32, u32, vp, sz]
     L.iqd_stream.argtypes = [vp]
     L.iqd_stream.restype = vp
+    L.iqd_channelizer_create.argtypes = [vp, C.POINTER(ChannelizerConfig), C.POINTER(vp)]
+    L.iqd_channelizer_destroy.argtypes = [vp]
+    L.iqd_channelizer_destroy.restype = None
+    L.iqd_channelizer_reset.argtypes = [vp]
+    L.iqd_channelizer_set_channels.argtypes = [vp, u32, u32, vp, vp, vp]
+    L.iqd_channelizer_run_device.argtypes = [vp, vp, sz, vp]
+    L.iqd_channelizer_run.argtypes = [vp, vp, sz, vp]
+    L.iqd_accept_wideband.argtypes = [vp, vp, u32, vp, sz, vp, vp, vp, vp]
+    L.iqd_channelizer_phasor_table.argtypes = [vp]
+    L.iqd_channelizer_default_taps.argtypes = [u32, vp, u32]
     _LIB = L
     return L
 
@@ -155,6 +174,8 @@ class Engine:
         self.block_bytes = block_bytes or 32768
 
     def close(self):
+        for child in list(getattr(self, "_children", ())):   # channelizers go before their engine (include/iqdemod.h)
+            child.close()
         if getattr(self, "_h", None):
             self._L.iqd_destroy(self._h)
             self._h = C.c_void_p()
@@ -299,6 +320,21 @@ class Engine:
         allowed = np.zeros((n, max(nblk, 1)), dtype=np.uint8)
         self._check(self._L.iqd_accept_iq(self._h, f, n, _np_ptr(iq_u8), bpc, _np_ptr(pcm), _np_ptr(cnt),
                                           _np_ptr(mag), _np_ptr(allowed)))
+        return pcm, cnt, mag, allowed
+
+    def accept_wideband(self, chz, wide_u8, first=0):
+        """iqd_accept_wideband: one call's [n_sources, bytes_per_source] uint8 capture through the channelizer `chz` into
+        engine channels [first, first + chz.n_channels).  Returns (pcm rows, counts, magnitude, allowed) like accept()."""
+        wide = np.ascontiguousarray(wide_u8, dtype=np.uint8).reshape(chz.n_sources, -1)
+        bps = wide.shape[1]
+        row, n = bps // chz.decimation, chz.n_channels
+        nblk = row // self.block_bytes if row % self.block_bytes == 0 else 1
+        pcm = np.zeros((n, row // 64), dtype=np.int16)
+        cnt = np.zeros(n, dtype=np.uint32)
+        mag = np.zeros((n, nblk), dtype=np.uint32)
+        allowed = np.zeros((n, nblk), dtype=np.uint8)
+        self._check(self._L.iqd_accept_wideband(self._h, chz._h, first, _np_ptr(wide), bps, _np_ptr(pcm), _np_ptr(cnt),
+                                                _np_ptr(mag), _np_ptr(allowed)))
         return pcm, cnt, mag, allowed
 
     def front_end(self, iq_u8, first=0, n=None):
@@ -478,3 +514,83 @@ class Resampler:
             self._L.iqd_resampler_destroy(self._h)
             self._h = None
 
+
+
+def channelizer_phasor_table():
+    """The channelizer's phasor table P[i] = (c, s), [4096, 2] int16 (host only, no GPU)."""
+    out = np.zeros(8192, np.int16)
+    rc = _lib().iqd_channelizer_phasor_table(_np_ptr(out))
+    if rc != 0:
+        raise IqdError(rc, "iqd_channelizer_phasor_table")
+    return out.reshape(4096, 2)
+
+
+def channelizer_default_taps(decimation):
+    """The library's default Q15 prototype for decimation M (host only, no GPU)."""
+    L = _lib()
+    n = L.iqd_channelizer_default_taps(int(decimation), None, 0)
+    if n < 0:
+        raise IqdError(n, "no default taps for decimation %r" % (decimation,))
+    out = np.zeros(n, np.int16)
+    L.iqd_channelizer_default_taps(int(decimation), _np_ptr(out), n)
+    return out
+
+
+def phase_inc(offset_hz, fs):
+    """The channelizer's phase increment for a channel at offset_hz from the capture's centre (f = int32(d) / 2^32 fs)."""
+    return int(round(float(offset_hz) / float(fs) * 2.0 ** 32)) & 0xffffffff
+
+
+class Channelizer:
+    """iqd_channelizer_*: n_channels channels cut out of n_sources wideband captures at decimation x 256 kS/s."""
+
+    def __init__(self, engine, decimation, n_channels, n_sources=1, taps=None):
+        self._e, self._L = engine, engine._L
+        self._h = None
+        self.decimation, self.n_channels, self.n_sources = int(decimation), int(n_channels), int(n_sources)
+        self._taps = None if taps is None else np.ascontiguousarray(taps, np.int16)
+        cfg = ChannelizerConfig(self.n_sources, self.n_channels, self.decimation,
+                                0 if self._taps is None else len(self._taps),
+                                None if self._taps is None else self._taps.ctypes.data)
+        h = C.c_void_p()
+        engine._check(self._L.iqd_channelizer_create(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        if not hasattr(engine, "_children"):
+            engine._children = weakref.WeakSet()
+        engine._children.add(self)
+
+    def set_channels(self, first=0, source=None, offset_hz=None, fs=None, phase_inc=None, gain_shift=None, n=None):
+        """Retunes channels [first, first + n): offsets in Hz with the capture's rate fs, or raw increments; a field left
+        None keeps its value."""
+        if offset_hz is not None:
+            phase_inc = [globals()["phase_inc"](f, fs) for f in np.atleast_1d(offset_hz)]
+        arrs = [None if v is None else np.atleast_1d(np.asarray(v)) for v in (source, phase_inc, gain_shift)]
+        if n is None:
+            n = max(len(a) for a in arrs if a is not None)
+        src = None if arrs[0] is None else np.ascontiguousarray(np.broadcast_to(arrs[0], n), np.uint32)
+        inc = None if arrs[1] is None else np.ascontiguousarray(np.broadcast_to(arrs[1].astype(np.uint64) & 0xffffffff, n), np.uint32)
+        sh = None if arrs[2] is None else np.ascontiguousarray(np.broadcast_to(arrs[2], n), np.uint8)
+        self._e._check(self._L.iqd_channelizer_set_channels(self._h, int(first), int(n), _np_ptr(src), _np_ptr(inc),
+                                                            _np_ptr(sh)))
+
+    def run(self, wide_u8):
+        """[n_sources, bytes_per_source] uint8 -> [n_channels, bytes_per_source / M] uint8 (host arrays)."""
+        wide = np.ascontiguousarray(wide_u8, dtype=np.uint8).reshape(self.n_sources, -1)
+        out = np.zeros((self.n_channels, wide.shape[1] // self.decimation), np.uint8)
+        self._e._check(self._L.iqd_channelizer_run(self._h, _np_ptr(wide), wide.shape[1], _np_ptr(out)))
+        return out
+
+    def run_device(self, wide_dev, bytes_per_source, out_dev):
+        self._e._check(self._L.iqd_channelizer_run_device(self._h, C.c_void_p(wide_dev), int(bytes_per_source),
+                                                          C.c_void_p(out_dev)))
+
+    def reset(self):
+        self._e._check(self._L.iqd_channelizer_reset(self._h))
+
+    def close(self):
+        """iqd_channelizer_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
+        if self._h and self._e._h:
+            self._L.iqd_channelizer_destroy(self._h)
+        self._h = None
+
+    __del__ = close

@@ -1,0 +1,521 @@
+// Wideband channelizer, host side (include/iqdemod.h: iqd_channelizer_*, iqd_accept_wideband).
+//
+// Keeps the prototype, every channel's (source, increment, gain shift) and complex taps, groups the channels by source
+// into tiles of 8 (padding slots have zero taps and store nothing), packs the tiles' taps as MFMA A operands
+// (iqd_chan.h) and queues the kernel of iqd_chan.hip on the engine's stream.  Only the channels a set_channels call
+// names get new taps; the packing is redone at the next run.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "iqdemod.h"
+#include "iqd_chan.h"
+
+using namespace iqd;
+
+namespace {
+
+struct Buf {
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes)
+    {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// Page-locked staging of a tap upload: the copies read it after the host call returned, so a slot is refilled only once
+// the event behind its last copies has passed (two slots: the wait is for the upload before the previous one).
+struct Staging {
+    void *h = nullptr;
+    size_t cap = 0;
+    hipEvent_t done = nullptr;
+    bool pending = false;
+    hipError_t ensure(size_t bytes)
+    {
+        if (!done) {
+            hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+            if (e != hipSuccess) return e;
+        }
+        if (pending) {
+            hipError_t e = hipEventSynchronize(done);
+            if (e != hipSuccess) return e;
+            pending = false;
+        }
+        if (bytes <= cap) return hipSuccess;
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+        cap = 0;
+        hipError_t e = hipHostMalloc(&h, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    void release()
+    {
+        if (done) {
+            if (pending) (void)hipEventSynchronize(done);
+            (void)hipEventDestroy(done);
+        }
+        if (h) (void)hipHostFree(h);
+        *this = Staging();
+    }
+};
+
+double bessel_i0(double x)
+{
+    double sum = 1, term = 1;
+    for (int k = 1; k < 200; k++) {
+        const double f = x / (2.0 * k);
+        term *= f * f;
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return sum;
+}
+
+}  // namespace
+
+struct iqd_channelizer {
+    iqd_t *e = nullptr;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint32_t n_src = 0, n_ch = 0, m = 0, k = 0, kp = 0, nq = 0;
+    std::vector<int16_t> h, phasor;               // prototype [K]; (c, s) pairs [8192]
+    std::vector<uint32_t> src, inc;
+    std::vector<uint8_t> shift;
+    std::vector<int16_t> gr, gi;                  // [n_ch][K]
+    bool layout_dirty = true;                     // a channel changed source: regroup
+    std::vector<uint8_t> ch_dirty;                // new taps since the last packing
+    bool any_dirty = true;
+    uint64_t m_abs = 0;                           // outputs per channel since create / reset
+    std::vector<ChzTile> tiles;
+    std::vector<ChzWg> wgs;
+    std::vector<uint32_t> slot_of;                // [n_ch]: tile * 8 + slot
+    std::vector<uint8_t> amat;                    // [n_tiles][nq][2][64][16]
+    Buf d_amat, d_tiles, d_wgs, d_phasor, d_hist[2], st_wide, st_out;
+    Buf w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
+    Staging stg[2];                               // tap uploads
+    int stg_cur = 0;
+    int cur = 0;
+
+    int fail(int code, const char *msg) { return engine_fail(e, code, msg); }
+};
+
+#define CHZ_TRY(z, call)                                                                                  \
+    do {                                                                                                  \
+        hipError_t err_ = (call);                                                                         \
+        if (err_ != hipSuccess) return (z)->fail(IQD_EHIP, hipGetErrorString(err_));                      \
+    } while (0)
+
+namespace iqd {
+
+void chz_phasor_table(int16_t *out)
+{
+    for (int i = 0; i < (int)CHZ_PHASOR; i++) {
+        const double ph = 2.0 * M_PI * i / CHZ_PHASOR;
+        out[2 * i] = (int16_t)lrint(32767.0 * cos(ph));
+        out[2 * i + 1] = (int16_t)lrint(32767.0 * sin(ph));
+    }
+}
+
+void chz_channel_taps(const int16_t *h, uint32_t k, uint32_t inc, const int16_t *phasor, int16_t *gr, int16_t *gi)
+{
+    for (uint32_t j = 0; j < k; j++) {
+        const uint32_t i = (uint32_t)(j * inc) >> 20;
+        gr[j] = (int16_t)(((int32_t)h[j] * phasor[2 * i] + (1 << 14)) >> 15);
+        gi[j] = (int16_t)(((int32_t)h[j] * phasor[2 * i + 1] + (1 << 14)) >> 15);
+    }
+}
+
+}  // namespace iqd
+
+static void chz_new_taps(iqd_channelizer *z, uint32_t c)
+{
+    chz_channel_taps(z->h.data(), z->k, z->inc[c], z->phasor.data(), &z->gr[(size_t)c * z->k], &z->gi[(size_t)c * z->k]);
+    z->ch_dirty[c] = 1;
+    z->any_dirty = true;
+}
+
+// channels sorted by source, 8 per tile, up to CHZ_WAVES tiles of one source per workgroup row
+static void chz_group(iqd_channelizer *z)
+{
+    z->tiles.clear();
+    z->wgs.clear();
+    z->slot_of.assign(z->n_ch, 0);
+    std::vector<std::vector<uint32_t>> by_src(z->n_src);
+    for (uint32_t c = 0; c < z->n_ch; c++) by_src[z->src[c]].push_back(c);
+    for (uint32_t s = 0; s < z->n_src; s++) {
+        const auto &list = by_src[s];
+        const uint32_t first_tile = (uint32_t)z->tiles.size();
+        for (size_t i = 0; i < list.size(); i += CHZ_TILE_CH) {
+            ChzTile t;
+            for (uint32_t l = 0; l < CHZ_TILE_CH; l++) {
+                t.ch[l] = i + l < list.size() ? list[i + l] : CHZ_NONE;
+                if (t.ch[l] != CHZ_NONE) z->slot_of[t.ch[l]] = (uint32_t)z->tiles.size() * CHZ_TILE_CH + l;
+            }
+            z->tiles.push_back(t);
+        }
+        const uint32_t n_tiles = (uint32_t)z->tiles.size() - first_tile;
+        for (uint32_t t = 0; t < n_tiles; t += CHZ_WAVES)
+            z->wgs.push_back(ChzWg{s, first_tile + t, std::min(CHZ_WAVES, n_tiles - t), 0});
+    }
+    z->amat.assign(z->tiles.size() * z->nq * 2 * 64 * 16, 0);
+    std::fill(z->ch_dirty.begin(), z->ch_dirty.end(), 1);
+}
+
+// A operands of one tile slot (iqd_chan.h): rows 2 l (Ar) and 2 l + 1 (Ai), both planes, every K-chunk
+static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
+{
+    ChzTile &t = z->tiles[tile];
+    const uint32_t c = t.ch[l];
+    t.inc[l] = c == CHZ_NONE ? 0 : z->inc[c];
+    t.shift[l] = c == CHZ_NONE ? 0 : z->shift[c];
+    for (uint32_t row = 0; row < 2; row++) {
+        const uint32_t rho = 2 * l + row;
+        for (uint32_t q = 0; q < z->nq; q++)
+            for (uint32_t g = 0; g < 4; g++)
+                for (uint32_t j = 0; j < 16; j++) {
+                    const uint32_t kappa = 64 * q + 16 * g + j, comp = kappa & 1;
+                    const uint32_t kk = z->kp - 1 - kappa / 2;
+                    int32_t v = 0;
+                    if (c != CHZ_NONE && kk < z->k) {
+                        const int32_t r = z->gr[(size_t)c * z->k + kk], i = z->gi[(size_t)c * z->k + kk];
+                        v = row == 0 ? (comp == 0 ? r : -i) : (comp == 0 ? i : r);
+                    }
+                    const int8_t lo = (int8_t)(v & 0xff);
+                    const int8_t hi = (int8_t)((v - lo) / 256);
+                    const size_t lane = rho + 16 * g;
+                    for (uint32_t p = 0; p < 2; p++)
+                        z->amat[((((size_t)tile * z->nq + q) * 2 + p) * 64 + lane) * 16 + j] = (uint8_t)(p == 0 ? lo : hi);
+                }
+    }
+}
+
+// Packs the tiles that hold a channel with new parameters and queues their upload on the engine's stream (runs of
+// consecutive such tiles as one copy each; after a regrouping, everything).  No host synchronisation: the bytes go
+// through page-locked staging.
+static int chz_upload(iqd_channelizer *z)
+{
+    const bool regroup = z->layout_dirty;
+    if (regroup) chz_group(z);
+    const size_t n_tiles = z->tiles.size(), tile_bytes = (size_t)z->nq * 2 * 64 * 16;
+    std::vector<uint8_t> tile_dirty(n_tiles, regroup ? 1 : 0);
+    for (uint32_t t = 0; t < n_tiles; t++)
+        for (uint32_t l = 0; l < CHZ_TILE_CH; l++) {
+            const uint32_t c = z->tiles[t].ch[l];
+            if (regroup || (c != CHZ_NONE && z->ch_dirty[c])) {
+                chz_pack_slot(z, t, l);
+                tile_dirty[t] = 1;
+            }
+        }
+    std::fill(z->ch_dirty.begin(), z->ch_dirty.end(), 0);
+    if (regroup) {
+        CHZ_TRY(z, z->d_amat.ensure(z->amat.size()));
+        CHZ_TRY(z, z->d_tiles.ensure(n_tiles * sizeof(ChzTile)));
+        CHZ_TRY(z, z->d_wgs.ensure(z->wgs.size() * sizeof(ChzWg)));
+    }
+    struct Run { size_t first, n; };
+    std::vector<Run> runs;
+    size_t bytes = regroup ? z->wgs.size() * sizeof(ChzWg) : 0;
+    for (size_t t = 0; t < n_tiles; t++) {
+        if (!tile_dirty[t]) continue;
+        if (!runs.empty() && runs.back().first + runs.back().n == t) runs.back().n++;
+        else runs.push_back(Run{t, 1});
+        bytes += tile_bytes + sizeof(ChzTile);
+    }
+    Staging &st = z->stg[z->stg_cur];
+    CHZ_TRY(z, st.ensure(bytes ? bytes : 16));
+    uint8_t *h = (uint8_t *)st.h;
+    size_t at = 0;
+    auto copy = [&](void *dst, const void *src, size_t n) {
+        memcpy(h + at, src, n);
+        const hipError_t e = hipMemcpyAsync(dst, h + at, n, hipMemcpyHostToDevice, z->stream);
+        at += n;
+        return e;
+    };
+    for (const Run &r : runs) {
+        CHZ_TRY(z, copy((uint8_t *)z->d_amat.p + r.first * tile_bytes, &z->amat[r.first * tile_bytes], r.n * tile_bytes));
+        CHZ_TRY(z, copy((ChzTile *)z->d_tiles.p + r.first, &z->tiles[r.first], r.n * sizeof(ChzTile)));
+    }
+    if (regroup) CHZ_TRY(z, copy(z->d_wgs.p, z->wgs.data(), z->wgs.size() * sizeof(ChzWg)));
+    CHZ_TRY(z, hipEventRecord(st.done, z->stream));
+    st.pending = true;
+    z->stg_cur ^= 1;
+    z->layout_dirty = false;
+    z->any_dirty = false;
+    return IQD_OK;
+}
+
+static int chz_fill_history(iqd_channelizer *z)   // zero history: offset-binary 0x80
+{
+    CHZ_TRY(z, hipMemsetAsync(z->d_hist[z->cur].p, 0x80, (size_t)z->n_src * 2 * z->kp, z->stream));
+    z->m_abs = 0;
+    return IQD_OK;
+}
+
+extern "C" {
+
+int iqd_channelizer_phasor_table(int16_t out[8192])
+{
+    if (!out) return IQD_EINVAL;
+    chz_phasor_table(out);
+    return IQD_OK;
+}
+
+// Kaiser-windowed sinc (beta 5, cut-off 124 kHz at the wide rate, 13 M + 1 taps), quantised to Q15; the centre tap takes
+// up the rounding so that the DC gain is exactly 32768.  Stopband from 156 kHz >= 53 dB, passband +-100 kHz ripple
+// 0.32 dB (tests/test_chan_host.py checks the quantised taps for M in 2..64).
+int iqd_channelizer_default_taps(uint32_t decimation, int16_t *out, uint32_t capacity)
+{
+    if (decimation < 2 || decimation > 64 || (!out && capacity)) return IQD_EINVAL;
+    const uint32_t n = 13 * decimation + 1;
+    const double fc = 124.0 / (256.0 * decimation), beta = 5.0, i0b = bessel_i0(beta);
+    std::vector<double> w(n);
+    double sum = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const double x = (double)i - (n - 1) / 2.0, r = 2.0 * i / (n - 1) - 1.0;
+        const double sinc = x == 0 ? 1.0 : sin(2 * M_PI * fc * x) / (2 * M_PI * fc * x);
+        w[i] = 2 * fc * sinc * bessel_i0(beta * sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+        sum += w[i];
+    }
+    std::vector<int32_t> q(n);
+    int32_t qs = 0;
+    for (uint32_t i = 0; i < n; i++) qs += q[i] = (int32_t)lrint(w[i] / sum * 32768.0);
+    q[(n - 1) / 2] += 32768 - qs;
+    for (uint32_t i = 0; i < n && i < capacity; i++) out[i] = (int16_t)q[i];
+    return (int)n;
+}
+
+int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_channelizer_t **out)
+{
+    if (!e) return IQD_EINVAL;
+    if (!cfg || !out) return engine_fail(e, IQD_EINVAL, "NULL config or output pointer");
+    if (cfg->n_sources < 1 || cfg->n_channels < 1 || cfg->decimation < 2 || cfg->decimation > 64)
+        return engine_fail(e, IQD_EINVAL, "channelizer: n_sources, n_channels >= 1 and 2 <= decimation <= 64");
+    for (uint32_t r : cfg->reserved)
+        if (r) return engine_fail(e, IQD_EINVAL, "channelizer: reserved fields must be 0");
+    std::vector<int16_t> h;
+    if (cfg->taps) {
+        if (cfg->n_taps < 1 || cfg->n_taps > 1024) return engine_fail(e, IQD_EINVAL, "channelizer: 1 <= n_taps <= 1024");
+        h.assign(cfg->taps, cfg->taps + cfg->n_taps);
+    } else {
+        h.resize(iqd_channelizer_default_taps(cfg->decimation, nullptr, 0));
+        iqd_channelizer_default_taps(cfg->decimation, h.data(), (uint32_t)h.size());
+    }
+    int64_t abs_sum = 0;
+    for (int16_t t : h) {
+        if (t > 32639 || t < -32639) return engine_fail(e, IQD_EINVAL, "channelizer: |h[k]| must be <= 32639");
+        abs_sum += t < 0 ? -t : t;
+    }
+    if (256 * abs_sum > 2147483647LL - 255) return engine_fail(e, IQD_EINVAL, "channelizer: 256 sum |h| must be <= 2^31 - 256");
+    if (cfg->n_channels > (1u << 20) || cfg->n_sources > (1u << 20)) return engine_fail(e, IQD_EINVAL, "channelizer: too many channels or sources");
+
+    iqd_channelizer *z = new (std::nothrow) iqd_channelizer;
+    if (!z) return engine_fail(e, IQD_ENOMEM, "channelizer: host allocation failed");
+    z->e = e;
+    (void)iqd_get_device(e, &z->device);
+    z->stream = (hipStream_t)iqd_stream(e);
+    (void)hipSetDevice(z->device);
+    z->n_src = cfg->n_sources;
+    z->n_ch = cfg->n_channels;
+    z->m = cfg->decimation;
+    z->h = h;
+    z->k = (uint32_t)h.size();
+    z->kp = (z->k + 31) / 32 * 32;
+    z->nq = z->kp / 32;
+    z->phasor.resize(2 * CHZ_PHASOR);
+    chz_phasor_table(z->phasor.data());
+    z->src.assign(z->n_ch, 0);
+    z->inc.assign(z->n_ch, 0);
+    z->shift.assign(z->n_ch, 0);
+    z->gr.assign((size_t)z->n_ch * z->k, 0);
+    z->gi.assign((size_t)z->n_ch * z->k, 0);
+    z->ch_dirty.assign(z->n_ch, 0);
+    for (uint32_t c = 0; c < z->n_ch; c++) chz_new_taps(z, c);
+    std::vector<uint32_t> packed(CHZ_PHASOR);
+    for (uint32_t i = 0; i < CHZ_PHASOR; i++)
+        packed[i] = (uint16_t)z->phasor[2 * i] | ((uint32_t)(uint16_t)z->phasor[2 * i + 1] << 16);
+    const size_t hb = (size_t)z->n_src * 2 * z->kp;
+    bool ok = z->d_phasor.ensure(CHZ_PHASOR * 4) == hipSuccess && z->d_hist[0].ensure(hb) == hipSuccess &&
+              z->d_hist[1].ensure(hb) == hipSuccess;
+    ok = ok && hipMemcpy(z->d_phasor.p, packed.data(), CHZ_PHASOR * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && chz_fill_history(z) == IQD_OK && hipStreamSynchronize(z->stream) == hipSuccess;
+    if (!ok) {
+        iqd_channelizer_destroy(z);
+        return engine_fail(e, IQD_ENOMEM, "channelizer: device allocation failed");
+    }
+    *out = z;
+    return IQD_OK;
+}
+
+void iqd_channelizer_destroy(iqd_channelizer_t *z)
+{
+    if (!z) return;
+    (void)hipSetDevice(z->device);
+    (void)hipStreamSynchronize(z->stream);
+    for (Buf *b : {&z->d_amat, &z->d_tiles, &z->d_wgs, &z->d_phasor, &z->d_hist[0], &z->d_hist[1], &z->st_wide, &z->st_out,
+                   &z->w_rows, &z->w_pcm, &z->w_cnt, &z->w_mag, &z->w_sp})
+        b->release();
+    z->stg[0].release();
+    z->stg[1].release();
+    delete z;
+}
+
+int iqd_channelizer_reset(iqd_channelizer_t *z)
+{
+    if (!z) return IQD_EINVAL;
+    (void)hipSetDevice(z->device);
+    return chz_fill_history(z);
+}
+
+int iqd_channelizer_set_channels(iqd_channelizer_t *z, uint32_t first, uint32_t n, const uint32_t *source,
+                                 const uint32_t *phase_inc, const uint8_t *gain_shift)
+{
+    if (!z) return IQD_EINVAL;
+    if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
+    for (uint32_t i = 0; i < n; i++) {
+        if (source && source[i] >= z->n_src) return z->fail(IQD_EINVAL, "channelizer: source index out of range");
+        if (gain_shift && gain_shift[i] > 8) return z->fail(IQD_EINVAL, "channelizer: gain shift must be 0..8");
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t c = first + i;
+        if (source && source[i] != z->src[c]) {
+            z->src[c] = source[i];
+            z->layout_dirty = true;
+        }
+        if (gain_shift) z->shift[c] = gain_shift[i];
+        if (phase_inc) z->inc[c] = phase_inc[i];
+        z->ch_dirty[c] = 1;
+        z->any_dirty = true;
+        if (phase_inc) chz_new_taps(z, c);
+    }
+    return IQD_OK;
+}
+
+static int chz_check_len(iqd_channelizer *z, size_t bytes_per_source)
+{
+    if (bytes_per_source == 0 || bytes_per_source % (64 * (size_t)z->m) != 0)
+        return z->fail(IQD_EINVAL, "channelizer: bytes_per_source must be a positive multiple of 64 * decimation");
+    if (bytes_per_source > 0x7fffffffull) return z->fail(IQD_EINVAL, "channelizer: bytes_per_source too large");
+    return IQD_OK;
+}
+
+int iqd_channelizer_run_device(iqd_channelizer_t *z, const void *wide_dev, size_t bytes_per_source, void *out_dev)
+{
+    if (!z) return IQD_EINVAL;
+    if (!wide_dev || !out_dev) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
+    if ((((uintptr_t)wide_dev) | ((uintptr_t)out_dev)) & 15) return z->fail(IQD_EINVAL, "channelizer: buffers must be 16-byte aligned");
+    int rc = chz_check_len(z, bytes_per_source);
+    if (rc != IQD_OK) return rc;
+    (void)hipSetDevice(z->device);
+    if (z->any_dirty || z->layout_dirty) {
+        rc = chz_upload(z);
+        if (rc != IQD_OK) return rc;
+    }
+    const uint32_t n_out = (uint32_t)(bytes_per_source / (2 * z->m));   // a multiple of 32
+    uint32_t t_max = std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - z->kp) / z->m) / CHZ_GROUP * CHZ_GROUP;
+    ChzLaunch a{};
+    a.wide = (const uint8_t *)wide_dev;
+    a.hist = (const uint8_t *)z->d_hist[z->cur].p;
+    a.hist_next = (uint8_t *)z->d_hist[z->cur ^ 1].p;
+    a.phasor = (const uint32_t *)z->d_phasor.p;
+    a.amat = (const uint4 *)z->d_amat.p;
+    a.tiles = (const ChzTile *)z->d_tiles.p;
+    a.wgs = (const ChzWg *)z->d_wgs.p;
+    a.out = (uint8_t *)out_dev;
+    a.bytes_per_source = bytes_per_source;
+    a.n_sources = z->n_src;
+    a.out_row = 2 * n_out;
+    a.n_out = n_out;
+    a.m = z->m;
+    a.kp = z->kp;
+    a.nq = z->nq;
+    a.t_blk = n_out <= t_max ? n_out : t_max;
+    a.nbase = (uint32_t)(z->m_abs * z->m);
+    CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->stream));
+    z->cur ^= 1;
+    z->m_abs += n_out;
+    return IQD_OK;
+}
+
+int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_per_source, uint8_t *out)
+{
+    if (!z) return IQD_EINVAL;
+    if (!wide || !out) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
+    int rc = chz_check_len(z, bytes_per_source);
+    if (rc != IQD_OK) return rc;
+    (void)hipSetDevice(z->device);
+    const size_t ib = (size_t)z->n_src * bytes_per_source, ob = (size_t)z->n_ch * (bytes_per_source / z->m);
+    CHZ_TRY(z, z->st_wide.ensure(ib));
+    CHZ_TRY(z, z->st_out.ensure(ob));
+    CHZ_TRY(z, hipMemcpyAsync(z->st_wide.p, wide, ib, hipMemcpyHostToDevice, z->stream));
+    rc = iqd_channelizer_run_device(z, z->st_wide.p, bytes_per_source, z->st_out.p);
+    if (rc != IQD_OK) return rc;
+    CHZ_TRY(z, hipMemcpyAsync(out, z->st_out.p, ob, hipMemcpyDeviceToHost, z->stream));
+    CHZ_TRY(z, hipStreamSynchronize(z->stream));
+    return IQD_OK;
+}
+
+int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const uint8_t *wide, size_t bytes_per_source,
+                        int16_t *pcm, uint32_t *pcm_count, uint32_t *magnitude, uint8_t *signal_present)
+{
+    if (!e) return IQD_EINVAL;
+    if (!z || z->e != e) return engine_fail(e, IQD_EINVAL, "accept_wideband: the channelizer belongs to another engine");
+    if (!wide || !pcm) return z->fail(IQD_EINVAL, "accept_wideband: NULL buffer");
+    int rc = chz_check_len(z, bytes_per_source);
+    if (rc != IQD_OK) return rc;
+    uint32_t e_nch = 0, bb = 0, flags = 0;
+    engine_geometry(e, &e_nch, &bb, &flags);
+    if (first_ch >= e_nch || z->n_ch > e_nch - first_ch) return z->fail(IQD_EINVAL, "accept_wideband: bad engine channel range");
+    const size_t row = bytes_per_source / z->m;
+    if (row % bb != 0 && (row >= bb || row % 64 != 0))
+        return z->fail(IQD_EINVAL, "accept_wideband: bytes_per_source / decimation must be a multiple of block_bytes, or one short block");
+    const size_t nblk = row % bb == 0 ? row / bb : 1;
+    (void)hipSetDevice(z->device);
+    const size_t n = z->n_ch, ib = (size_t)z->n_src * bytes_per_source;
+    CHZ_TRY(z, z->st_wide.ensure(ib));
+    CHZ_TRY(z, z->w_rows.ensure(n * row));
+    CHZ_TRY(z, z->w_pcm.ensure(n * (row / 64) * 2));
+    CHZ_TRY(z, z->w_cnt.ensure(n * 4));
+    CHZ_TRY(z, z->w_mag.ensure(n * nblk * 4));
+    CHZ_TRY(z, z->w_sp.ensure(n * nblk));
+    CHZ_TRY(z, hipMemcpyAsync(z->st_wide.p, wide, ib, hipMemcpyHostToDevice, z->stream));
+    rc = iqd_channelizer_run_device(z, z->st_wide.p, bytes_per_source, z->w_rows.p);
+    if (rc != IQD_OK) return rc;
+    if (flags & IQD_F_PREPASS_OVERLAP) CHZ_TRY(z, hipStreamSynchronize(z->stream));   // that path wants its input complete
+    rc = iqd_accept_iq_device(e, first_ch, z->n_ch, z->w_rows.p, row, z->w_pcm.p, z->w_cnt.p,
+                              magnitude ? z->w_mag.p : nullptr, signal_present ? z->w_sp.p : nullptr);
+    if (rc != IQD_OK) {
+        // The checks above are the engine's own (range, block_bytes rule), so it does not refuse these rows; should it
+        // still, the channelizer steps back as well: the call's history went to the other buffer, so the stream stands
+        // where it stood before the call, like the engine's.
+        z->cur ^= 1;
+        z->m_abs -= bytes_per_source / (2 * z->m);
+        return rc;
+    }
+    CHZ_TRY(z, hipMemcpyAsync(pcm, z->w_pcm.p, n * (row / 64) * 2, hipMemcpyDeviceToHost, z->stream));
+    if (pcm_count) CHZ_TRY(z, hipMemcpyAsync(pcm_count, z->w_cnt.p, n * 4, hipMemcpyDeviceToHost, z->stream));
+    if (magnitude) CHZ_TRY(z, hipMemcpyAsync(magnitude, z->w_mag.p, n * nblk * 4, hipMemcpyDeviceToHost, z->stream));
+    if (signal_present) CHZ_TRY(z, hipMemcpyAsync(signal_present, z->w_sp.p, n * nblk, hipMemcpyDeviceToHost, z->stream));
+    CHZ_TRY(z, hipStreamSynchronize(z->stream));
+    return IQD_OK;
+}
+
+}  // extern "C"

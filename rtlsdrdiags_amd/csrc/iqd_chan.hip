@@ -1,0 +1,199 @@
+// Wideband channelizer kernel (include/iqdemod.h: iqd_channelizer_*; layout of the operands: iqd_chan.h).
+//
+// Grid: x = blocks of t_blk outputs, y = workgroup rows (ChzWg: up to 8 tiles of 8 channels, all of one source).
+// A workgroup stages its source's window - bytes [2 M m0 - 2 Kp, 2 M (m0 + n)) of [history | this call], made signed -
+// and the phasor table in LDS; each wave then owns one tile of 8 channels and walks the block in groups of 64 outputs
+// (four 16-output MFMA tiles, two at a time: four independent accumulator chains):
+//   MFMA   per 64-byte K-chunk q and tap plane p: acc[t][p] += A[q][p] x B[t][q], B read from the window (the window of
+//          output j starts at byte 2 M (j + 1), 2-byte aligned for odd M: five dwords and v_alignbyte per operand)
+//   VALU   A = lo + 256 hi, a = sat16((A + 128) >> 8), phasor from LDS, rotation on v_dot2_i32_i16, round / saturate,
+//          byte pack into a per-wave LDS staging row of 8 channels x 128 bytes
+//   store  one 16-byte store per lane: 8 lanes write one channel's 128 contiguous bytes (whole sectors)
+// A second, tiny kernel writes each source's last Kp samples (the next call's history) with vector stores.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "iqd_chan.h"
+
+namespace iqd {
+
+typedef int chz_v4i __attribute__((ext_vector_type(4)));
+typedef short chz_s2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ int32_t chz_sat(int32_t x, int32_t lo, int32_t hi) { return min(max(x, lo), hi); }
+
+__device__ __forceinline__ void chz_wave_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// B operand: 16 window bytes at LDS byte offset o (o even)
+__device__ __forceinline__ chz_v4i chz_b_operand(const uint8_t *win, uint32_t o)
+{
+    const uint32_t *w = (const uint32_t *)(win + (o & ~3u));
+    const uint32_t sh = o & 3u;
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+    chz_v4i b;
+    b.x = (int)__builtin_amdgcn_alignbyte(w1, w0, sh);
+    b.y = (int)__builtin_amdgcn_alignbyte(w2, w1, sh);
+    b.z = (int)__builtin_amdgcn_alignbyte(w3, w2, sh);
+    b.w = (int)__builtin_amdgcn_alignbyte(w4, w3, sh);
+    return b;
+}
+
+// one channel's output at one sample: the two rails' accumulators (lo / hi planes) -> two offset-binary bytes
+__device__ __forceinline__ uint32_t chz_epilogue(int32_t rlo, int32_t rhi, int32_t ilo, int32_t ihi, uint32_t p,
+                                                 int32_t rnd, uint32_t sh)
+{
+    // A = lo + 256 hi + 128 fits int32 (the tap bounds), but 256 hi alone need not: combined modulo 2^32
+    const int32_t Ar = (int32_t)((uint32_t)rlo + ((uint32_t)rhi << 8) + 128u);
+    const int32_t Ai = (int32_t)((uint32_t)ilo + ((uint32_t)ihi << 8) + 128u);
+    const int32_t ar = chz_sat(Ar >> 8, -32768, 32767);
+    const int32_t ai = chz_sat(Ai >> 8, -32768, 32767);
+    const int32_t c = (int16_t)(p & 0xffffu), s = (int16_t)(p >> 16);
+    const chz_s2 va = {(short)ar, (short)ai};
+    const chz_s2 vb = {(short)ai, (short)ar};
+    const chz_s2 cs = {(short)c, (short)s};
+    const chz_s2 cns = {(short)c, (short)-s};                          // |s| <= 32767: -s fits
+    const int32_t rr = __builtin_amdgcn_sdot2(va, cs, 0, false);       // ar c + ai s
+    const int32_t ri = __builtin_amdgcn_sdot2(vb, cns, 0, false);      // ai c - ar s
+    const int32_t yr = chz_sat((rr + rnd) >> sh, -128, 127), yi = chz_sat((ri + rnd) >> sh, -128, 127);
+    return (uint32_t)(yr + 128) | ((uint32_t)(yi + 128) << 8);
+}
+
+template <int NQR>   // NQR > 0: nq <= NQR, the A operands stay in registers; 0: they are read per group
+__global__ __launch_bounds__(512) void chz_kernel(const ChzLaunch a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t chz_lds[];
+    uint32_t *sp = (uint32_t *)chz_lds;
+    uint8_t *stage_all = chz_lds + CHZ_PHASOR * 4;
+    uint8_t *win = chz_lds + CHZ_LDS_FIXED;
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const ChzWg w = a.wgs[blockIdx.y];
+    const uint32_t m0 = blockIdx.x * a.t_blk;
+    const uint32_t nloc = min(a.t_blk, a.n_out - m0);           // a multiple of 32
+    const uint32_t M = a.m, kp = a.kp, nq = a.nq;
+
+    for (uint32_t i = tid; i < CHZ_PHASOR / 4; i += blockDim.x) ((uint4 *)sp)[i] = ((const uint4 *)a.phasor)[i];
+    {
+        const uint8_t *src = a.wide + (size_t)w.source * a.bytes_per_source;
+        const uint8_t *hsrc = a.hist + (size_t)w.source * 2 * kp;
+        const int64_t b0 = 2 * (int64_t)m0 * M - 2 * (int64_t)kp;   // 16-byte aligned, like the history's end
+        const uint32_t wbytes = 2 * (nloc * M + kp);
+        for (uint32_t i = tid * 16; i < wbytes; i += blockDim.x * 16) {
+            const int64_t b = b0 + i;
+            uint4 v = b < 0 ? *(const uint4 *)(hsrc + 2 * kp + b) : *(const uint4 *)(src + b);
+            v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
+            *(uint4 *)(win + i) = v;
+        }
+    }
+    __syncthreads();
+    if (wave >= w.n_tiles) return;
+
+    const uint32_t tile = w.first_tile + wave;
+    const ChzTile *T = a.tiles + tile;
+    const uint32_t col = lane & 15, g = lane >> 4;
+    uint32_t inc[2], shv[2];
+    int32_t rnd[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        inc[i] = T->inc[2 * g + i];
+        const uint32_t L = T->shift[2 * g + i];
+        shv[i] = 22 - L;
+        rnd[i] = 1 << (21 - L);
+    }
+    const uint32_t st_cl = lane >> 3, st_piece = lane & 7;
+    const uint32_t st_ch = T->ch[st_cl];
+    uint8_t *stage = stage_all + wave * (CHZ_TILE_CH * 2 * CHZ_GROUP);
+    const uint4 *amat = a.amat + (size_t)tile * nq * 2 * 64 + lane;
+
+    chz_v4i A[NQR > 0 ? NQR : 1][2];
+    if (NQR > 0) {
+#pragma unroll
+        for (int q = 0; q < NQR; q++)
+            if (q < (int)nq) {
+                A[q][0] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 0) * 64]);
+                A[q][1] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 1) * 64]);
+            }
+    }
+    const chz_v4i zero = {0, 0, 0, 0};
+
+    for (uint32_t grp = 0; grp * CHZ_GROUP < nloc; grp++) {
+        const uint32_t ntl = min(4u, (nloc - grp * CHZ_GROUP) / 16);   // 2 or 4
+        // two 16-output tiles at a time: four independent accumulator chains (tile x plane)
+        for (uint32_t tp = 0; tp < ntl; tp += 2) {
+            chz_v4i acc[2][2] = {{zero, zero}, {zero, zero}};
+            const uint32_t obase = 2 * M * (grp * CHZ_GROUP + 16 * tp + col + 1) + 16 * g;
+            if (NQR > 0) {
+#pragma unroll
+                for (int q = 0; q < NQR; q++)
+                    if (q < (int)nq) {
+#pragma unroll
+                        for (int t = 0; t < 2; t++) {
+                            const chz_v4i b = chz_b_operand(win, obase + 2 * M * 16 * t + 64 * q);
+                            acc[t][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[q][0], b, acc[t][0], 0, 0, 0);
+                            acc[t][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[q][1], b, acc[t][1], 0, 0, 0);
+                        }
+                    }
+            } else {
+                for (uint32_t q = 0; q < nq; q++) {
+                    const chz_v4i alo = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 0) * 64]);
+                    const chz_v4i ahi = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 1) * 64]);
+#pragma unroll
+                    for (int t = 0; t < 2; t++) {
+                        const chz_v4i b = chz_b_operand(win, obase + 2 * M * 16 * t + 64 * q);
+                        acc[t][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(alo, b, acc[t][0], 0, 0, 0);
+                        acc[t][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ahi, b, acc[t][1], 0, 0, 0);
+                    }
+                }
+            }
+            // epilogue: lane (col, g) holds rows 4 g .. 4 g + 3 = channels 2 g, 2 g + 1 (re, im) of output col of each tile
+#pragma unroll
+            for (int t = 0; t < 2; t++) {
+                const uint32_t jt = 16 * (tp + t) + col;                       // output within the group
+                const uint32_t n32 = a.nbase + (m0 + grp * CHZ_GROUP + jt) * M + M - 1;   // mod 2^32
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    const uint32_t p = sp[(n32 * inc[i]) >> 20];
+                    const uint32_t v = chz_epilogue(acc[t][0][2 * i], acc[t][1][2 * i], acc[t][0][2 * i + 1],
+                                                    acc[t][1][2 * i + 1], p, rnd[i], shv[i]);
+                    *(uint16_t *)(stage + (2 * g + i) * (2 * CHZ_GROUP) + 2 * jt) = (uint16_t)v;
+                }
+            }
+        }
+        chz_wave_fence();
+        if (st_ch != CHZ_NONE && st_piece * 8 < ntl * 16) {
+            const uint4 v = *(const uint4 *)(stage + st_cl * (2 * CHZ_GROUP) + 16 * st_piece);
+            *(uint4 *)(a.out + (size_t)st_ch * a.out_row + 2 * (size_t)(m0 + grp * CHZ_GROUP) + 16 * st_piece) = v;
+        }
+        chz_wave_fence();
+    }
+}
+
+// the next call's history: the last 2 kp bytes of [history | this call] per source
+__global__ void chz_history_kernel(const ChzLaunch a)
+{
+    const uint32_t hb = 2 * a.kp;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.n_sources * hb) return;
+    const uint32_t s = t / hb, i = t - s * hb;
+    const int64_t b = (int64_t)a.bytes_per_source - hb + i;
+    a.hist_next[t] = b < 0 ? a.hist[(size_t)s * hb + hb + b] : a.wide[(size_t)s * a.bytes_per_source + b];
+}
+
+hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s)
+{
+    const dim3 grid((a.n_out + a.t_blk - 1) / a.t_blk, n_wgs);
+    const size_t lds = CHZ_LDS_FIXED + 2 * ((size_t)a.t_blk * a.m + a.kp) + 16;
+    if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_kernel<CHZ_NQ_REG>, grid, dim3(512), lds, s, a);
+    else hipLaunchKernelGGL(chz_kernel<0>, grid, dim3(512), lds, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint32_t nh = a.n_sources * 2 * a.kp;
+    hipLaunchKernelGGL(chz_history_kernel, dim3((nh + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace iqd

@@ -26,6 +26,7 @@
 #include "iqd_taps.h"
 #include "iqd_wbfm.h"
 #include "iqd_chains.h"
+#include "iqd_chan.h"
 
 using namespace iqd;
 
@@ -203,6 +204,17 @@ static int family_of_mode(int mode)
     default: return FAM_COUNT;
     }
 }
+
+// The channelizer (iqd_chan.cpp) reports through the engine's error text and needs its call geometry.
+namespace iqd {
+int engine_fail(iqd_t *e, int code, const char *msg) { return e->fail(code, "%s", msg); }
+void engine_geometry(const iqd_t *e, uint32_t *n_ch, uint32_t *block_bytes, uint32_t *flags)
+{
+    *n_ch = e->n_ch;
+    *block_bytes = e->block_bytes;
+    *flags = e->flags;
+}
+}  // namespace iqd
 
 static bool range_ok(const iqd_t *e, uint32_t first, uint32_t n)
 {

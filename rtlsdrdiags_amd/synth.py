@@ -64,3 +64,26 @@ def stepped_amplitude(block_amplitudes, block_samples=16384, seed=1234, sigma=1.
         phase = -0.5 * np.pi * n + 30.0 * np.sin(2 * np.pi * 1000.0 * n / FS)
         out.append(_finish(amp * np.exp(1j * phase), sigma, rng))
     return np.concatenate(out)
+
+
+def wideband(n_samples, rate, stations, seed=1234, sigma=2.0):
+    """One wideband capture at `rate` (M x 256 kS/s): a sum of stations, each a dict with `offset` (Hz from the centre),
+    `kind` ('fm' / 'wbfm' / 'am' / 'usb' / 'lsb'), `amplitude`, `tone` (Hz) and for FM `deviation` (Hz), quantised to
+    offset-binary uint8 with white noise of `sigma`."""
+    rng = np.random.default_rng(seed)
+    n = np.arange(n_samples, dtype=np.float64)
+    z = np.zeros(n_samples, np.complex128)
+    for st in stations:
+        kind, amp, tone = st["kind"], st.get("amplitude", 30.0), st.get("tone", 1000.0)
+        carrier = 2 * np.pi * st["offset"] * n / rate
+        audio = 2 * np.pi * tone * n / rate
+        if kind in ("fm", "wbfm"):
+            dev = st.get("deviation", 5000.0 if kind == "fm" else 60000.0)
+            z += amp * np.exp(1j * (carrier + (dev / tone) * np.sin(audio)))
+        elif kind == "am":
+            z += amp * (1.0 + st.get("depth", 0.5) * np.sin(audio)) * np.exp(1j * carrier)
+        elif kind in ("usb", "lsb"):
+            z += amp * np.exp(1j * (carrier + (audio if kind == "usb" else -audio)))
+        else:
+            raise ValueError(kind)
+    return _finish(z, sigma, rng)
