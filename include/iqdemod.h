@@ -355,6 +355,45 @@ int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const
 int iqd_channelizer_phasor_table(int16_t out[8192]);
 int iqd_channelizer_default_taps(uint32_t decimation, int16_t *out, uint32_t capacity);
 
+/* Scanner-driven channels: a channelizer channel c may FOLLOW THE SCANNER of the engine channel it feeds in
+ * iqd_accept_wideband*(e, z, first_ch, ...), e_c = first_ch + c.  A following channel's row of one call is split into the
+ * engine's blocks (block_bytes, or the one short block); block b is cut by exactly the spec above with the increment d_b:
+ *
+ *   f_b       e_c's scanner frequency (iqd_scanner_get's current_hz) when block b begins: for b = 0 after the call's
+ *             pending settings are applied (a start() after new parameters has already jumped to the end frequency -
+ *             in the reference that tuning command precedes any data); for b > 0 after block b-1's squelch / scanner
+ *             step (the engine's frequency-trace entry of block b-1).  Scanning or not: a stopped scanner leaves the
+ *             channel where the scan stopped, as it would leave the dongle.
+ *   centre    f_b + 64000 r, r = e_c's rotation selector in force for the call (+1, the default: the reference's
+ *             "tune to station + Fs/4", Radio.cc:617-618).
+ *   offset    o = f_b + 64000 r - F_s exactly (no wrap-around), Fs = 256000 M, F_s = the source's centre
+ *             (iqd_channelizer_set_source_frequency, default 0).
+ *   in band   -Fs/2 <= o < Fs/2: d_b = floor((o 2^32 + Fs/2) / Fs) mod 2^32 (floor division), and everything else -
+ *             taps from d_b, the rotation P[(n d_b mod 2^32) >> 20] with absolute n, the gain shift, the history - as
+ *             above.
+ *   out of band  every byte of block b's row is 0x80 (silence: the squelch sees magnitude 0, the scanner moves on).
+ *
+ * This is the ideal retune: block b is cut at the frequency the scanner held when it began (the reference's dongle has
+ * blocks in flight on USB when it retunes; that latency is not modelled).  The AGC keeps its meaning (the IF gain the
+ * squelch compares with); it does not scale the channelizer's output.  The result is byte for byte what a host loop of
+ * one-block calls gives that retunes every channel from iqd_scanner_get + iqd_channelizer_tuning, writes 0x80 over the
+ * rows out of band and feeds iqd_accept_iq.  The decisions stay on the device: no host synchronisation per block, and
+ * the number of launches per call does not grow with the number of blocks.
+ *
+ * iqd_channelizer_follow_scanner(z, first, n, 1 / 0): while a channel follows, its set_channels increment is kept but
+ *             ignored (source and gain shift still apply); it is back in force at the next call after follow = 0.
+ *             iqd_channelizer_run / run_device return IQD_EINVAL while any channel follows (no engine channel to follow);
+ *             iqd_channelizer_reset keeps the following flags and source centres, as it keeps set_channels' values.
+ * iqd_channelizer_tuning: the rule above as a host-only function (no GPU): IQD_EINVAL when out of band.
+ * iqd_accept_wideband_device: iqd_accept_wideband with device pointers, queued on the engine's stream like
+ *             iqd_accept_iq_device.  rows_dev [n_channels][bytes_per_source / M] (16-byte aligned, as wide_dev) is the
+ *             caller's and holds the cut rows afterwards. */
+int iqd_channelizer_set_source_frequency(iqd_channelizer_t *z, uint32_t first_source, uint32_t n, const uint64_t *centre_hz);
+int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_t n, int follow);
+int iqd_channelizer_tuning(uint32_t decimation, uint64_t source_centre_hz, uint64_t station_hz, int rotation, uint32_t *inc);
+int iqd_accept_wideband_device(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const void *wide_dev, size_t bytes_per_source,
+                               void *rows_dev, void *pcm_dev, void *pcm_count_dev, void *magnitude_dev, void *signal_present_dev);
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

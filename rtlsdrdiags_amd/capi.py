@@ -67,7 +67,8 @@ EXPORTS = [
     "iqd_demod_accept", "iqd_demod_set_sideband", "iqd_get_device", "iqd_gather_info", "iqd_device_count",
     "iqd_channelizer_create", "iqd_channelizer_destroy", "iqd_channelizer_reset", "iqd_channelizer_set_channels",
     "iqd_channelizer_run_device", "iqd_channelizer_run", "iqd_accept_wideband", "iqd_channelizer_phasor_table",
-    "iqd_channelizer_default_taps",
+    "iqd_channelizer_default_taps", "iqd_channelizer_set_source_frequency", "iqd_channelizer_follow_scanner",
+    "iqd_channelizer_tuning", "iqd_accept_wideband_device",
 ]
 
 _LIB = None
@@ -151,6 +152,10 @@ def _lib():
     L.iqd_accept_wideband.argtypes = [vp, vp, u32, vp, sz, vp, vp, vp, vp]
     L.iqd_channelizer_phasor_table.argtypes = [vp]
     L.iqd_channelizer_default_taps.argtypes = [u32, vp, u32]
+    L.iqd_channelizer_set_source_frequency.argtypes = [vp, u32, u32, vp]
+    L.iqd_channelizer_follow_scanner.argtypes = [vp, u32, u32, C.c_int]
+    L.iqd_channelizer_tuning.argtypes = [u32, u64, u64, C.c_int, C.POINTER(u32)]
+    L.iqd_accept_wideband_device.argtypes = [vp, vp, u32, vp, sz, vp, vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -336,6 +341,14 @@ class Engine:
         self._check(self._L.iqd_accept_wideband(self._h, chz._h, first, _np_ptr(wide), bps, _np_ptr(pcm), _np_ptr(cnt),
                                                 _np_ptr(mag), _np_ptr(allowed)))
         return pcm, cnt, mag, allowed
+
+    def accept_wideband_device(self, chz, wide_dev, bytes_per_source, rows_dev, pcm_dev, count_dev=0, mag_dev=0,
+                               allowed_dev=0, first=0):
+        """iqd_accept_wideband_device: device pointers (integers), queued on the engine's stream; rows_dev receives the
+        cut rows [n_channels, bytes_per_source / M]."""
+        self._check(self._L.iqd_accept_wideband_device(self._h, chz._h, int(first), C.c_void_p(wide_dev), int(bytes_per_source),
+                                                       C.c_void_p(rows_dev), C.c_void_p(pcm_dev), C.c_void_p(count_dev or None),
+                                                       C.c_void_p(mag_dev or None), C.c_void_p(allowed_dev or None)))
 
     def front_end(self, iq_u8, first=0, n=None):
         """u8 -> s8 -> rotation only: the bytes the reference leaves in its buffer / dumps over UDP."""
@@ -536,6 +549,21 @@ def channelizer_default_taps(decimation):
     return out
 
 
+def channelizer_tuning(decimation, source_centre_hz, station_hz, rotation=1):
+    """iqd_channelizer_tuning (host only): the increment that cuts station_hz + 64000 rotation out of a source centred on
+    source_centre_hz at decimation x 256 kS/s, or None when that is out of band.  A bad decimation (2..64) or rotation
+    (-1, 0, +1) raises IqdError, as the C function's IQD_EINVAL would otherwise read as "out of band"."""
+    if not 2 <= int(decimation) <= 64 or int(rotation) not in (-1, 0, 1):
+        raise IqdError(-1, "channelizer_tuning: decimation must be 2..64 and rotation -1, 0 or +1")
+    inc = C.c_uint32()
+    rc = _lib().iqd_channelizer_tuning(int(decimation), int(source_centre_hz), int(station_hz), int(rotation), C.byref(inc))
+    if rc == -1:
+        return None
+    if rc != 0:
+        raise IqdError(rc, "iqd_channelizer_tuning")
+    return inc.value
+
+
 def phase_inc(offset_hz, fs):
     """The channelizer's phase increment for a channel at offset_hz from the capture's centre (f = int32(d) / 2^32 fs)."""
     return int(round(float(offset_hz) / float(fs) * 2.0 ** 32)) & 0xffffffff
@@ -586,6 +614,16 @@ class Channelizer:
 
     def reset(self):
         self._e._check(self._L.iqd_channelizer_reset(self._h))
+
+    def set_source_frequency(self, centre_hz, first=0):
+        """Centre frequencies (Hz) of sources [first, first + len)."""
+        c = np.ascontiguousarray(np.atleast_1d(np.asarray(centre_hz, dtype=np.uint64)))
+        self._e._check(self._L.iqd_channelizer_set_source_frequency(self._h, int(first), len(c), _np_ptr(c)))
+
+    def follow_scanner(self, follow=True, first=0, n=None):
+        """Channels [first, first + n) follow (or stop following) their engine channel's scanner."""
+        n = self.n_channels - int(first) if n is None else int(n)
+        self._e._check(self._L.iqd_channelizer_follow_scanner(self._h, int(first), n, 1 if follow else 0))
 
     def close(self):
         """iqd_channelizer_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""

@@ -100,16 +100,25 @@ struct iqd_channelizer {
     std::vector<int16_t> h, phasor;               // prototype [K]; (c, s) pairs [8192]
     std::vector<uint32_t> src, inc;
     std::vector<uint8_t> shift;
+    std::vector<uint8_t> follow;                  // [n_ch]: the channel follows its engine channel's scanner
+    std::vector<unsigned long long> centre;       // [n_src]: source centre frequencies
+    uint32_t n_follow = 0;
+    bool centre_dirty = true;
+    uint32_t n_cus = 256;
     std::vector<int16_t> gr, gi;                  // [n_ch][K]
     bool layout_dirty = true;                     // a channel changed source: regroup
     std::vector<uint8_t> ch_dirty;                // new taps since the last packing
     bool any_dirty = true;
     uint64_t m_abs = 0;                           // outputs per channel since create / reset
     std::vector<ChzTile> tiles;
-    std::vector<ChzWg> wgs;
+    std::vector<ChzWg> wgs;                       // chz_kernel's workgroups (fixed channels)
+    std::vector<ChzWg> swgs;                      // the walker's (following channels)
+    uint32_t scan_waves = 1;                      // tiles per walker workgroup
+    uint32_t scan_wpt = 1;                        // waves per tile
+    uint32_t n_fixed_tiles = 0;                   // tiles [0, n_fixed_tiles) hold fixed channels, the rest following ones
     std::vector<uint32_t> slot_of;                // [n_ch]: tile * 8 + slot
     std::vector<uint8_t> amat;                    // [n_tiles][nq][2][64][16]
-    Buf d_amat, d_tiles, d_wgs, d_phasor, d_hist[2], st_wide, st_out;
+    Buf d_amat, d_tiles, d_wgs, d_swgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
     Buf w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
     Staging stg[2];                               // tap uploads
     int stg_cur = 0;
@@ -153,29 +162,47 @@ static void chz_new_taps(iqd_channelizer *z, uint32_t c)
     z->any_dirty = true;
 }
 
-// channels sorted by source, 8 per tile, up to CHZ_WAVES tiles of one source per workgroup row
+// channels sorted by source, 8 per tile, up to CHZ_WAVES tiles of one source per workgroup row; fixed and following
+// channels never share a tile.  The walker's workgroups take scan_waves tiles each: as few as keep every CU busy.
 static void chz_group(iqd_channelizer *z)
 {
     z->tiles.clear();
     z->wgs.clear();
+    z->swgs.clear();
     z->slot_of.assign(z->n_ch, 0);
-    std::vector<std::vector<uint32_t>> by_src(z->n_src);
-    for (uint32_t c = 0; c < z->n_ch; c++) by_src[z->src[c]].push_back(c);
-    for (uint32_t s = 0; s < z->n_src; s++) {
-        const auto &list = by_src[s];
-        const uint32_t first_tile = (uint32_t)z->tiles.size();
-        for (size_t i = 0; i < list.size(); i += CHZ_TILE_CH) {
-            ChzTile t;
-            for (uint32_t l = 0; l < CHZ_TILE_CH; l++) {
-                t.ch[l] = i + l < list.size() ? list[i + l] : CHZ_NONE;
-                if (t.ch[l] != CHZ_NONE) z->slot_of[t.ch[l]] = (uint32_t)z->tiles.size() * CHZ_TILE_CH + l;
+    std::vector<std::vector<uint32_t>> by_src[2];
+    by_src[0].resize(z->n_src);
+    by_src[1].resize(z->n_src);
+    for (uint32_t c = 0; c < z->n_ch; c++) by_src[z->follow[c] ? 1 : 0][z->src[c]].push_back(c);
+    std::vector<ChzWg> runs;                      // following tiles per source
+    for (int f = 0; f < 2; f++)
+        for (uint32_t s = 0; s < z->n_src; s++) {
+            const auto &list = by_src[f][s];
+            const uint32_t first_tile = (uint32_t)z->tiles.size();
+            for (size_t i = 0; i < list.size(); i += CHZ_TILE_CH) {
+                ChzTile t;
+                for (uint32_t l = 0; l < CHZ_TILE_CH; l++) {
+                    t.ch[l] = i + l < list.size() ? list[i + l] : CHZ_NONE;
+                    if (t.ch[l] != CHZ_NONE) z->slot_of[t.ch[l]] = (uint32_t)z->tiles.size() * CHZ_TILE_CH + l;
+                }
+                z->tiles.push_back(t);
             }
-            z->tiles.push_back(t);
+            const uint32_t n_tiles = (uint32_t)z->tiles.size() - first_tile;
+            z->n_fixed_tiles = f == 0 ? (uint32_t)z->tiles.size() : z->n_fixed_tiles;
+            if (f == 0)
+                for (uint32_t t = 0; t < n_tiles; t += CHZ_WAVES)
+                    z->wgs.push_back(ChzWg{s, first_tile + t, std::min(CHZ_WAVES, n_tiles - t), 0});
+            else if (n_tiles)
+                runs.push_back(ChzWg{s, first_tile, n_tiles, 0});
         }
-        const uint32_t n_tiles = (uint32_t)z->tiles.size() - first_tile;
-        for (uint32_t t = 0; t < n_tiles; t += CHZ_WAVES)
-            z->wgs.push_back(ChzWg{s, first_tile + t, std::min(CHZ_WAVES, n_tiles - t), 0});
-    }
+    uint32_t n_follow_tiles = 0;
+    for (const ChzWg &r : runs) n_follow_tiles += r.n_tiles;
+    z->scan_waves = std::max(1u, std::min(CHZ_WAVES, n_follow_tiles / std::max(1u, z->n_cus)));
+    z->scan_wpt = 1;   // the rest of the workgroup's 8 waves share the tiles' outputs
+    while (2 * z->scan_wpt * z->scan_waves <= CHZ_WAVES) z->scan_wpt *= 2;
+    for (const ChzWg &r : runs)
+        for (uint32_t t = 0; t < r.n_tiles; t += z->scan_waves)
+            z->swgs.push_back(ChzWg{r.source, r.first_tile + t, std::min(z->scan_waves, r.n_tiles - t), 0});
     z->amat.assign(z->tiles.size() * z->nq * 2 * 64 * 16, 0);
     std::fill(z->ch_dirty.begin(), z->ch_dirty.end(), 1);
 }
@@ -187,6 +214,7 @@ static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
     const uint32_t c = t.ch[l];
     t.inc[l] = c == CHZ_NONE ? 0 : z->inc[c];
     t.shift[l] = c == CHZ_NONE ? 0 : z->shift[c];
+    if (tile >= z->n_fixed_tiles) return;   // a following channel: the walker builds its operands itself, per block
     for (uint32_t row = 0; row < 2; row++) {
         const uint32_t rho = 2 * l + row;
         for (uint32_t q = 0; q < z->nq; q++)
@@ -229,11 +257,12 @@ static int chz_upload(iqd_channelizer *z)
     if (regroup) {
         CHZ_TRY(z, z->d_amat.ensure(z->amat.size()));
         CHZ_TRY(z, z->d_tiles.ensure(n_tiles * sizeof(ChzTile)));
-        CHZ_TRY(z, z->d_wgs.ensure(z->wgs.size() * sizeof(ChzWg)));
+        CHZ_TRY(z, z->d_wgs.ensure(std::max<size_t>(1, z->wgs.size()) * sizeof(ChzWg)));
+        CHZ_TRY(z, z->d_swgs.ensure(std::max<size_t>(1, z->swgs.size()) * sizeof(ChzWg)));
     }
     struct Run { size_t first, n; };
     std::vector<Run> runs;
-    size_t bytes = regroup ? z->wgs.size() * sizeof(ChzWg) : 0;
+    size_t bytes = regroup ? (z->wgs.size() + z->swgs.size()) * sizeof(ChzWg) : 0;
     for (size_t t = 0; t < n_tiles; t++) {
         if (!tile_dirty[t]) continue;
         if (!runs.empty() && runs.back().first + runs.back().n == t) runs.back().n++;
@@ -251,10 +280,12 @@ static int chz_upload(iqd_channelizer *z)
         return e;
     };
     for (const Run &r : runs) {
-        CHZ_TRY(z, copy((uint8_t *)z->d_amat.p + r.first * tile_bytes, &z->amat[r.first * tile_bytes], r.n * tile_bytes));
+        const size_t na = r.first < z->n_fixed_tiles ? std::min<size_t>(r.n, z->n_fixed_tiles - r.first) : 0;
+        if (na) CHZ_TRY(z, copy((uint8_t *)z->d_amat.p + r.first * tile_bytes, &z->amat[r.first * tile_bytes], na * tile_bytes));
         CHZ_TRY(z, copy((ChzTile *)z->d_tiles.p + r.first, &z->tiles[r.first], r.n * sizeof(ChzTile)));
     }
-    if (regroup) CHZ_TRY(z, copy(z->d_wgs.p, z->wgs.data(), z->wgs.size() * sizeof(ChzWg)));
+    if (regroup && !z->wgs.empty()) CHZ_TRY(z, copy(z->d_wgs.p, z->wgs.data(), z->wgs.size() * sizeof(ChzWg)));
+    if (regroup && !z->swgs.empty()) CHZ_TRY(z, copy(z->d_swgs.p, z->swgs.data(), z->swgs.size() * sizeof(ChzWg)));
     CHZ_TRY(z, hipEventRecord(st.done, z->stream));
     st.pending = true;
     z->stg_cur ^= 1;
@@ -345,6 +376,13 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
     z->src.assign(z->n_ch, 0);
     z->inc.assign(z->n_ch, 0);
     z->shift.assign(z->n_ch, 0);
+    z->follow.assign(z->n_ch, 0);
+    z->centre.assign(z->n_src, 0);
+    {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, z->device) == hipSuccess && cus > 0)
+            z->n_cus = (uint32_t)cus;
+    }
     z->gr.assign((size_t)z->n_ch * z->k, 0);
     z->gi.assign((size_t)z->n_ch * z->k, 0);
     z->ch_dirty.assign(z->n_ch, 0);
@@ -356,6 +394,10 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
     bool ok = z->d_phasor.ensure(CHZ_PHASOR * 4) == hipSuccess && z->d_hist[0].ensure(hb) == hipSuccess &&
               z->d_hist[1].ensure(hb) == hipSuccess;
     ok = ok && hipMemcpy(z->d_phasor.p, packed.data(), CHZ_PHASOR * 4, hipMemcpyHostToDevice) == hipSuccess;
+    std::vector<int16_t> proto(z->kp, 0);
+    std::copy(z->h.begin(), z->h.end(), proto.begin());
+    ok = ok && z->d_proto.ensure(z->kp * 2) == hipSuccess && z->d_centre.ensure((size_t)z->n_src * 8) == hipSuccess;
+    ok = ok && hipMemcpy(z->d_proto.p, proto.data(), z->kp * 2, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && chz_fill_history(z) == IQD_OK && hipStreamSynchronize(z->stream) == hipSuccess;
     if (!ok) {
         iqd_channelizer_destroy(z);
@@ -370,7 +412,7 @@ void iqd_channelizer_destroy(iqd_channelizer_t *z)
     if (!z) return;
     (void)hipSetDevice(z->device);
     (void)hipStreamSynchronize(z->stream);
-    for (Buf *b : {&z->d_amat, &z->d_tiles, &z->d_wgs, &z->d_phasor, &z->d_hist[0], &z->d_hist[1], &z->st_wide, &z->st_out,
+    for (Buf *b : {&z->d_amat, &z->d_tiles, &z->d_wgs, &z->d_swgs, &z->d_phasor, &z->d_proto, &z->d_centre, &z->d_hist[0], &z->d_hist[1], &z->st_wide, &z->st_out,
                    &z->w_rows, &z->w_pcm, &z->w_cnt, &z->w_mag, &z->w_sp})
         b->release();
     z->stg[0].release();
@@ -417,16 +459,12 @@ static int chz_check_len(iqd_channelizer *z, size_t bytes_per_source)
     return IQD_OK;
 }
 
-int iqd_channelizer_run_device(iqd_channelizer_t *z, const void *wide_dev, size_t bytes_per_source, void *out_dev)
+// Queues one call: chz_kernel for the fixed channels, the walker for the following ones (scan != NULL), the history.
+static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_source, void *out_dev, ChzScanLaunch *scan)
 {
-    if (!z) return IQD_EINVAL;
-    if (!wide_dev || !out_dev) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
-    if ((((uintptr_t)wide_dev) | ((uintptr_t)out_dev)) & 15) return z->fail(IQD_EINVAL, "channelizer: buffers must be 16-byte aligned");
-    int rc = chz_check_len(z, bytes_per_source);
-    if (rc != IQD_OK) return rc;
     (void)hipSetDevice(z->device);
     if (z->any_dirty || z->layout_dirty) {
-        rc = chz_upload(z);
+        int rc = chz_upload(z);
         if (rc != IQD_OK) return rc;
     }
     const uint32_t n_out = (uint32_t)(bytes_per_source / (2 * z->m));   // a multiple of 32
@@ -447,18 +485,47 @@ int iqd_channelizer_run_device(iqd_channelizer_t *z, const void *wide_dev, size_
     a.m = z->m;
     a.kp = z->kp;
     a.nq = z->nq;
-    a.t_blk = n_out <= t_max ? n_out : t_max;
     a.nbase = (uint32_t)(z->m_abs * z->m);
-    CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->stream));
+    if (!scan) {
+        a.t_blk = n_out <= t_max ? n_out : t_max;
+        CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->stream));
+    } else {
+        if (z->centre_dirty) {
+            CHZ_TRY(z, hipMemcpyAsync(z->d_centre.p, z->centre.data(), (size_t)z->n_src * 8, hipMemcpyHostToDevice, z->stream));
+            CHZ_TRY(z, hipStreamSynchronize(z->stream));   // (the host vector may change once this returns)
+            z->centre_dirty = false;
+        }
+        scan->proto = (const int16_t *)z->d_proto.p;
+        scan->centre = (const unsigned long long *)z->d_centre.p;
+        scan->waves = z->scan_waves;
+        scan->wpt = z->scan_wpt;
+        // chz_kernel's windows as before; the walker's stay inside one block
+        a.t_blk = n_out <= t_max ? n_out : t_max;
+        scan->t_blk = scan->block_out <= t_max ? scan->block_out : t_max;
+        CHZ_TRY(z, launch_channelizer_scan(a, (uint32_t)z->wgs.size(), (const ChzWg *)z->d_swgs.p, (uint32_t)z->swgs.size(),
+                                           *scan, z->stream));
+    }
     z->cur ^= 1;
     z->m_abs += n_out;
     return IQD_OK;
+}
+
+int iqd_channelizer_run_device(iqd_channelizer_t *z, const void *wide_dev, size_t bytes_per_source, void *out_dev)
+{
+    if (!z) return IQD_EINVAL;
+    if (!wide_dev || !out_dev) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
+    if ((((uintptr_t)wide_dev) | ((uintptr_t)out_dev)) & 15) return z->fail(IQD_EINVAL, "channelizer: buffers must be 16-byte aligned");
+    if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: a channel follows its scanner; use iqd_accept_wideband*");
+    int rc = chz_check_len(z, bytes_per_source);
+    if (rc != IQD_OK) return rc;
+    return chz_queue(z, wide_dev, bytes_per_source, out_dev, nullptr);
 }
 
 int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_per_source, uint8_t *out)
 {
     if (!z) return IQD_EINVAL;
     if (!wide || !out) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
+    if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: a channel follows its scanner; use iqd_accept_wideband*");
     int rc = chz_check_len(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(z->device);
@@ -473,12 +540,15 @@ int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_
     return IQD_OK;
 }
 
-int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const uint8_t *wide, size_t bytes_per_source,
-                        int16_t *pcm, uint32_t *pcm_count, uint32_t *magnitude, uint8_t *signal_present)
+// Checks and queues one wideband accept: the rows into rows_dev, then iqd_accept_iq_device on them.  With following
+// channels the engine's pending settings are applied first (once), so that the walker reads the state the accept starts
+// from.
+static int wideband_queue(iqd_t *e, iqd_channelizer *z, uint32_t first_ch, const void *wide_dev, size_t bytes_per_source,
+                          void *rows_dev, void *pcm_dev, void *pcm_count_dev, void *magnitude_dev, void *signal_present_dev)
 {
-    if (!e) return IQD_EINVAL;
     if (!z || z->e != e) return engine_fail(e, IQD_EINVAL, "accept_wideband: the channelizer belongs to another engine");
-    if (!wide || !pcm) return z->fail(IQD_EINVAL, "accept_wideband: NULL buffer");
+    if (!wide_dev || !rows_dev || !pcm_dev) return z->fail(IQD_EINVAL, "accept_wideband: NULL buffer");
+    if ((((uintptr_t)wide_dev) | ((uintptr_t)rows_dev)) & 15) return z->fail(IQD_EINVAL, "accept_wideband: wide and rows buffers must be 16-byte aligned");
     int rc = chz_check_len(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     uint32_t e_nch = 0, bb = 0, flags = 0;
@@ -489,19 +559,20 @@ int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const
         return z->fail(IQD_EINVAL, "accept_wideband: bytes_per_source / decimation must be a multiple of block_bytes, or one short block");
     const size_t nblk = row % bb == 0 ? row / bb : 1;
     (void)hipSetDevice(z->device);
-    const size_t n = z->n_ch, ib = (size_t)z->n_src * bytes_per_source;
-    CHZ_TRY(z, z->st_wide.ensure(ib));
-    CHZ_TRY(z, z->w_rows.ensure(n * row));
-    CHZ_TRY(z, z->w_pcm.ensure(n * (row / 64) * 2));
-    CHZ_TRY(z, z->w_cnt.ensure(n * 4));
-    CHZ_TRY(z, z->w_mag.ensure(n * nblk * 4));
-    CHZ_TRY(z, z->w_sp.ensure(n * nblk));
-    CHZ_TRY(z, hipMemcpyAsync(z->st_wide.p, wide, ib, hipMemcpyHostToDevice, z->stream));
-    rc = iqd_channelizer_run_device(z, z->st_wide.p, bytes_per_source, z->w_rows.p);
+    if (z->n_follow) {
+        ChzScanLaunch sl{};
+        rc = engine_settle(e, &sl);
+        if (rc != IQD_OK) return rc;
+        sl.first_ch = first_ch;
+        sl.n_blocks = (uint32_t)nblk;
+        sl.block_out = (uint32_t)(row / nblk / 2);
+        rc = chz_queue(z, wide_dev, bytes_per_source, rows_dev, &sl);
+    } else {
+        rc = chz_queue(z, wide_dev, bytes_per_source, rows_dev, nullptr);
+    }
     if (rc != IQD_OK) return rc;
     if (flags & IQD_F_PREPASS_OVERLAP) CHZ_TRY(z, hipStreamSynchronize(z->stream));   // that path wants its input complete
-    rc = iqd_accept_iq_device(e, first_ch, z->n_ch, z->w_rows.p, row, z->w_pcm.p, z->w_cnt.p,
-                              magnitude ? z->w_mag.p : nullptr, signal_present ? z->w_sp.p : nullptr);
+    rc = iqd_accept_iq_device(e, first_ch, z->n_ch, rows_dev, row, pcm_dev, pcm_count_dev, magnitude_dev, signal_present_dev);
     if (rc != IQD_OK) {
         // The checks above are the engine's own (range, block_bytes rule), so it does not refuse these rows; should it
         // still, the channelizer steps back as well: the call's history went to the other buffer, so the stream stands
@@ -510,12 +581,77 @@ int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const
         z->m_abs -= bytes_per_source / (2 * z->m);
         return rc;
     }
+    return IQD_OK;
+}
+
+int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const uint8_t *wide, size_t bytes_per_source,
+                        int16_t *pcm, uint32_t *pcm_count, uint32_t *magnitude, uint8_t *signal_present)
+{
+    if (!e) return IQD_EINVAL;
+    if (!z || z->e != e) return engine_fail(e, IQD_EINVAL, "accept_wideband: the channelizer belongs to another engine");
+    if (!wide || !pcm) return z->fail(IQD_EINVAL, "accept_wideband: NULL buffer");
+    int rc = chz_check_len(z, bytes_per_source);
+    if (rc != IQD_OK) return rc;
+    uint32_t e_nch = 0, bb = 0, flags = 0;
+    engine_geometry(e, &e_nch, &bb, &flags);
+    const size_t row = bytes_per_source / z->m;
+    const size_t nblk = row % bb == 0 ? row / bb : 1;
+    (void)hipSetDevice(z->device);
+    const size_t n = z->n_ch, ib = (size_t)z->n_src * bytes_per_source;
+    CHZ_TRY(z, z->st_wide.ensure(ib));
+    CHZ_TRY(z, z->w_rows.ensure(n * row));
+    CHZ_TRY(z, z->w_pcm.ensure(n * (row / 64) * 2));
+    CHZ_TRY(z, z->w_cnt.ensure(n * 4));
+    CHZ_TRY(z, z->w_mag.ensure(n * nblk * 4));
+    CHZ_TRY(z, z->w_sp.ensure(n * nblk));
+    CHZ_TRY(z, hipMemcpyAsync(z->st_wide.p, wide, ib, hipMemcpyHostToDevice, z->stream));
+    rc = wideband_queue(e, z, first_ch, z->st_wide.p, bytes_per_source, z->w_rows.p, z->w_pcm.p, z->w_cnt.p,
+                        magnitude ? z->w_mag.p : nullptr, signal_present ? z->w_sp.p : nullptr);
+    if (rc != IQD_OK) return rc;
     CHZ_TRY(z, hipMemcpyAsync(pcm, z->w_pcm.p, n * (row / 64) * 2, hipMemcpyDeviceToHost, z->stream));
     if (pcm_count) CHZ_TRY(z, hipMemcpyAsync(pcm_count, z->w_cnt.p, n * 4, hipMemcpyDeviceToHost, z->stream));
     if (magnitude) CHZ_TRY(z, hipMemcpyAsync(magnitude, z->w_mag.p, n * nblk * 4, hipMemcpyDeviceToHost, z->stream));
     if (signal_present) CHZ_TRY(z, hipMemcpyAsync(signal_present, z->w_sp.p, n * nblk, hipMemcpyDeviceToHost, z->stream));
     CHZ_TRY(z, hipStreamSynchronize(z->stream));
     return IQD_OK;
+}
+
+int iqd_accept_wideband_device(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const void *wide_dev, size_t bytes_per_source,
+                               void *rows_dev, void *pcm_dev, void *pcm_count_dev, void *magnitude_dev, void *signal_present_dev)
+{
+    if (!e) return IQD_EINVAL;
+    return wideband_queue(e, z, first_ch, wide_dev, bytes_per_source, rows_dev, pcm_dev, pcm_count_dev, magnitude_dev,
+                          signal_present_dev);
+}
+
+int iqd_channelizer_set_source_frequency(iqd_channelizer_t *z, uint32_t first_source, uint32_t n, const uint64_t *centre_hz)
+{
+    if (!z) return IQD_EINVAL;
+    if (!centre_hz || n < 1 || first_source >= z->n_src || n > z->n_src - first_source)
+        return z->fail(IQD_EINVAL, "channelizer: bad source range");
+    for (uint32_t i = 0; i < n; i++) z->centre[first_source + i] = centre_hz[i];
+    z->centre_dirty = true;
+    return IQD_OK;
+}
+
+int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_t n, int follow)
+{
+    if (!z) return IQD_EINVAL;
+    if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
+    for (uint32_t i = 0; i < n; i++) {
+        uint8_t &f = z->follow[first + i];
+        if (f == (follow ? 1 : 0)) continue;
+        f = follow ? 1 : 0;
+        z->n_follow += follow ? 1 : -1;
+        z->layout_dirty = true;
+    }
+    return IQD_OK;
+}
+
+int iqd_channelizer_tuning(uint32_t decimation, uint64_t source_centre_hz, uint64_t station_hz, int rotation, uint32_t *inc)
+{
+    if (decimation < 2 || decimation > 64 || rotation < -1 || rotation > 1 || !inc) return IQD_EINVAL;
+    return chz_tuning(decimation, source_centre_hz, station_hz, rotation, inc) ? IQD_OK : IQD_EINVAL;
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "iqdemod.h"
+#include "iqd_device.h"
 
 namespace iqd {
 
@@ -24,6 +25,8 @@ constexpr uint32_t CHZ_WIN_MAX = 32768;      // LDS bytes of a workgroup's windo
 constexpr uint32_t CHZ_LDS_FIXED = CHZ_PHASOR * 4 + CHZ_WAVES * CHZ_TILE_CH * 2 * CHZ_GROUP;   // phasor + output staging
 constexpr uint32_t CHZ_NQ_REG = 8;           // up to this many K-chunks the A operands stay in registers
 constexpr uint32_t CHZ_NONE = 0xffffffffu;   // a padding slot of a tile
+constexpr uint32_t CHZ_PROTO_MAX = 1024;     // prototype taps (the scan walker keeps them in LDS, zero up to Kp)
+constexpr uint32_t CHZ_SCAN_MAGSUM = 2 * CHZ_WAVES * CHZ_TILE_CH * 4;   // the walker's per-block magnitude sums in LDS
 
 struct ChzTile {
     uint32_t ch[CHZ_TILE_CH];       // output row per slot, CHZ_NONE = padding (its taps are 0, nothing is stored)
@@ -49,7 +52,43 @@ struct ChzLaunch {
     uint32_t nbase;                  // (outputs before this call * M) mod 2^32
 };
 
+// What the scan walker (chz_scan_kernel) reads besides ChzLaunch: a.wgs are its own workgroups (tiles of following
+// channels only); the engine's per-channel state is read, never written (the walker steps a shadow copy).
+struct ChzScanLaunch {
+    const int16_t *proto;                  // [kp] prototype, zero from K on
+    const unsigned long long *centre;      // [n_sources] source centre frequencies F_s
+    const ChanParams *params;              // the engine's state, [engine ch]
+    const AgcConfig *agc_cfg;
+    const AgcState *agc;
+    const ScanConfig *scan_cfg;
+    const ScanState *scan;
+    const uint32_t *tracker;
+    const Consts *consts;                  // the engine's constant tables (dB table)
+    uint32_t first_ch;                     // engine channel of channelizer channel 0
+    uint32_t block_out, n_blocks;          // outputs per block, blocks in this call
+    uint32_t t_blk;                        // outputs per window (a multiple of 64, or the whole short block)
+    uint32_t waves;                        // tiles per workgroup
+    uint32_t wpt;                          // waves per tile (waves * wpt <= CHZ_WAVES)
+};
+
+// iqd_channelizer_tuning: the increment of a channel whose station is `station` Hz (centre station + 64000 r) cut from a
+// source centred on `centre` Hz at Fs = 256000 M; false when out of band.  Host and device share this one statement.
+__host__ __device__ inline bool chz_tuning(uint32_t m, unsigned long long centre, unsigned long long station, int32_t r,
+                                           uint32_t *inc)
+{
+    const __int128 fs = (__int128)256000 * m;
+    const __int128 o = (__int128)station + (__int128)(64000 * r) - (__int128)centre;
+    if (o < -(fs / 2) || o >= fs / 2) return false;
+    // floor((o 2^32 + Fs/2) / Fs) on a non-negative numerator: (o + Fs/2) 2^32 + Fs/2 < 2^56 gives the quotient + 2^31
+    const unsigned long long num = ((unsigned long long)(o + fs / 2) << 32) + (unsigned long long)(fs / 2);
+    *inc = (uint32_t)(num / (unsigned long long)fs) ^ 0x80000000u;
+    return true;
+}
+
 hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s);
+// n_fixed_wgs workgroups of chz_kernel (a.wgs), n_scan_wgs of the walker (scan_wgs), then the history kernel
+hipError_t launch_channelizer_scan(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
+                                   const ChzScanLaunch &s, hipStream_t st);
 
 // host-only spec pieces (iqd_chan.cpp)
 void chz_phasor_table(int16_t *out /* [8192] (c, s) pairs */);
@@ -59,5 +98,8 @@ void chz_channel_taps(const int16_t *h, uint32_t k, uint32_t inc, const int16_t 
 // the engine's side (iqd_engine.cpp)
 int engine_fail(iqd_t *e, int code, const char *msg);
 void engine_geometry(const iqd_t *e, uint32_t *n_ch, uint32_t *block_bytes, uint32_t *flags);
+// Applies the pending settings now (parameters, AGC one-shots, the scanner's start jump: once; the accept that follows
+// finds nothing left to apply) and fills the device state pointers of s.
+int engine_settle(iqd_t *e, ChzScanLaunch *s);
 
 }  // namespace iqd

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "iqd_chan.h"
+#include "iqd_chains.h"
 
 namespace iqd {
 
@@ -63,64 +64,38 @@ __device__ __forceinline__ uint32_t chz_epilogue(int32_t rlo, int32_t rhi, int32
     return (uint32_t)(yr + 128) | ((uint32_t)(yi + 128) << 8);
 }
 
-template <int NQR>   // NQR > 0: nq <= NQR, the A operands stay in registers; 0: they are read per group
-__global__ __launch_bounds__(512) void chz_kernel(const ChzLaunch a)
+// Every thread of the workgroup: the window of outputs [m0, m0 + nloc) of one source - bytes [2 M m0 - 2 Kp, 2 M (m0 +
+// nloc)) of [history | this call], made signed - into LDS.
+__device__ __forceinline__ void chz_stage_window(const ChzLaunch &a, uint32_t source, uint32_t m0, uint32_t nloc, uint8_t *win)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t chz_lds[];
-    uint32_t *sp = (uint32_t *)chz_lds;
-    uint8_t *stage_all = chz_lds + CHZ_PHASOR * 4;
-    uint8_t *win = chz_lds + CHZ_LDS_FIXED;
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const ChzWg w = a.wgs[blockIdx.y];
-    const uint32_t m0 = blockIdx.x * a.t_blk;
-    const uint32_t nloc = min(a.t_blk, a.n_out - m0);           // a multiple of 32
-    const uint32_t M = a.m, kp = a.kp, nq = a.nq;
-
-    for (uint32_t i = tid; i < CHZ_PHASOR / 4; i += blockDim.x) ((uint4 *)sp)[i] = ((const uint4 *)a.phasor)[i];
-    {
-        const uint8_t *src = a.wide + (size_t)w.source * a.bytes_per_source;
-        const uint8_t *hsrc = a.hist + (size_t)w.source * 2 * kp;
-        const int64_t b0 = 2 * (int64_t)m0 * M - 2 * (int64_t)kp;   // 16-byte aligned, like the history's end
-        const uint32_t wbytes = 2 * (nloc * M + kp);
-        for (uint32_t i = tid * 16; i < wbytes; i += blockDim.x * 16) {
-            const int64_t b = b0 + i;
-            uint4 v = b < 0 ? *(const uint4 *)(hsrc + 2 * kp + b) : *(const uint4 *)(src + b);
-            v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
-            *(uint4 *)(win + i) = v;
-        }
+    const uint32_t M = a.m, kp = a.kp;
+    const uint8_t *src = a.wide + (size_t)source * a.bytes_per_source;
+    const uint8_t *hsrc = a.hist + (size_t)source * 2 * kp;
+    const int64_t b0 = 2 * (int64_t)m0 * M - 2 * (int64_t)kp;   // 16-byte aligned, like the history's end
+    const uint32_t wbytes = 2 * (nloc * M + kp);
+    for (uint32_t i = threadIdx.x * 16; i < wbytes; i += blockDim.x * 16) {
+        const int64_t b = b0 + i;
+        uint4 v = b < 0 ? *(const uint4 *)(hsrc + 2 * kp + b) : *(const uint4 *)(src + b);
+        v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
+        *(uint4 *)(win + i) = v;
     }
-    __syncthreads();
-    if (wave >= w.n_tiles) return;
+}
 
-    const uint32_t tile = w.first_tile + wave;
-    const ChzTile *T = a.tiles + tile;
-    const uint32_t col = lane & 15, g = lane >> 4;
-    uint32_t inc[2], shv[2];
-    int32_t rnd[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        inc[i] = T->inc[2 * g + i];
-        const uint32_t L = T->shift[2 * g + i];
-        shv[i] = 22 - L;
-        rnd[i] = 1 << (21 - L);
-    }
+// One wave: its tile's outputs [m0, m0 + nloc) (nloc a multiple of 32) from the staged window, through the MFMA, the
+// epilogue and the 16-byte stores.  A: the tile's operands in registers (NQR > 0) or amat, read per group (NQR = 0).
+// MAG: also sums SignalDetector's magnitude of the bytes this lane stores (the scan walker's squelch).
+template <int NQR, bool MAG>
+__device__ __forceinline__ void chz_tile_outputs(const ChzLaunch &a, const uint8_t *win, const uint32_t *sp, uint8_t *stage,
+                                                 const chz_v4i (&A)[NQR > 0 ? NQR : 1][2], const uint4 *amat,
+                                                 const uint32_t (&inc)[2], const uint32_t (&shv)[2], const int32_t (&rnd)[2],
+                                                 uint32_t st_ch, uint32_t m0, uint32_t nloc, uint32_t &mag,
+                                                 uint32_t grp0 = 0, uint32_t gstride = 1)
+{
+    const uint32_t lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
     const uint32_t st_cl = lane >> 3, st_piece = lane & 7;
-    const uint32_t st_ch = T->ch[st_cl];
-    uint8_t *stage = stage_all + wave * (CHZ_TILE_CH * 2 * CHZ_GROUP);
-    const uint4 *amat = a.amat + (size_t)tile * nq * 2 * 64 + lane;
-
-    chz_v4i A[NQR > 0 ? NQR : 1][2];
-    if (NQR > 0) {
-#pragma unroll
-        for (int q = 0; q < NQR; q++)
-            if (q < (int)nq) {
-                A[q][0] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 0) * 64]);
-                A[q][1] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 1) * 64]);
-            }
-    }
+    const uint32_t M = a.m, nq = a.nq;
     const chz_v4i zero = {0, 0, 0, 0};
-
-    for (uint32_t grp = 0; grp * CHZ_GROUP < nloc; grp++) {
+    for (uint32_t grp = grp0; grp * CHZ_GROUP < nloc; grp += gstride) {
         const uint32_t ntl = min(4u, (nloc - grp * CHZ_GROUP) / 16);   // 2 or 4
         // two 16-output tiles at a time: four independent accumulator chains (tile x plane)
         for (uint32_t tp = 0; tp < ntl; tp += 2) {
@@ -167,8 +142,199 @@ __global__ __launch_bounds__(512) void chz_kernel(const ChzLaunch a)
         if (st_ch != CHZ_NONE && st_piece * 8 < ntl * 16) {
             const uint4 v = *(const uint4 *)(stage + st_cl * (2 * CHZ_GROUP) + 16 * st_piece);
             *(uint4 *)(a.out + (size_t)st_ch * a.out_row + 2 * (size_t)(m0 + grp * CHZ_GROUP) + 16 * st_piece) = v;
+            if (MAG)
+                mag += magnitude2(v.x ^ 0x80808080u) + magnitude2(v.y ^ 0x80808080u) + magnitude2(v.z ^ 0x80808080u) +
+                       magnitude2(v.w ^ 0x80808080u);
         }
         chz_wave_fence();
+    }
+}
+
+template <int NQR>   // NQR > 0: nq <= NQR, the A operands stay in registers; 0: they are read per group
+__global__ __launch_bounds__(512) void chz_kernel(const ChzLaunch a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t chz_lds[];
+    uint32_t *sp = (uint32_t *)chz_lds;
+    uint8_t *stage_all = chz_lds + CHZ_PHASOR * 4;
+    uint8_t *win = chz_lds + CHZ_LDS_FIXED;
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const ChzWg w = a.wgs[blockIdx.y];
+    const uint32_t m0 = blockIdx.x * a.t_blk;
+    const uint32_t nloc = min(a.t_blk, a.n_out - m0);           // a multiple of 32
+    const uint32_t nq = a.nq;
+
+    for (uint32_t i = tid; i < CHZ_PHASOR / 4; i += blockDim.x) ((uint4 *)sp)[i] = ((const uint4 *)a.phasor)[i];
+    chz_stage_window(a, w.source, m0, nloc, win);
+    __syncthreads();
+    if (wave >= w.n_tiles) return;
+
+    const uint32_t tile = w.first_tile + wave;
+    const ChzTile *T = a.tiles + tile;
+    const uint32_t g = lane >> 4;
+    uint32_t inc[2], shv[2];
+    int32_t rnd[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        inc[i] = T->inc[2 * g + i];
+        const uint32_t L = T->shift[2 * g + i];
+        shv[i] = 22 - L;
+        rnd[i] = 1 << (21 - L);
+    }
+    const uint32_t st_ch = T->ch[lane >> 3];
+    uint8_t *stage = stage_all + wave * (CHZ_TILE_CH * 2 * CHZ_GROUP);
+    const uint4 *amat = a.amat + (size_t)tile * nq * 2 * 64 + lane;
+
+    chz_v4i A[NQR > 0 ? NQR : 1][2];
+    if (NQR > 0) {
+#pragma unroll
+        for (int q = 0; q < NQR; q++)
+            if (q < (int)nq) {
+                A[q][0] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 0) * 64]);
+                A[q][1] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 1) * 64]);
+            }
+    }
+    uint32_t mag = 0;
+    chz_tile_outputs<NQR, false>(a, win, sp, stage, A, amat, inc, shv, rnd, st_ch, m0, nloc, mag);
+}
+
+// The scan walker (include/iqdemod.h: iqd_channelizer_follow_scanner).  One workgroup owns up to s.waves tiles of
+// following channels of one source for the whole call and walks its blocks in order, s.wpt waves per tile (each takes
+// every s.wpt-th group of 64 outputs of a window and keeps its own, identical, shadow copy); per block
+//   1. the lane that owns a channel's shadow state (lane 8 l of the tile's wave for slot l) turns its current frequency
+//      into the block's increment d_b, or into silence (out of band: zero taps, every output byte 0x80);
+//   2. every lane builds its own part of the tile's A operands for d_b - exactly chz_pack_slot's bytes - from the
+//      prototype and the phasor table in LDS (in registers for nq <= CHZ_NQ_REG, else in the tile's slice of a.amat);
+//   3. the block's outputs go through chz_tile_outputs, window by window, summing the squelch magnitude;
+//   4. the owner lanes step the shadow copy of their engine channel's per-block recurrence in squelch_track_kernel's
+//      order: dBFS against the threshold with the IF gain in force, the tracker, scanner_step on a rejected block while
+//      scanning, agc_run.
+// The shadow state is dropped at the end: iqd_accept_iq_device on the rows re-derives the same decisions for real.
+template <int NQR>
+__global__ __launch_bounds__(512) void chz_scan_kernel(const ChzLaunch a, const ChzScanLaunch s)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t chz_lds[];
+    uint32_t *sp = (uint32_t *)chz_lds;
+    uint8_t *stage_all = chz_lds + CHZ_PHASOR * 4;
+    int16_t *proto = (int16_t *)(chz_lds + CHZ_LDS_FIXED);
+    uint32_t *magsum = (uint32_t *)(chz_lds + CHZ_LDS_FIXED + 2 * CHZ_PROTO_MAX);   // [2][CHZ_WAVES * 8], by block parity
+    uint8_t *win = chz_lds + CHZ_LDS_FIXED + 2 * CHZ_PROTO_MAX + CHZ_SCAN_MAGSUM;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t tl = (tid >> 6) / s.wpt, part = (tid >> 6) % s.wpt;   // tile of the workgroup, share of its outputs
+    const ChzWg w = a.wgs[blockIdx.x];
+    const uint32_t kp = a.kp, nq = a.nq;
+
+    for (uint32_t i = tid; i < CHZ_PHASOR / 4; i += blockDim.x) ((uint4 *)sp)[i] = ((const uint4 *)a.phasor)[i];
+    for (uint32_t i = tid; i < kp / 8; i += blockDim.x) ((uint4 *)proto)[i] = ((const uint4 *)s.proto)[i];
+
+    const bool active = tl < w.n_tiles;
+    const uint32_t tile = w.first_tile + (active ? tl : 0);
+    const ChzTile *T = a.tiles + tile;
+    const uint32_t col = lane & 15, g = lane >> 4;
+    uint32_t shv[2];
+    int32_t rnd[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const uint32_t L = T->shift[2 * g + i];
+        shv[i] = 22 - L;
+        rnd[i] = 1 << (21 - L);
+    }
+    const uint32_t st_ch = active ? T->ch[lane >> 3] : CHZ_NONE;
+    uint8_t *stage = stage_all + (tid >> 6) * (CHZ_TILE_CH * 2 * CHZ_GROUP);
+    uint4 *amat = const_cast<uint4 *>(a.amat) + (size_t)tile * nq * 2 * 64 + lane;
+    const uint32_t a_slot = col >> 1, a_row = col & 1;           // the A rows this lane builds: slot a_slot, Ar / Ai
+    const bool a_real = active && T->ch[a_slot] != CHZ_NONE;
+
+    // the shadow state, in the owner lane of each channel
+    const bool owner = (lane & 7) == 0 && st_ch != CHZ_NONE;
+    const uint32_t ech = s.first_ch + (owner ? st_ch : 0);
+    AgcConfig cfg = s.agc_cfg[ech];
+    AgcState st = s.agc[ech];
+    const ScanConfig sc = s.scan_cfg[ech];
+    ScanState ss = s.scan[ech];
+    uint32_t gain = st.rx_gain, tracking = s.tracker[ech];
+    const int32_t threshold = s.params[ech].threshold, rot = s.params[ech].rotation;
+    const unsigned long long centre = s.centre[w.source];
+    const Consts &cst = *s.consts;
+
+    chz_v4i A[NQR > 0 ? NQR : 1][2];
+    for (uint32_t b = 0; b < s.n_blocks; b++) {
+        // 1. this block's increment, or silence
+        uint32_t d = 0;
+        const uint32_t on = owner && chz_tuning(a.m, centre, ss.current_hz, rot, &d) ? 1u : 0u;
+        uint32_t inc[2];
+#pragma unroll
+        for (int i = 0; i < 2; i++) inc[i] = (uint32_t)__shfl((int)d, (int)(8 * (2 * g + i)));
+        const uint32_t d_a = (uint32_t)__shfl((int)d, (int)(8 * a_slot));
+        const uint32_t on_a = (uint32_t)__shfl((int)on, (int)(8 * a_slot));   // (every lane: the owner must be active)
+        const bool live = a_real && on_a != 0;
+        if (tid < CHZ_WAVES * 8) magsum[(b & 1) * CHZ_WAVES * 8 + tid] = 0;
+        // 2. A operands: K-index kappa = 64 q + 16 g + j is sample kp - 1 - kappa / 2, rail kappa & 1 (iqd_chan.h)
+        __syncthreads();   // (the prototype; and the previous block's last window has been read)
+        auto build = [&](uint32_t q, uint4 &vlo, uint4 &vhi) {
+            uint32_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+            if (live) {
+#pragma unroll
+                for (uint32_t j = 0; j < 8; j++) {
+                    const uint32_t kk = kp - 1 - 32 * q - 8 * g - j;
+                    const int32_t h = proto[kk];
+                    const uint32_t p = sp[(kk * d_a) >> 20];
+                    const int32_t gr = (h * (int32_t)(int16_t)(p & 0xffffu) + (1 << 14)) >> 15;
+                    const int32_t gi = (h * (int32_t)(int16_t)(p >> 16) + (1 << 14)) >> 15;
+                    const int32_t v0 = a_row == 0 ? gr : gi, v1 = a_row == 0 ? -gi : gr;
+                    // the two signed-byte planes: v = 256 hi + lo, lo = (int8) v
+                    const uint32_t l2 = (uint32_t)(v0 & 0xff) | (uint32_t)(v1 & 0xff) << 8;
+                    const uint32_t h2 = (uint32_t)(((v0 - (int8_t)v0) >> 8) & 0xff) | (uint32_t)(((v1 - (int8_t)v1) >> 8) & 0xff) << 8;
+                    lo[j >> 1] |= l2 << (16 * (j & 1));
+                    hi[j >> 1] |= h2 << (16 * (j & 1));
+                }
+            }
+            vlo = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+            vhi = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+        };
+        if (NQR > 0) {
+#pragma unroll
+            for (int q = 0; q < NQR; q++)
+                if (q < (int)nq) {
+                    uint4 vlo, vhi;
+                    build((uint32_t)q, vlo, vhi);
+                    A[q][0] = __builtin_bit_cast(chz_v4i, vlo);
+                    A[q][1] = __builtin_bit_cast(chz_v4i, vhi);
+                }
+        } else if (active && part == 0) {   // one wave per tile writes them; the window's barrier comes before any read
+            for (uint32_t q = 0; q < nq; q++) {
+                uint4 vlo, vhi;
+                build(q, vlo, vhi);
+                amat[(q * 2 + 0) * 64] = vlo;
+                amat[(q * 2 + 1) * 64] = vhi;
+            }
+        }
+        // 3. the block's outputs, window by window
+        uint32_t mag = 0;
+        const uint32_t mb = b * s.block_out, me = mb + s.block_out;
+        for (uint32_t m0 = mb; m0 < me; m0 += s.t_blk) {
+            const uint32_t nloc = min(s.t_blk, me - m0);
+            if (m0 != mb) __syncthreads();
+            chz_stage_window(a, w.source, m0, nloc, win);
+            __syncthreads();
+            if (active) chz_tile_outputs<NQR, true>(a, win, sp, stage, A, amat, inc, shv, rnd, st_ch, m0, nloc, mag, part, s.wpt);
+        }
+        // 4. the squelch's magnitude per channel (its 8 storing lanes), then the shadow step
+        mag += (uint32_t)__shfl_xor((int)mag, 1);
+        mag += (uint32_t)__shfl_xor((int)mag, 2);
+        mag += (uint32_t)__shfl_xor((int)mag, 4);
+        uint32_t *ms = magsum + (b & 1) * CHZ_WAVES * 8 + tl * 8 + (lane >> 3);
+        if (owner) atomicAdd(ms, mag);
+        __syncthreads();
+        if (owner) {
+            mag = *ms;
+            const uint32_t avg = mag / s.block_out;
+            const int32_t dbfs = (int32_t)((uint32_t)magnitude_dbfs(cst, avg) - gain);
+            const uint32_t present = dbfs >= threshold ? 1u : 0u;
+            const uint32_t allowed = present | tracking;
+            tracking = present;
+            if (!allowed && sc.scanning) scanner_step(sc, ss);
+            if (cfg.enabled) gain = agc_run(cst, cfg, st, avg, gain);
+        }
     }
 }
 
@@ -193,6 +359,32 @@ hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s)
     if (e != hipSuccess) return e;
     const uint32_t nh = a.n_sources * 2 * a.kp;
     hipLaunchKernelGGL(chz_history_kernel, dim3((nh + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_channelizer_scan(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
+                                   const ChzScanLaunch &s, hipStream_t st)
+{
+    if (n_fixed_wgs) {
+        const dim3 grid((a.n_out + a.t_blk - 1) / a.t_blk, n_fixed_wgs);
+        const size_t lds = CHZ_LDS_FIXED + 2 * ((size_t)a.t_blk * a.m + a.kp) + 16;
+        if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_kernel<CHZ_NQ_REG>, grid, dim3(512), lds, st, a);
+        else hipLaunchKernelGGL(chz_kernel<0>, grid, dim3(512), lds, st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (n_scan_wgs) {
+        ChzLaunch b = a;
+        b.wgs = scan_wgs;
+        const size_t lds = CHZ_LDS_FIXED + 2 * CHZ_PROTO_MAX + CHZ_SCAN_MAGSUM + 2 * ((size_t)s.t_blk * a.m + a.kp) + 16;
+        const dim3 block(64 * s.waves * s.wpt);
+        if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_scan_kernel<CHZ_NQ_REG>, dim3(n_scan_wgs), block, lds, st, b, s);
+        else hipLaunchKernelGGL(chz_scan_kernel<0>, dim3(n_scan_wgs), block, lds, st, b, s);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t nh = a.n_sources * 2 * a.kp;
+    hipLaunchKernelGGL(chz_history_kernel, dim3((nh + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

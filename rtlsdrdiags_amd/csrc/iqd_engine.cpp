@@ -215,6 +215,27 @@ void engine_geometry(const iqd_t *e, uint32_t *n_ch, uint32_t *block_bytes, uint
     *flags = e->flags;
 }
 }  // namespace iqd
+static int upload_params(iqd_t *e);
+static int agc_sync(iqd_t *e);
+namespace iqd {
+int engine_settle(iqd_t *e, ChzScanLaunch *s)
+{
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        int rc = upload_params(e);
+        if (rc == IQD_OK) rc = agc_sync(e);
+        if (rc != IQD_OK) return rc;
+    }
+    s->params = e->d_params;
+    s->agc_cfg = e->d_agc_cfg;
+    s->agc = e->d_agc;
+    s->scan_cfg = e->d_scan_cfg;
+    s->scan = e->d_scan;
+    s->tracker = e->d_tracker;
+    HIP_TRY(e, consts_address(&s->consts));
+    return IQD_OK;
+}
+}  // namespace iqd
 
 static bool range_ok(const iqd_t *e, uint32_t first, uint32_t n)
 {

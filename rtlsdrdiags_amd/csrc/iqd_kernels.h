@@ -83,6 +83,7 @@ struct SquelchLaunch {
 };
 
 hipError_t upload_consts(const Consts &c, hipStream_t s);
+hipError_t consts_address(const Consts **p);   // the device address of the uploaded tables (other kernel files read them)
 hipError_t launch_wbfm(const ChainLaunch &a, bool gated, bool mag, uint32_t n_blocks, hipStream_t s);
 hipError_t launch_fm(const ChainLaunch &a, bool gated, bool mag, uint32_t n_blocks, hipStream_t s);
 hipError_t launch_am(const ChainLaunch &a, int family, bool gated, bool mag, uint32_t n_blocks, hipStream_t s);

@@ -15,6 +15,14 @@ hipError_t upload_consts(const Consts &c, hipStream_t s)
     return hipMemcpyToSymbolAsync(HIP_SYMBOL(g_consts), &c, sizeof(Consts), 0, hipMemcpyHostToDevice, s);
 }
 
+hipError_t consts_address(const Consts **p)
+{
+    void *a = nullptr;
+    const hipError_t e = hipGetSymbolAddress(&a, HIP_SYMBOL(g_consts));
+    *p = (const Consts *)a;
+    return e;
+}
+
 // SIMT machine for the phase functions (see the host twin in tests/emu).
 struct DeviceExec {
     int tid;

@@ -69,7 +69,8 @@ def stepped_amplitude(block_amplitudes, block_samples=16384, seed=1234, sigma=1.
 def wideband(n_samples, rate, stations, seed=1234, sigma=2.0):
     """One wideband capture at `rate` (M x 256 kS/s): a sum of stations, each a dict with `offset` (Hz from the centre),
     `kind` ('fm' / 'wbfm' / 'am' / 'usb' / 'lsb'), `amplitude`, `tone` (Hz) and for FM `deviation` (Hz), quantised to
-    offset-binary uint8 with white noise of `sigma`."""
+    offset-binary uint8 with white noise of `sigma`.  Optional `on`: a list of (first, end) sample windows outside which
+    the station is keyed off (carriers that come and go)."""
     rng = np.random.default_rng(seed)
     n = np.arange(n_samples, dtype=np.float64)
     z = np.zeros(n_samples, np.complex128)
@@ -79,11 +80,17 @@ def wideband(n_samples, rate, stations, seed=1234, sigma=2.0):
         audio = 2 * np.pi * tone * n / rate
         if kind in ("fm", "wbfm"):
             dev = st.get("deviation", 5000.0 if kind == "fm" else 60000.0)
-            z += amp * np.exp(1j * (carrier + (dev / tone) * np.sin(audio)))
+            s = amp * np.exp(1j * (carrier + (dev / tone) * np.sin(audio)))
         elif kind == "am":
-            z += amp * (1.0 + st.get("depth", 0.5) * np.sin(audio)) * np.exp(1j * carrier)
+            s = amp * (1.0 + st.get("depth", 0.5) * np.sin(audio)) * np.exp(1j * carrier)
         elif kind in ("usb", "lsb"):
-            z += amp * np.exp(1j * (carrier + (audio if kind == "usb" else -audio)))
+            s = amp * np.exp(1j * (carrier + (audio if kind == "usb" else -audio)))
         else:
             raise ValueError(kind)
+        if "on" in st:
+            key = np.zeros(n_samples, bool)
+            for a, b in st["on"]:
+                key[max(0, int(a)):max(0, int(b))] = True
+            s = np.where(key, s, 0)
+        z += s
     return _finish(z, sigma, rng)

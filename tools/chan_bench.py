@@ -3,12 +3,21 @@
 per channel and call, M = 8, default taps.  Prints one JSON line:
 
     python tools/chan_bench.py [--steps K] [--settle-ms 100]
+    python tools/chan_bench.py --scan [--steps K]      (scanner-driven channels, written to profiles/ as well)
 
   chan_ms            per call, host clock around iqd_channelizer_run_device + synchronize (median of K steps, after
                      about --settle-ms of the same call untimed, like bench.py's clock settle)
   fm_ms / chan_fm_ms FM accept of the channelizer's rows alone (4096 channels x 2^17 bytes) / channelize + FM accept
   bytes, mfma_ops    what one call moves through HBM and issues on the matrix cores, with each as a share of the call's
-                     time at 8 TB/s and at 2x the 2.5 PF dense BF16 rate (the i8 rate)"""
+                     time at 8 TB/s and at 2x the 2.5 PF dense BF16 rate (the i8 rate)
+
+--scan: every channel follows its scanner (iqd_channelizer_follow_scanner), FM, squelch and scanning; each call is 4
+blocks (block_bytes 32768).  scan_call_ms: iqd_accept_wideband_device + synchronize; fixed_call_ms: the same call with
+the channels fixed (chz_kernel); rows_accept_ms: the accept on the rows alone, and walker_ms = scan_call_ms -
+rows_accept_ms, an estimate of the walker's share (the two are timed in separate loops).  The walker kernel's own time
+comes from a kernel trace of this run: rocprofv3 --kernel-trace (profiles/chan_scan_kernel_trace.json).  The same for 16
+following channels (one source), and host_loop_ms: today's host-driven loop for those 16 - one-block calls of
+iqd_channelizer_run + iqd_accept_iq with iqd_scanner_get + iqd_channelizer_tuning before each block."""
 import argparse
 import json
 import os
@@ -40,8 +49,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--settle-ms", type=float, default=100.0)
     ap.add_argument("--chan-only", action="store_true", help="only the channelizer calls (counter runs)")
+    ap.add_argument("--scan", action="store_true", help="scanner-driven channels (see above)")
     args = ap.parse_args()
     from rtlsdrdiags_amd import capi
+    if args.scan:
+        return scan_bench(capi, args)
 
     M, n_src, n_ch, n_out = 8, 16, 4096, 1 << 16
     bps = n_out * 2 * M
@@ -79,6 +91,76 @@ def main():
     print(json.dumps(line))
     z.close()
     eng.close()
+
+
+def _scan_setup(capi, n_ch, n_src, M, n_out, follow=True):
+    from rtlsdrdiags_amd import synth
+    bps = n_out * 2 * M
+    row = bps // M
+    eng = capi.Engine(n_ch)
+    eng.set_mode("fm")
+    eng.set_squelch(-40)
+    centre = 1_700_000_000
+    fs = 256000 * M
+    eng.scanner_set_parameters(centre - fs // 2, centre + fs // 2 - 64000, 25000)
+    eng.scanner_start(True)
+    z = capi.Channelizer(eng, M, n_ch, n_src)
+    z.set_channels(0, source=np.arange(n_ch) % n_src, gain_shift=np.full(n_ch, 3))
+    z.set_source_frequency([centre] * n_src)
+    z.follow_scanner(follow)
+    d_in, d_rows = eng.dev_alloc(n_src * bps), eng.dev_alloc(n_ch * row)
+    d_pcm, d_cnt = eng.dev_alloc(n_ch * row // 64 * 2), eng.dev_alloc(n_ch * 4)
+    eng.dev_upload(d_in, np.concatenate([synth.white_u8(bps // 2, seed=s) for s in range(n_src)]))
+    call = lambda: eng.accept_wideband_device(z, d_in, bps, d_rows, d_pcm, d_cnt)
+    rows = lambda: eng.accept_device(d_rows, row, d_pcm, d_cnt)
+    return eng, z, call, rows, bps
+
+
+def scan_bench(capi, args):
+    M, n_out = 8, 1 << 16
+    line = {"workload": "scanner-driven channelizer, M=8 / default taps / 2^16 outputs (4 blocks) per call"}
+    for n_ch, n_src, tag in ((4096, 16, ""), (16, 1, "_16")):
+        eng, z, call, rows, _ = _scan_setup(capi, n_ch, n_src, M, n_out)
+        scan_ms, _ = timed(call, eng.synchronize, args.steps, args.settle_ms)
+        rows_ms, _ = timed(rows, eng.synchronize, args.steps, args.settle_ms)
+        z.close(); eng.close()
+        eng, z, call, _, _ = _scan_setup(capi, n_ch, n_src, M, n_out, follow=False)
+        fixed_ms, _ = timed(call, eng.synchronize, args.steps, args.settle_ms)
+        z.close(); eng.close()
+        line.update({"scan_call_ms" + tag: round(scan_ms, 4), "rows_accept_ms" + tag: round(rows_ms, 4),
+                     "walker_ms" + tag: round(scan_ms - rows_ms, 4), "fixed_call_ms" + tag: round(fixed_ms, 4)})
+    # today's host-driven loop for the 16 channels: one block per call, retuned from the scanners between blocks
+    from rtlsdrdiags_amd import synth
+    n_ch, bb = 16, 32768
+    blk_bytes = bb * M
+    wide = synth.white_u8(n_out * M, seed=0).reshape(1, -1)
+    eng = capi.Engine(n_ch)
+    eng.set_mode("fm")
+    eng.set_squelch(-40)
+    centre, fs = 1_700_000_000, 256000 * M
+    eng.scanner_set_parameters(centre - fs // 2, centre + fs // 2 - 64000, 25000)
+    eng.scanner_start(True)
+    z = capi.Channelizer(eng, M, n_ch, 1)
+    z.set_channels(0, gain_shift=np.full(n_ch, 3))
+
+    def loop():
+        for b in range(wide.shape[1] // blk_bytes):
+            incs, silent = [], []
+            for c in range(n_ch):
+                d = capi.channelizer_tuning(M, centre, eng.scanner_tuned(c)[0], 1)
+                incs.append(0 if d is None else d)
+                silent.append(d is None)
+            z.set_channels(0, phase_inc=incs)
+            r = z.run(wide[:, b * blk_bytes:(b + 1) * blk_bytes])
+            r[np.array(silent)] = 0x80
+            eng.accept(r)
+    loop_ms, _ = timed(loop, eng.synchronize, max(5, args.steps // 5), args.settle_ms)
+    z.close(); eng.close()
+    line["host_loop_ms_16"] = round(loop_ms, 4)
+    print(json.dumps(line))
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "chan_scan_bench.json"), "w") as f:
+        f.write(json.dumps(line) + "\n")
 
 
 if __name__ == "__main__":
