@@ -75,6 +75,9 @@ def test_bit_identical_to_the_model(capi, P, M, K, n_src, n_ch):
     bad = [c for c in range(n_ch) if not np.array_equal(out[c], want[c])]
     assert not bad, (bad[:8], src[bad[0]], inc[bad[0]], shift[bad[0]])
     assert (out == 0).any() and (out == 255).any()     # both saturations were reached
+    if K not in ("default", 1):                         # and, with random taps, both rails of stage a (sat16)
+        a = np.concatenate(cm.channel(wide[src[0]], h, M, int(inc[0]), int(shift[0]), P, stage_a=True))
+        assert a.min() == -32768 and a.max() == 32767
     z.close()
     eng.close()
 

@@ -1,0 +1,506 @@
+"""Diagnostic: randomized channelizer-vs-model runs on an MI355X (include/iqdemod.h: iqd_channelizer_*, bit for bit
+against tests/chan_model.py; scanner-driven channels against tests/chan_scan_model.py on oracle chains).
+
+    python tools/chan_fuzz.py [cases] [seed]
+
+Bound by a case count, so that a seed is the same cases on every machine.  One case in eight is a scan case
+(FUZZ_SCAN=1: every case, FUZZ_SCAN=0: none).  On the first difference it prints the whole configuration, leaves the
+generator state of that case in fuzz_out/chan_fuzz_fail_state.json (FUZZ_STATE=<path>: there) and exits non-zero;
+FUZZ_REPLAY=<that file> python tools/chan_fuzz.py  runs that one case again.
+
+A plain case is drawn without a GPU (draw_plain) and then run (run_plain), so that a CPU test can hold the fixed slices
+of tests/test_gpu_chan_fuzz.py to the mutants of tests/chan_mutants.py before they go to the GPU (first_channel_kills)."""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np                                     # noqa: E402
+from rtlsdrdiags_amd import capi, synth                # noqa: E402
+from tests import chan_model as cm                     # noqa: E402
+from tests import chan_mutants as mu                   # noqa: E402
+from tests import chan_scan_model as sm                # noqa: E402
+
+K_EDGES = (1, 31, 32, 33, 255, 256, 257, 1023, 1024)
+INC_EDGES = (0, 1, 2 ** 31, 2 ** 31 - 1, 2 ** 32 - 1)
+BOUND_SUM = (2 ** 31 - 256) // 256
+SLICES = {"plain": ((9101, 150), (9102, 150)), "scan": (9103, 40)}   # (seed, cases): tests/test_gpu_chan_fuzz.py's
+MODEL_BUDGET = 4e7        # tap x wideband-sample products the model may spend per case (chan_model convolves at the
+#                           wide rate: K M outputs per channel); fewer channels are compared when a case is past it
+
+
+def t_max(M, K):
+    """outputs per window of the kernels (iqd_chan.cpp: chz_queue)"""
+    kp = (K + 31) // 32 * 32
+    return min(1024, (16384 - kp) // M) // 64 * 64
+
+
+def draw_taps(rng, M):
+    """(taps argument, h): None -> the default prototype"""
+    if rng.random() < 0.5:
+        K = int(rng.integers(1, 1025))
+    else:
+        K = int(rng.choice(K_EDGES + (0,)))
+        if K == 0:
+            return None, capi.channelizer_default_taps(M)
+    smax = min(32639, BOUND_SUM // K)
+    if rng.random() < 0.06:                               # exactly at the bound (K >= 258), else the largest taps
+        h = np.full(K, smax, np.int64) * rng.choice([-1, 1], K)
+        if K * 32639 >= BOUND_SUM:
+            h[:BOUND_SUM - K * smax] += np.sign(h[:BOUND_SUM - K * smax])
+        return h.astype(np.int16), h.astype(np.int16)
+    s = int(2.0 ** rng.uniform(3, np.log2(smax)))
+    h = rng.integers(-s, s + 1, K).astype(np.int16)
+    if rng.random() < 0.25:                               # a few taps at the extremes, whatever the scale of the rest
+        at = rng.choice(K, min(K, 3), replace=False)
+        h[at] = rng.choice([-32639, 32639], len(at))
+        if np.abs(h.astype(np.int64)).sum() > BOUND_SUM:
+            h[at] = 0
+    return h, h
+
+
+def draw_input(rng, M, n_samples):
+    kind = int(rng.integers(0, 5))
+    seed = int(rng.integers(1 << 30))
+    if kind == 0:
+        return "white", synth.white_u8(n_samples, seed)
+    if kind == 1:
+        return "rails", synth.rails_u8(n_samples, seed)
+    if kind == 2:
+        amp = int(2.0 ** rng.uniform(0, 5))
+        return "low %d" % amp, (128 + np.random.default_rng(seed).integers(-amp, amp + 1, 2 * n_samples)).astype(np.uint8)
+    if kind == 3:
+        fs = 256000.0 * M
+        st = [{"offset": float(rng.uniform(-0.45, 0.45)) * fs, "kind": ("fm", "am", "usb")[i % 3],
+               "amplitude": float(2.0 ** rng.uniform(1, 5.5)), "tone": 1000.0 + 300 * i,
+               "on": [(int(a), int(a) + int(rng.integers(1, n_samples + 1)))
+                      for a in rng.integers(0, n_samples, 2)]} for i in range(int(rng.integers(1, 4)))]
+        return "carriers", synth.wideband(n_samples, fs, st, seed=seed, sigma=float(rng.choice([0.0, 1.0, 4.0])))
+    return "constant", np.tile(rng.integers(0, 256, 2).astype(np.uint8), n_samples)
+
+
+def draw_count(rng):
+    r = rng.random()
+    if r < 0.4:
+        return int(rng.integers(1, 4))
+    if r < 0.65:
+        return int(rng.integers(7, 10))
+    if r < 0.87:
+        return int(rng.integers(63, 66))
+    return int(rng.integers(100, 400))
+
+
+def draw_inc(rng):
+    return int(rng.choice(INC_EDGES)) if rng.random() < 0.3 else int(rng.integers(0, 2 ** 32))
+
+
+def draw_plain(rng):
+    """One plain case, drawn without a GPU: the configuration, the wideband bytes and the script of calls and operator
+    steps between them."""
+    M = int(rng.integers(2, 65))
+    taps, h = draw_taps(rng, M)
+    K = len(h)
+    n_src = int(rng.integers(1, 5))
+    used = [s for s in range(n_src) if rng.random() < 0.7] or [int(rng.integers(0, n_src))]   # the rest: no channel
+    n_ch = draw_count(rng)
+    src = rng.choice(used, n_ch).astype(np.uint32)
+    inc = np.array([draw_inc(rng) for _ in range(n_ch)], np.uint64)
+    shift = rng.integers(0, 9, n_ch).astype(np.uint8)
+    tm = t_max(M, K)
+    calls, long_calls = [], 0
+    for _ in range(int(rng.integers(1, 9))):
+        r = rng.random()
+        if r < 0.3:
+            u = 1                                                       # the shortest call: 32 outputs
+        elif r < 0.55:
+            u = 2 * int(rng.integers(1, 6)) + 1                         # n_out % 64 == 32
+        elif r < 0.8 or long_calls >= 2:
+            u = 2 * int(rng.integers(1, 6))
+        else:
+            u = tm // 32 + int(rng.integers(1, 7))                      # several windows; odd: a 32-output tail
+            long_calls += 1
+        ops = []
+        if calls and rng.random() < 0.5:
+            what = int(rng.integers(0, 4))
+            if what == 0:
+                first = int(rng.integers(0, n_ch))
+                n = int(rng.integers(1, min(4, n_ch - first) + 1))
+                ops.append(("retune", first, [draw_inc(rng) for _ in range(n)], [int(v) for v in rng.integers(0, 9, n)]))
+            elif what == 1:
+                ops.append(("move", int(rng.integers(0, n_ch)), int(rng.integers(0, n_src))))
+            elif what == 2:
+                ops.append(("reset",))
+            else:
+                ops.append(("form",))
+        calls.append({"units": u, "ops": ops})
+    kinds, wide = [], []
+    total = sum(c["units"] for c in calls) * 32 * M
+    for s in range(n_src):
+        k, w = draw_input(rng, M, total)
+        kinds.append(k)
+        wide.append(w)
+    n_check = n_ch if n_ch <= 64 else 32
+    work = 4.0 * K * M * sum(c["units"] for c in calls) * 32
+    n_check = int(max(min(4, n_ch), min(n_check, MODEL_BUDGET // work)))
+    check = np.arange(n_ch) if n_check == n_ch else np.unique(np.concatenate(
+        [[0, n_ch - 1], rng.choice(n_ch, n_check, replace=False)]))
+    return {"M": M, "K": K, "taps": taps, "h": h, "n_src": n_src, "n_ch": n_ch, "src": src, "inc": inc, "shift": shift,
+            "calls": calls, "kinds": kinds, "wide": np.stack(wide), "check": check, "device_form": bool(rng.random() < 0.5)}
+
+
+def describe(cfg):
+    return ("M=%d K=%d (%s, sum|h|=%d) sources=%d (inputs %s) channels=%d calls(units of 64M bytes)=%r ops=%r "
+            "src=%r inc=%r shift=%r" % (
+                cfg["M"], cfg["K"], "default taps" if cfg["taps"] is None else "max|h|=%d" % np.abs(cfg["h"].astype(int)).max(),
+                np.abs(cfg["h"].astype(np.int64)).sum(), cfg["n_src"], cfg["kinds"], cfg["n_ch"],
+                [c["units"] for c in cfg["calls"]], [(i, c["ops"]) for i, c in enumerate(cfg["calls"]) if c["ops"]],
+                cfg["src"].tolist()[:16], cfg["inc"].tolist()[:16], cfg["shift"].tolist()[:16]))
+
+
+def walk(cfg):
+    """The script, step by step: yields (call index, device form?, ops applied before it, the epoch's wideband bytes
+    so far [n_src, bytes] (from the last reset), first output of this call in the epoch, outputs, src, inc, shift)."""
+    M, unit = cfg["M"], 64 * cfg["M"]
+    src, inc, shift = cfg["src"].copy(), cfg["inc"].copy(), cfg["shift"].copy()
+    device, at, epoch0 = cfg["device_form"], 0, 0
+    for i, call in enumerate(cfg["calls"]):
+        for op in call["ops"]:
+            if op[0] == "retune":
+                n = len(op[2])
+                inc[op[1]:op[1] + n], shift[op[1]:op[1] + n] = op[2], op[3]
+            elif op[0] == "move":
+                src[op[1]] = op[2]
+            elif op[0] == "reset":
+                epoch0 = at
+            else:
+                device = not device
+        nb = call["units"] * unit
+        yield (i, device, call["ops"], cfg["wide"][:, epoch0:at + nb], (at - epoch0) // (2 * M), nb // (2 * M),
+               src.copy(), inc.copy(), shift.copy())
+        at += nb
+
+
+def first_channel_kills(cfg, P):
+    """The mutants of tests/chan_mutants.py that channel 0 of this case exposes (CPU only)."""
+    killed = set()
+    for _, _, _, epoch, m0, n_out, src, inc, shift in walk(cfg):
+        out = mu.all_outputs(epoch[src[0]], cfg["h"], cfg["M"], int(inc[0]), int(shift[0]), P, m_range=(m0, m0 + n_out))
+        killed |= {m for m in mu.MUTANTS if not np.array_equal(out[m], out[None])}
+    return killed
+
+
+class Context:
+    """The pieces every case shares: the library, its phasor table, one engine for the plain cases."""
+
+    def __init__(self, oracle=None):
+        self.capi, self.P, self.oracle = capi, capi.channelizer_phasor_table(), oracle
+        self.eng = capi.Engine(1)
+        self.stats = {}            # what the scan cases met (blocks of checked following channels): see run_scan
+
+    def count(self, key, n=1):
+        self.stats[key] = self.stats.get(key, 0) + int(n)
+
+    def close(self):
+        self.eng.close()
+
+
+def run_plain(cfg, ctx):
+    """Runs the case's script through iqd_channelizer_run / run_device; None, or what differed."""
+    eng, P, M = ctx.eng, ctx.P, cfg["M"]
+    z = capi.Channelizer(eng, M, cfg["n_ch"], n_sources=cfg["n_src"], taps=cfg["taps"])
+    z.set_channels(0, source=cfg["src"], phase_inc=cfg["inc"], gain_shift=cfg["shift"])
+    bad = None
+    for i, device, ops, epoch, m0, n_out, src, inc, shift in walk(cfg):
+        for op in ops:
+            if op[0] == "retune":
+                z.set_channels(op[1], phase_inc=op[2], gain_shift=op[3])
+            elif op[0] == "move":
+                z.set_channels(op[1], source=[op[2]])
+            elif op[0] == "reset":
+                z.reset()
+        piece = np.ascontiguousarray(epoch[:, 2 * M * m0:])
+        if device:
+            d_in, d_out = eng.dev_alloc(piece.nbytes), eng.dev_alloc(cfg["n_ch"] * 2 * n_out)
+            eng.dev_upload(d_in, piece)
+            z.run_device(d_in, piece.shape[1], d_out)
+            eng.synchronize()
+            got = eng.dev_download(d_out, cfg["n_ch"] * 2 * n_out).reshape(cfg["n_ch"], -1)
+            eng.dev_free(d_in)
+            eng.dev_free(d_out)
+        else:
+            got = z.run(piece)
+        for c in cfg["check"]:
+            want = cm.channel(epoch[src[c]], cfg["h"], M, int(inc[c]), int(shift[c]), P, m_range=(m0, m0 + n_out))
+            if not np.array_equal(got[c], want):
+                d = np.flatnonzero(got[c] != want)
+                bad = ("call %d (%s form, %d outputs from output %d of the epoch): channel %d (source %d inc 0x%08x L %d) "
+                       "differs in %d bytes, first at byte %d (outputs %s): got %s, model %s" % (
+                           i, "device" if device else "host", n_out, m0, c, src[c], inc[c], shift[c], len(d), d[0],
+                           np.unique(d // 2)[:12].tolist(), got[c][d[:8]].tolist(), want[d[:8]].tolist()))
+                break
+        if bad:
+            break
+    z.close()
+    return bad
+
+
+def plain_case(rng, ctx):
+    cfg = draw_plain(rng)
+    bad = run_plain(cfg, ctx)
+    return None if bad is None else "plain case: %s\n  %s" % (describe(cfg), bad)
+
+
+# ------------------------------------------------------------------------------------------------------ scan cases
+BASE_HZ = 1_700_000_000
+
+
+def _dev_call(eng, z, wide, bb, first=0):
+    """iqd_accept_wideband_device -> rows, pcm, counts, magnitude, allowed"""
+    n, bps = z.n_channels, wide.shape[1]
+    row = bps // z.decimation
+    nblk = row // bb if row % bb == 0 else 1
+    sizes = (wide.nbytes, n * row, n * row // 64 * 2, 4 * n, 4 * n * nblk, n * nblk)
+    d = [eng.dev_alloc(max(16, s)) for s in sizes]
+    eng.dev_upload(d[0], np.ascontiguousarray(wide))
+    eng.accept_wideband_device(z, d[0], bps, d[1], d[2], d[3], d[4], d[5], first=first)
+    eng.synchronize()
+    out = (eng.dev_download(d[1], n * row).reshape(n, row), eng.dev_download(d[2], n * row // 64 * 2, np.int16).reshape(n, -1),
+           eng.dev_download(d[3], 4 * n, np.uint32), eng.dev_download(d[4], 4 * n * nblk, np.uint32).reshape(n, nblk),
+           eng.dev_download(d[5], n * nblk).reshape(n, nblk))
+    for p in d:
+        eng.dev_free(p)
+    return out
+
+
+def draw_grid(rng, M, centre, rot):
+    """A scan grid in station Hz around one source: inside the band, leaving it on either side, or touching the offsets
+    o = -Fs/2, Fs/2 - 1 and Fs/2 exactly (o = station + 64000 rot - centre)."""
+    fs = 256000 * M
+    st0 = centre - 64000 * rot                  # the station whose offset is 0
+    kind = int(rng.integers(0, 5))
+    step = int(rng.choice([fs // 16, fs // 8, 12500, fs // 4]))
+    if kind == 0:
+        start = st0 + int(rng.integers(-fs // 2, fs // 4))
+        return start, start + step * int(rng.integers(1, 6)), step
+    if kind == 1:                               # leaves the band at the top
+        start = st0 + fs // 2 - step * int(rng.integers(1, 4))
+        return start, start + step * 6, step
+    if kind == 2:                               # starts below the band
+        start = st0 - fs // 2 - step * int(rng.integers(1, 4))
+        return start, start + step * 6, step
+    if kind == 3:                               # ends exactly on o = Fs/2 (out), the step before on Fs/2 - 1 (in)
+        return st0 + fs // 2 - 3, st0 + fs // 2, 1
+    return st0 - fs // 2 - step, st0 - fs // 2 + step, step      # passes o = -Fs/2 exactly (in band)
+
+
+def run_scan(ctx, M, taps, h, n_src, n_ch, bb, calls, rng, check=None, follow_p=0.75, what="scan case"):
+    """Following and fixed channels through iqd_accept_wideband_device, against chan_scan_model.follow on oracle chains.
+    calls: engine blocks per call (0: one short block).  None, or what differed."""
+    P = ctx.P
+    fs, bo = 256000 * M, bb // 2
+    centres = [BASE_HZ + 3_000_000 * s + int(rng.integers(0, 1000)) for s in range(n_src)]
+    src = rng.integers(0, n_src, n_ch).astype(np.uint32)
+    inc = np.array([draw_inc(rng) for _ in range(n_ch)], np.uint64)
+    shift = rng.integers(0, 4, n_ch).astype(np.uint8)
+    follow = rng.random(n_ch) < follow_p
+    follow[0] = True
+    outs = [k * bo if k else 32 * int(rng.integers(1, max(2, bo // 32))) for k in calls]
+    total = sum(outs)
+    stations = lambda s: [{"offset": int(f * fs), "kind": ("fm", "am")[i % 2], "amplitude": 40.0,   # noqa: E731
+                           "on": [(int(a), int(a) + int(rng.integers(bo * M, 3 * bo * M + 1)))
+                                  for a in rng.integers(0, max(1, total * M), 2)]}
+                          for i, f in enumerate((-0.3, -0.1, 0.15, 0.35))]
+    wide = np.stack([synth.wideband(total * M, fs, stations(s), seed=int(rng.integers(1 << 30)), sigma=1.0)
+                     for s in range(n_src)])
+    check = list(range(n_ch)) if check is None else check
+    eng = capi.Engine(n_ch, block_bytes=bb)
+    eng.set_gain_trace(True)
+    chains = {c: ctx.oracle.chain() for c in check}
+    setup = []
+    for c in range(n_ch):
+        rot = int(rng.integers(-1, 2))
+        th = int(rng.choice([-200, -60, -50, -45, 0]))
+        agc = int(rng.integers(0, 2)) if rng.random() < 0.3 else None
+        grid = draw_grid(rng, M, centres[src[c]], rot)
+        setup.append([rot, th, agc, grid])
+        eng.set_mode("fm", c, 1)
+        eng.set_squelch(th, c, 1)
+        eng.set_rotation(rot, c, 1)
+        eng.scanner_set_parameters(*grid, first=c, n=1)
+        eng.scanner_start(True, c, 1)
+        if agc is not None:
+            eng.agc_set_type(agc, c, 1)
+            eng.agc_enable(True, c, 1)
+        if c in chains:
+            ch = chains[c]
+            ch.set_mode("fm")
+            ch.set_squelch(th)
+            ch.set_rotation(rot)
+            ch.scanner_set_parameters(*grid)
+            ch.scanner_start()
+            if agc is not None:
+                ch.agc_set_type(agc)
+                ch.agc_enable(True)
+    z = capi.Channelizer(eng, M, n_ch, n_src, taps=taps)
+    z.set_channels(0, source=src, phase_inc=inc, gain_shift=shift)
+    z.set_source_frequency(centres)
+    for c in np.flatnonzero(follow):
+        z.follow_scanner(True, int(c), 1)
+    log, bad, m_at = [], None, 0
+    for i, n_out in enumerate(outs):
+        if i and rng.random() < 0.6:                       # between calls: follow toggled, or a scanner command
+            c = int(rng.choice(check))
+            op = int(rng.integers(0, 4))
+            if op == 0:
+                follow[c] = not follow[c]
+                z.follow_scanner(bool(follow[c]), c, 1)
+                log.append((i, c, "follow", bool(follow[c])))
+                ctx.count("follow toggles")
+            elif op == 1:
+                eng.scanner_start(False, c, 1)
+                chains[c].scanner_stop()
+                log.append((i, c, "stop"))
+                ctx.count("scanner commands")
+            elif op == 2:                                  # (parameters are refused while scanning: stop first)
+                grid = draw_grid(rng, M, centres[src[c]], setup[c][0])
+                eng.scanner_start(False, c, 1)
+                chains[c].scanner_stop()
+                eng.scanner_set_parameters(*grid, first=c, n=1)
+                eng.scanner_start(True, c, 1)
+                chains[c].scanner_set_parameters(*grid)
+                chains[c].scanner_start()
+                log.append((i, c, "grid", grid))
+                ctx.count("scanner commands")
+            else:
+                eng.scanner_start(True, c, 1)
+                chains[c].scanner_start()
+                log.append((i, c, "start"))
+                ctx.count("scanner commands")
+        nblk = calls[i] if calls[i] else 1
+        blk = n_out // nblk
+        piece = wide[:, 2 * M * m_at:2 * M * (m_at + n_out)]
+        rows, pcm, cnt, mag, alw = _dev_call(eng, z, piece, bb)
+        trace = eng.frequency_trace(nblk)
+        for c in check:
+            s = int(src[c])
+            if follow[c]:
+                f0 = sm.scanner_hz(chains[c])
+                r, p, mg, al, tr = sm.follow(chains[c], wide[s], h, M, P, int(shift[c]), centres[s], blk, nblk,
+                                             m_first=m_at, rotation=setup[c][0])
+                quiet = (r.reshape(nblk, -1) == 0x80).all(axis=1)
+                ctx.count("blocks", nblk)
+                ctx.count("silent blocks", quiet.sum())
+                ctx.count("open blocks", (al != 0).sum())
+                ctx.count("closed blocks", (al == 0).sum())
+                ctx.count("retunes", (np.concatenate([[f0], tr[:-1]]) != tr).sum())
+                ctx.count("short blocks", calls[i] == 0)
+                ctx.count("agc blocks", nblk if setup[c][2] is not None else 0)
+            else:
+                r = cm.channel(wide[s], h, M, int(inc[c]), int(shift[c]), P, m_range=(m_at, m_at + n_out))
+                p, mg, al = chains[c].accept_stream(r, block_bytes=2 * blk)
+                tr = None                                    # (its scanner runs on all the same: the chain steps with it)
+            diff = ("rows" if not np.array_equal(rows[c], r) else
+                    "pcm" if cnt[c] != len(p) or not np.array_equal(pcm[c, :cnt[c]], p) else
+                    "magnitude" if not np.array_equal(mag[c], mg) else
+                    "allowed" if not np.array_equal(alw[c], al) else
+                    "frequency trace" if follow[c] and not np.array_equal(trace[c], tr) else None)
+            if diff:
+                d = np.flatnonzero(rows[c] != r)
+                bad = ("%s: M=%d K=%d (%s) sources=%d channels=%d block_bytes=%d calls(outputs)=%r: call %d, channel %d "
+                       "(source %d, following %s, rot/threshold/agc/grid %r, centre %d, L %d) differs in %s%s; ops %r" % (
+                           what, M, len(h), "default taps" if taps is None else "given taps", n_src, n_ch, bb, outs, i, c,
+                           s, bool(follow[c]), setup[c], centres[s], shift[c], diff,
+                           " (%d bytes, first at %d)" % (len(d), d[0]) if len(d) else "", log))
+                break
+        if bad:
+            break
+        m_at += n_out
+    z.close()
+    eng.close()
+    return bad
+
+
+def scan_case(rng, ctx):
+    M = int(rng.integers(2, 65))
+    if rng.random() < 0.5:
+        taps, h = None, capi.channelizer_default_taps(M)
+    else:
+        K = int(rng.choice(K_EDGES)) if rng.random() < 0.5 else int(rng.integers(1, 1025))
+        taps = h = rng.integers(-4000, 4001, K).astype(np.int16)
+    bb = int(rng.choice([256, 2048, 4096, 32768]))
+    n_ch = int(rng.choice([1, 3, 8, 9, 17]))
+    n_src = int(rng.integers(1, 4))
+    budget = 6 * 4096 // 2                                  # outputs per case and channel
+    per = max(1, min(5, budget // (bb // 2)))
+    calls = [0 if rng.random() < 0.25 else int(rng.integers(1, per + 1)) for _ in range(int(rng.integers(1, 5)))]
+    n_check = max(1, min(n_ch, int(MODEL_BUDGET // 2 // (4.0 * len(h) * M * max(32, sum(c * bb // 2 for c in calls))))))
+    check = sorted(set([0] + rng.choice(n_ch, n_check, replace=False).tolist()))
+    return run_scan(ctx, M, taps, h, n_src, n_ch, bb, calls, rng, check=check)
+
+
+def compute_units():
+    """torch.cuda.get_device_properties(0).multi_processor_count, asked in a child process: torch brings its own HIP
+    runtime, which finds no device in a process where the engine's has opened it first."""
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"],
+                       capture_output=True, text=True, timeout=300)
+    if r.returncode != 0:
+        raise RuntimeError("torch could not read the device's properties: " + r.stderr[-2000:])
+    return int(r.stdout.split()[-1])
+
+
+def fixed_scan_case(which, ctx, cus=None):
+    """The two walker geometries no draw reaches cheaply.  "waves3": enough following tiles (3 per compute unit) for
+    workgroups of three tiles and two waves per tile, at 256-byte engine blocks.  "window64": M = 64, K = 1024 - windows
+    of 192 outputs - at 2048-byte engine blocks: 1024 = 5 x 192 + 64, a last window of 64 outputs."""
+    rng = np.random.default_rng({"waves3": 31, "window64": 32}[which])
+    if which == "waves3":
+        n_ch = 3 * 8 * int(cus if cus else compute_units())
+        M = 4
+        check = sorted(rng.choice(n_ch, 24, replace=False).tolist())
+        return run_scan(ctx, M, None, capi.channelizer_default_taps(M), 1, n_ch, 256, [3, 2], rng, check=check,
+                        follow_p=1.1, what="fixed scan case waves3")
+    h = rng.integers(-4000, 4001, 1024).astype(np.int16)
+    check = sorted(rng.choice(40, 24, replace=False).tolist())
+    return run_scan(ctx, 64, h, h, 2, 40, 2048, [1, 1], rng, check=check, what="fixed scan case window64")
+
+
+def main():
+    cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    rng = np.random.default_rng(seed)
+    from oracle import bindings
+    ctx = Context(bindings.Oracle())
+    mode = os.environ.get("FUZZ_SCAN")
+
+    def one():
+        scan = mode == "1" or (mode is None and rng.random() < 0.125)
+        return scan, (scan_case(rng, ctx) if scan else plain_case(rng, ctx))
+
+    if os.environ.get("FUZZ_REPLAY"):
+        rng.bit_generator.state = json.load(open(os.environ["FUZZ_REPLAY"]))
+        _, bad = one()
+        print("replayed case:", "identical to the model" if bad is None else "MISMATCH: " + bad)
+        sys.exit(0 if bad is None else 1)
+    t0, n_scan = time.time(), 0
+    for case in range(cases):
+        if case and case % 500 == 0:
+            print("chan_fuzz: %d cases so far, %.0f s" % (case, time.time() - t0), flush=True)
+        state0 = rng.bit_generator.state
+        scan, bad = one()
+        n_scan += scan
+        if bad is not None:
+            print("MISMATCH in case %d of seed %d: %s" % (case, seed, bad))
+            path = os.environ.get("FUZZ_STATE", os.path.join("fuzz_out", "chan_fuzz_fail_state.json"))
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            json.dump(state0, open(path, "w"))
+            print("generator state kept: FUZZ_REPLAY=%s python tools/chan_fuzz.py" % path)
+            sys.exit(1)
+    print("chan_fuzz: %d cases (%d of them scan cases%s) identical to the model in %.0f s (seed %d)"
+          % (cases, n_scan, "".join(", %d %s" % (v, k) for k, v in ctx.stats.items()), time.time() - t0, seed))
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

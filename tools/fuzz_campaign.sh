@@ -24,3 +24,6 @@ run IQD_D4_LEADFREE=1 IQD_STREAM_MIN_SEG=1 FUZZ_WIDE=1 FUZZ_WIDE_RANGE=24,600 ti
 run IQD_D4_LEADFREE=2 FUZZ_WIDE=1 timeout 140 python3 tools/gpu_fuzz.py 120 $((87 + OFF))
 run IQD_D4_LEADFREE=1 IQD_WBFM_PATH=stream timeout 110 python3 tools/gpu_fuzz.py 90 $((88 + OFF))
 run IQD_D4_LEADFREE=0 FUZZ_WIDE=1 timeout 110 python3 tools/gpu_fuzz.py 90 $((89 + OFF))
+# the channelizer against its model: a case count, not seconds (plain cases; then scan cases only)
+run timeout 1500 python3 tools/chan_fuzz.py 20000 $((90 + OFF))
+run FUZZ_SCAN=1 timeout 1500 python3 tools/chan_fuzz.py 3000 $((91 + OFF))
