@@ -332,10 +332,11 @@ int iqd_resampler_run_device(iqd_resampler_t *r, const void *in_dev, size_t n_in
 typedef struct iqd_channelizer_config {
     uint32_t n_sources;     /* >= 1 */
     uint32_t n_channels;    /* >= 1 */
-    uint32_t decimation;    /* M, 2..64 */
-    uint32_t n_taps;        /* K, 1..1024 (ignored when taps == NULL) */
+    uint32_t decimation;    /* M, 2..64; with decimation_den > 1: P */
+    uint32_t n_taps;        /* K, 1..1024 (1..1024 Q); ignored when taps == NULL */
     const int16_t *taps;    /* h[0..K), Q15; NULL -> iqd_channelizer_default_taps(M) */
-    uint32_t reserved[4];   /* 0 */
+    uint32_t decimation_den; /* Q: 0 or 1 (integer decimation), 2, 4, 8 (fractional, below) */
+    uint32_t reserved[3];   /* 0 */
 } iqd_channelizer_config;
 typedef struct iqd_channelizer iqd_channelizer_t;
 int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_channelizer_t **out);
@@ -354,6 +355,30 @@ int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const
  * of 13 M + 1 taps).  default_taps returns the tap count (writing min(count, capacity) taps), or IQD_EINVAL. */
 int iqd_channelizer_phasor_table(int16_t out[8192]);
 int iqd_channelizer_default_taps(uint32_t decimation, int16_t *out, uint32_t capacity);
+
+/* Fractional decimation: captures at P / Q x 256 kS/s, Q = decimation_den in {2, 4, 8}, gcd(P, Q) = 1, 2 <= P / Q <= 64
+ * (2.4 MS/s is 75/8, 1.92 MS/s 15/2, 2.88 MS/s 45/4, 3.2 MS/s 25/2; else IQD_EINVAL).  Fs_wide = 256000 P / Q, which is
+ * what a channel's offset f_c = int32(d_c) / 2^32 Fs_wide refers to.  decimation_den = 0 or 1 is the integer channelizer
+ * above, bit for bit.  Everything not named here is as above:
+ *
+ *   prototype h[0..K) is given at the rate Q Fs_wide = 256000 P.  Branch r (0 <= r < Q) is h_r[k] = h[k Q + r],
+ *             k < ceil((K - r) / Q); a branch may be empty.  1 <= K, ceil(K / Q) <= 1024, |h[k]| <= 32639 and, for every
+ *             branch, 256 sum_k |h_r[k]| <= 2^31 - 256.  taps == NULL: iqd_channelizer_default_taps_q(P, Q).
+ *   output m  u = m P + P - 1, n = floor(u / Q) (the newest wide sample it uses), r = u mod Q; m counts since create /
+ *             reset.  Complex taps of the branch on its own sample delays: i_k = (k d_c mod 2^32) >> 20,
+ *             gr_r[k] = (h_r[k] Pc[i_k] + 2^14) >> 15, gi_r likewise; A = sum_k g_r[k] x[n - k]; then a, the rotation by
+ *             P[(n d_c mod 2^32) >> 20], y and the byte exactly as above.  An output of an empty branch is 0x80 0x80.
+ *   length    bytes_per_source: a multiple of 64 P (32 P wide samples, 32 Q outputs), so every call starts on u mod Q =
+ *             P - 1.  out and the rows of iqd_accept_wideband* are [n_channels][bytes_per_source Q / P]; the engine's
+ *             block_bytes rule applies to that row length.
+ *   default   iqd_channelizer_default_taps_q(P, Q): the design of iqd_channelizer_default_taps with M replaced by P
+ *             (13 P + 1 taps, cut-off 124 kHz at the rate 256000 P), quantised per branch: q_r = lrint(w_r / sum(w_r)
+ *             32768) and the first largest tap of each branch takes 32768 - sum(q_r), so that every branch has DC gain
+ *             exactly 32768: unity gain at L = 0 and no gain ripple at the output rate.  Q = 0 or 1:
+ *             iqd_channelizer_default_taps(P) tap for tap.  Host only, no GPU.
+ *   scanner   channels of a fractional channelizer cannot follow a scanner: iqd_channelizer_follow_scanner(z, ..., 1)
+ *             returns IQD_EINVAL.  iqd_channelizer_tuning is for integer M only. */
+int iqd_channelizer_default_taps_q(uint32_t decimation, uint32_t den, int16_t *out, uint32_t capacity);
 
 /* Scanner-driven channels: a channelizer channel c may FOLLOW THE SCANNER of the engine channel it feeds in
  * iqd_accept_wideband*(e, z, first_ch, ...), e_c = first_ch + c.  A following channel's row of one call is split into the

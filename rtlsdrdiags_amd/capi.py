@@ -43,7 +43,8 @@ class AgcState(C.Structure):
 
 class ChannelizerConfig(C.Structure):
     _fields_ = [("n_sources", C.c_uint32), ("n_channels", C.c_uint32), ("decimation", C.c_uint32),
-                ("n_taps", C.c_uint32), ("taps", C.c_void_p), ("reserved", C.c_uint32 * 4)]
+                ("n_taps", C.c_uint32), ("taps", C.c_void_p), ("decimation_den", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
 
 
 class IqdError(RuntimeError):
@@ -68,7 +69,7 @@ EXPORTS = [
     "iqd_channelizer_create", "iqd_channelizer_destroy", "iqd_channelizer_reset", "iqd_channelizer_set_channels",
     "iqd_channelizer_run_device", "iqd_channelizer_run", "iqd_accept_wideband", "iqd_channelizer_phasor_table",
     "iqd_channelizer_default_taps", "iqd_channelizer_set_source_frequency", "iqd_channelizer_follow_scanner",
-    "iqd_channelizer_tuning", "iqd_accept_wideband_device",
+    "iqd_channelizer_tuning", "iqd_accept_wideband_device", "iqd_channelizer_default_taps_q",
 ]
 
 _LIB = None
@@ -152,6 +153,7 @@ def _lib():
     L.iqd_accept_wideband.argtypes = [vp, vp, u32, vp, sz, vp, vp, vp, vp]
     L.iqd_channelizer_phasor_table.argtypes = [vp]
     L.iqd_channelizer_default_taps.argtypes = [u32, vp, u32]
+    L.iqd_channelizer_default_taps_q.argtypes = [u32, u32, vp, u32]
     L.iqd_channelizer_set_source_frequency.argtypes = [vp, u32, u32, vp]
     L.iqd_channelizer_follow_scanner.argtypes = [vp, u32, u32, C.c_int]
     L.iqd_channelizer_tuning.argtypes = [u32, u64, u64, C.c_int, C.POINTER(u32)]
@@ -332,7 +334,7 @@ class Engine:
         engine channels [first, first + chz.n_channels).  Returns (pcm rows, counts, magnitude, allowed) like accept()."""
         wide = np.ascontiguousarray(wide_u8, dtype=np.uint8).reshape(chz.n_sources, -1)
         bps = wide.shape[1]
-        row, n = bps // chz.decimation, chz.n_channels
+        row, n = bps // chz.decimation * chz.decimation_den, chz.n_channels
         nblk = row // self.block_bytes if row % self.block_bytes == 0 else 1
         pcm = np.zeros((n, row // 64), dtype=np.int16)
         cnt = np.zeros(n, dtype=np.uint32)
@@ -345,7 +347,7 @@ class Engine:
     def accept_wideband_device(self, chz, wide_dev, bytes_per_source, rows_dev, pcm_dev, count_dev=0, mag_dev=0,
                                allowed_dev=0, first=0):
         """iqd_accept_wideband_device: device pointers (integers), queued on the engine's stream; rows_dev receives the
-        cut rows [n_channels, bytes_per_source / M]."""
+        cut rows [n_channels, bytes_per_source / M] (fractional: bytes_per_source Q / P)."""
         self._check(self._L.iqd_accept_wideband_device(self._h, chz._h, int(first), C.c_void_p(wide_dev), int(bytes_per_source),
                                                        C.c_void_p(rows_dev), C.c_void_p(pcm_dev), C.c_void_p(count_dev or None),
                                                        C.c_void_p(mag_dev or None), C.c_void_p(allowed_dev or None)))
@@ -538,14 +540,21 @@ def channelizer_phasor_table():
     return out.reshape(4096, 2)
 
 
-def channelizer_default_taps(decimation):
-    """The library's default Q15 prototype for decimation M (host only, no GPU)."""
+def channelizer_default_taps(decimation, den=1):
+    """The library's default Q15 prototype for decimation M, or for the fractional decimation / den (the prototype at
+    the rate 256000 decimation, quantised per branch) (host only, no GPU)."""
     L = _lib()
-    n = L.iqd_channelizer_default_taps(int(decimation), None, 0)
+    if int(den) == 1:
+        n = L.iqd_channelizer_default_taps(int(decimation), None, 0)
+    else:
+        n = L.iqd_channelizer_default_taps_q(int(decimation), int(den), None, 0)
     if n < 0:
-        raise IqdError(n, "no default taps for decimation %r" % (decimation,))
+        raise IqdError(n, "no default taps for decimation %r / %r" % (decimation, den))
     out = np.zeros(n, np.int16)
-    L.iqd_channelizer_default_taps(int(decimation), _np_ptr(out), n)
+    if int(den) == 1:
+        L.iqd_channelizer_default_taps(int(decimation), _np_ptr(out), n)
+    else:
+        L.iqd_channelizer_default_taps_q(int(decimation), int(den), _np_ptr(out), n)
     return out
 
 
@@ -570,16 +579,18 @@ def phase_inc(offset_hz, fs):
 
 
 class Channelizer:
-    """iqd_channelizer_*: n_channels channels cut out of n_sources wideband captures at decimation x 256 kS/s."""
+    """iqd_channelizer_*: n_channels channels cut out of n_sources wideband captures at decimation / decimation_den x
+    256 kS/s (decimation_den 1, 2, 4 or 8; 2.4 MS/s is 75 / 8)."""
 
-    def __init__(self, engine, decimation, n_channels, n_sources=1, taps=None):
+    def __init__(self, engine, decimation, n_channels, n_sources=1, taps=None, decimation_den=1):
         self._e, self._L = engine, engine._L
         self._h = None
         self.decimation, self.n_channels, self.n_sources = int(decimation), int(n_channels), int(n_sources)
+        self.decimation_den = int(decimation_den) or 1
         self._taps = None if taps is None else np.ascontiguousarray(taps, np.int16)
         cfg = ChannelizerConfig(self.n_sources, self.n_channels, self.decimation,
                                 0 if self._taps is None else len(self._taps),
-                                None if self._taps is None else self._taps.ctypes.data)
+                                None if self._taps is None else self._taps.ctypes.data, int(decimation_den))
         h = C.c_void_p()
         engine._check(self._L.iqd_channelizer_create(engine._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -602,9 +613,10 @@ class Channelizer:
                                                             _np_ptr(sh)))
 
     def run(self, wide_u8):
-        """[n_sources, bytes_per_source] uint8 -> [n_channels, bytes_per_source / M] uint8 (host arrays)."""
+        """[n_sources, bytes_per_source] uint8 -> [n_channels, bytes_per_source decimation_den / decimation] uint8 (host
+        arrays)."""
         wide = np.ascontiguousarray(wide_u8, dtype=np.uint8).reshape(self.n_sources, -1)
-        out = np.zeros((self.n_channels, wide.shape[1] // self.decimation), np.uint8)
+        out = np.zeros((self.n_channels, wide.shape[1] // self.decimation * self.decimation_den), np.uint8)
         self._e._check(self._L.iqd_channelizer_run(self._h, _np_ptr(wide), wide.shape[1], _np_ptr(out)))
         return out
 

@@ -97,6 +97,7 @@ struct iqd_channelizer {
     int device = 0;
     hipStream_t stream = nullptr;
     uint32_t n_src = 0, n_ch = 0, m = 0, k = 0, kp = 0, nq = 0;
+    uint32_t q = 1, kb = 0;                       // decimation m / q; kb = ceil(k / q), the longest branch
     std::vector<int16_t> h, phasor;               // prototype [K]; (c, s) pairs [8192]
     std::vector<uint32_t> src, inc;
     std::vector<uint8_t> shift;
@@ -105,7 +106,7 @@ struct iqd_channelizer {
     uint32_t n_follow = 0;
     bool centre_dirty = true;
     uint32_t n_cus = 256;
-    std::vector<int16_t> gr, gi;                  // [n_ch][K]
+    std::vector<int16_t> gr, gi;                  // [n_ch][q branches][kb], zero from a branch's length on
     bool layout_dirty = true;                     // a channel changed source: regroup
     std::vector<uint8_t> ch_dirty;                // new taps since the last packing
     bool any_dirty = true;
@@ -117,7 +118,7 @@ struct iqd_channelizer {
     uint32_t scan_wpt = 1;                        // waves per tile
     uint32_t n_fixed_tiles = 0;                   // tiles [0, n_fixed_tiles) hold fixed channels, the rest following ones
     std::vector<uint32_t> slot_of;                // [n_ch]: tile * 8 + slot
-    std::vector<uint8_t> amat;                    // [n_tiles][nq][2][64][16]
+    std::vector<uint8_t> amat;                    // [n_tiles][q residues][nq][2][64][16]
     Buf d_amat, d_tiles, d_wgs, d_swgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
     Buf w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
     Staging stg[2];                               // tap uploads
@@ -155,9 +156,16 @@ void chz_channel_taps(const int16_t *h, uint32_t k, uint32_t inc, const int16_t 
 
 }  // namespace iqd
 
+// branch r of the prototype: h_r[k] = h[k q + r], k < ceil((K - r) / q) (q = 1: the prototype itself)
 static void chz_new_taps(iqd_channelizer *z, uint32_t c)
 {
-    chz_channel_taps(z->h.data(), z->k, z->inc[c], z->phasor.data(), &z->gr[(size_t)c * z->k], &z->gi[(size_t)c * z->k]);
+    std::vector<int16_t> hr(z->kb);
+    for (uint32_t r = 0; r < z->q; r++) {
+        const uint32_t kr = z->k > r ? (z->k - r + z->q - 1) / z->q : 0;
+        for (uint32_t k = 0; k < kr; k++) hr[k] = z->h[(size_t)k * z->q + r];
+        const size_t at = ((size_t)c * z->q + r) * z->kb;
+        chz_channel_taps(hr.data(), kr, z->inc[c], z->phasor.data(), &z->gr[at], &z->gi[at]);
+    }
     z->ch_dirty[c] = 1;
     z->any_dirty = true;
 }
@@ -203,11 +211,12 @@ static void chz_group(iqd_channelizer *z)
     for (const ChzWg &r : runs)
         for (uint32_t t = 0; t < r.n_tiles; t += z->scan_waves)
             z->swgs.push_back(ChzWg{r.source, r.first_tile + t, std::min(z->scan_waves, r.n_tiles - t), 0});
-    z->amat.assign(z->tiles.size() * z->nq * 2 * 64 * 16, 0);
+    z->amat.assign(z->tiles.size() * z->q * z->nq * 2 * 64 * 16, 0);
     std::fill(z->ch_dirty.begin(), z->ch_dirty.end(), 1);
 }
 
-// A operands of one tile slot (iqd_chan.h): rows 2 l (Ar) and 2 l + 1 (Ai), both planes, every K-chunk
+// A operands of one tile slot (iqd_chan.h): rows 2 l (Ar) and 2 l + 1 (Ai), both planes, every K-chunk, for every output
+// residue res (its branch: ((res + 1) m - 1) mod q)
 static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
 {
     ChzTile &t = z->tiles[tile];
@@ -215,24 +224,29 @@ static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
     t.inc[l] = c == CHZ_NONE ? 0 : z->inc[c];
     t.shift[l] = c == CHZ_NONE ? 0 : z->shift[c];
     if (tile >= z->n_fixed_tiles) return;   // a following channel: the walker builds its operands itself, per block
-    for (uint32_t row = 0; row < 2; row++) {
-        const uint32_t rho = 2 * l + row;
-        for (uint32_t q = 0; q < z->nq; q++)
-            for (uint32_t g = 0; g < 4; g++)
-                for (uint32_t j = 0; j < 16; j++) {
-                    const uint32_t kappa = 64 * q + 16 * g + j, comp = kappa & 1;
-                    const uint32_t kk = z->kp - 1 - kappa / 2;
-                    int32_t v = 0;
-                    if (c != CHZ_NONE && kk < z->k) {
-                        const int32_t r = z->gr[(size_t)c * z->k + kk], i = z->gi[(size_t)c * z->k + kk];
-                        v = row == 0 ? (comp == 0 ? r : -i) : (comp == 0 ? i : r);
+    for (uint32_t res = 0; res < z->q; res++) {
+        const uint32_t br = (uint32_t)((((uint64_t)res + 1) * z->m - 1) % z->q);
+        const size_t taps = c == CHZ_NONE ? 0 : ((size_t)c * z->q + br) * z->kb;
+        for (uint32_t row = 0; row < 2; row++) {
+            const uint32_t rho = 2 * l + row;
+            for (uint32_t q = 0; q < z->nq; q++)
+                for (uint32_t g = 0; g < 4; g++)
+                    for (uint32_t j = 0; j < 16; j++) {
+                        const uint32_t kappa = 64 * q + 16 * g + j, comp = kappa & 1;
+                        const uint32_t kk = z->kp - 1 - kappa / 2;
+                        int32_t v = 0;
+                        if (c != CHZ_NONE && kk < z->kb) {
+                            const int32_t r = z->gr[taps + kk], i = z->gi[taps + kk];
+                            v = row == 0 ? (comp == 0 ? r : -i) : (comp == 0 ? i : r);
+                        }
+                        const int8_t lo = (int8_t)(v & 0xff);
+                        const int8_t hi = (int8_t)((v - lo) / 256);
+                        const size_t lane = rho + 16 * g;
+                        for (uint32_t p = 0; p < 2; p++)
+                            z->amat[(((((size_t)tile * z->q + res) * z->nq + q) * 2 + p) * 64 + lane) * 16 + j] =
+                                (uint8_t)(p == 0 ? lo : hi);
                     }
-                    const int8_t lo = (int8_t)(v & 0xff);
-                    const int8_t hi = (int8_t)((v - lo) / 256);
-                    const size_t lane = rho + 16 * g;
-                    for (uint32_t p = 0; p < 2; p++)
-                        z->amat[((((size_t)tile * z->nq + q) * 2 + p) * 64 + lane) * 16 + j] = (uint8_t)(p == 0 ? lo : hi);
-                }
+        }
     }
 }
 
@@ -243,7 +257,7 @@ static int chz_upload(iqd_channelizer *z)
 {
     const bool regroup = z->layout_dirty;
     if (regroup) chz_group(z);
-    const size_t n_tiles = z->tiles.size(), tile_bytes = (size_t)z->nq * 2 * 64 * 16;
+    const size_t n_tiles = z->tiles.size(), tile_bytes = (size_t)z->q * z->nq * 2 * 64 * 16;
     std::vector<uint8_t> tile_dirty(n_tiles, regroup ? 1 : 0);
     for (uint32_t t = 0; t < n_tiles; t++)
         for (uint32_t l = 0; l < CHZ_TILE_CH; l++) {
@@ -315,21 +329,50 @@ int iqd_channelizer_phasor_table(int16_t out[8192])
 // 0.32 dB (tests/test_chan_host.py checks the quantised taps for M in 2..64).
 int iqd_channelizer_default_taps(uint32_t decimation, int16_t *out, uint32_t capacity)
 {
-    if (decimation < 2 || decimation > 64 || (!out && capacity)) return IQD_EINVAL;
+    return iqd_channelizer_default_taps_q(decimation, 1, out, capacity);
+}
+
+// Q in {1, 2, 4, 8}, gcd(P, Q) = 1 (P odd when Q > 1), 2 <= P / Q <= 64
+static bool chz_ratio_ok(uint32_t p, uint32_t q)
+{
+    if (q != 1 && q != 2 && q != 4 && q != 8) return false;
+    if (q > 1 && p % 2 == 0) return false;
+    return p >= 2 * q && p <= 64 * q;
+}
+
+// The same design at the rate 256000 P, quantised per branch r (taps r, r + Q, ...): each branch is normalised to DC gain
+// 32768 on its own and its first largest tap takes up the rounding, so the gain does not ripple at the output rate.
+int iqd_channelizer_default_taps_q(uint32_t decimation, uint32_t den, int16_t *out, uint32_t capacity)
+{
+    if (den == 0) den = 1;
+    if (!chz_ratio_ok(decimation, den) || (!out && capacity)) return IQD_EINVAL;
     const uint32_t n = 13 * decimation + 1;
     const double fc = 124.0 / (256.0 * decimation), beta = 5.0, i0b = bessel_i0(beta);
     std::vector<double> w(n);
-    double sum = 0;
     for (uint32_t i = 0; i < n; i++) {
         const double x = (double)i - (n - 1) / 2.0, r = 2.0 * i / (n - 1) - 1.0;
         const double sinc = x == 0 ? 1.0 : sin(2 * M_PI * fc * x) / (2 * M_PI * fc * x);
         w[i] = 2 * fc * sinc * bessel_i0(beta * sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
-        sum += w[i];
     }
     std::vector<int32_t> q(n);
-    int32_t qs = 0;
-    for (uint32_t i = 0; i < n; i++) qs += q[i] = (int32_t)lrint(w[i] / sum * 32768.0);
-    q[(n - 1) / 2] += 32768 - qs;
+    for (uint32_t br = 0; br < den; br++) {
+        double sum = 0, peak = 0;
+        for (uint32_t i = br; i < n; i += den) {
+            sum += w[i];
+            peak = std::max(peak, fabs(w[i]));
+        }
+        int32_t qs = 0;
+        uint32_t at = br;                          // the first largest tap (two equal ones: a rounding apart at most)
+        bool found = false;
+        for (uint32_t i = br; i < n; i += den) {
+            qs += q[i] = (int32_t)lrint(w[i] / sum * 32768.0);
+            if (!found && fabs(w[i]) >= peak * (1 - 1e-12)) {
+                at = i;
+                found = true;
+            }
+        }
+        q[at] += 32768 - qs;
+    }
     for (uint32_t i = 0; i < n && i < capacity; i++) out[i] = (int16_t)q[i];
     return (int)n;
 }
@@ -338,24 +381,32 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
 {
     if (!e) return IQD_EINVAL;
     if (!cfg || !out) return engine_fail(e, IQD_EINVAL, "NULL config or output pointer");
-    if (cfg->n_sources < 1 || cfg->n_channels < 1 || cfg->decimation < 2 || cfg->decimation > 64)
+    const uint32_t den = cfg->decimation_den ? cfg->decimation_den : 1;
+    if (cfg->n_sources < 1 || cfg->n_channels < 1 || (den == 1 && (cfg->decimation < 2 || cfg->decimation > 64)))
         return engine_fail(e, IQD_EINVAL, "channelizer: n_sources, n_channels >= 1 and 2 <= decimation <= 64");
+    if (!chz_ratio_ok(cfg->decimation, den))
+        return engine_fail(e, IQD_EINVAL, "channelizer: decimation_den must be 0, 1, 2, 4 or 8, coprime to decimation, and 2 <= "
+                                          "decimation / decimation_den <= 64");
     for (uint32_t r : cfg->reserved)
         if (r) return engine_fail(e, IQD_EINVAL, "channelizer: reserved fields must be 0");
     std::vector<int16_t> h;
     if (cfg->taps) {
-        if (cfg->n_taps < 1 || cfg->n_taps > 1024) return engine_fail(e, IQD_EINVAL, "channelizer: 1 <= n_taps <= 1024");
+        if (cfg->n_taps < 1 || cfg->n_taps > 1024 * den)
+            return engine_fail(e, IQD_EINVAL, den == 1 ? "channelizer: 1 <= n_taps <= 1024" : "channelizer: 1 <= n_taps <= 1024 * decimation_den");
         h.assign(cfg->taps, cfg->taps + cfg->n_taps);
     } else {
-        h.resize(iqd_channelizer_default_taps(cfg->decimation, nullptr, 0));
-        iqd_channelizer_default_taps(cfg->decimation, h.data(), (uint32_t)h.size());
+        h.resize(iqd_channelizer_default_taps_q(cfg->decimation, den, nullptr, 0));
+        iqd_channelizer_default_taps_q(cfg->decimation, den, h.data(), (uint32_t)h.size());
     }
-    int64_t abs_sum = 0;
-    for (int16_t t : h) {
+    for (int16_t t : h)
         if (t > 32639 || t < -32639) return engine_fail(e, IQD_EINVAL, "channelizer: |h[k]| must be <= 32639");
-        abs_sum += t < 0 ? -t : t;
+    for (uint32_t br = 0; br < den; br++) {
+        int64_t abs_sum = 0;
+        for (size_t i = br; i < h.size(); i += den) abs_sum += h[i] < 0 ? -h[i] : h[i];
+        if (256 * abs_sum > 2147483647LL - 255)
+            return engine_fail(e, IQD_EINVAL, den == 1 ? "channelizer: 256 sum |h| must be <= 2^31 - 256"
+                                                       : "channelizer: 256 sum |h| of every branch must be <= 2^31 - 256");
     }
-    if (256 * abs_sum > 2147483647LL - 255) return engine_fail(e, IQD_EINVAL, "channelizer: 256 sum |h| must be <= 2^31 - 256");
     if (cfg->n_channels > (1u << 20) || cfg->n_sources > (1u << 20)) return engine_fail(e, IQD_EINVAL, "channelizer: too many channels or sources");
 
     iqd_channelizer *z = new (std::nothrow) iqd_channelizer;
@@ -368,8 +419,10 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
     z->n_ch = cfg->n_channels;
     z->m = cfg->decimation;
     z->h = h;
+    z->q = den;
     z->k = (uint32_t)h.size();
-    z->kp = (z->k + 31) / 32 * 32;
+    z->kb = (z->k + den - 1) / den;
+    z->kp = (z->kb + 31) / 32 * 32;
     z->nq = z->kp / 32;
     z->phasor.resize(2 * CHZ_PHASOR);
     chz_phasor_table(z->phasor.data());
@@ -383,8 +436,8 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, z->device) == hipSuccess && cus > 0)
             z->n_cus = (uint32_t)cus;
     }
-    z->gr.assign((size_t)z->n_ch * z->k, 0);
-    z->gi.assign((size_t)z->n_ch * z->k, 0);
+    z->gr.assign((size_t)z->n_ch * z->q * z->kb, 0);
+    z->gi.assign((size_t)z->n_ch * z->q * z->kb, 0);
     z->ch_dirty.assign(z->n_ch, 0);
     for (uint32_t c = 0; c < z->n_ch; c++) chz_new_taps(z, c);
     std::vector<uint32_t> packed(CHZ_PHASOR);
@@ -395,7 +448,7 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
               z->d_hist[1].ensure(hb) == hipSuccess;
     ok = ok && hipMemcpy(z->d_phasor.p, packed.data(), CHZ_PHASOR * 4, hipMemcpyHostToDevice) == hipSuccess;
     std::vector<int16_t> proto(z->kp, 0);
-    std::copy(z->h.begin(), z->h.end(), proto.begin());
+    if (z->q == 1) std::copy(z->h.begin(), z->h.end(), proto.begin());   // (the walker's; it does not run at q > 1)
     ok = ok && z->d_proto.ensure(z->kp * 2) == hipSuccess && z->d_centre.ensure((size_t)z->n_src * 8) == hipSuccess;
     ok = ok && hipMemcpy(z->d_proto.p, proto.data(), z->kp * 2, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && chz_fill_history(z) == IQD_OK && hipStreamSynchronize(z->stream) == hipSuccess;
@@ -455,6 +508,7 @@ static int chz_check_len(iqd_channelizer *z, size_t bytes_per_source)
 {
     if (bytes_per_source == 0 || bytes_per_source % (64 * (size_t)z->m) != 0)
         return z->fail(IQD_EINVAL, "channelizer: bytes_per_source must be a positive multiple of 64 * decimation");
+    if (bytes_per_source / z->m * z->q > 0x7fffffffull) return z->fail(IQD_EINVAL, "channelizer: bytes_per_source too large");
     if (bytes_per_source > 0x7fffffffull) return z->fail(IQD_EINVAL, "channelizer: bytes_per_source too large");
     return IQD_OK;
 }
@@ -467,8 +521,11 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
         int rc = chz_upload(z);
         if (rc != IQD_OK) return rc;
     }
-    const uint32_t n_out = (uint32_t)(bytes_per_source / (2 * z->m));   // a multiple of 32
+    const uint32_t n_out = (uint32_t)(bytes_per_source / (2 * z->m) * z->q);   // a multiple of 32 q
     uint32_t t_max = std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - z->kp) / z->m) / CHZ_GROUP * CHZ_GROUP;
+    if (z->q > 1)   // windows of whole store groups: 2 (t_max m / q + kp) <= CHZ_FRAC_WIN_MAX
+        t_max = std::min<uint32_t>(1024, (uint32_t)((uint64_t)(CHZ_FRAC_WIN_MAX / 2 - z->kp) * z->q / z->m)) /
+                chz_frac_group(z->q) * chz_frac_group(z->q);
     ChzLaunch a{};
     a.wide = (const uint8_t *)wide_dev;
     a.hist = (const uint8_t *)z->d_hist[z->cur].p;
@@ -485,7 +542,8 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
     a.m = z->m;
     a.kp = z->kp;
     a.nq = z->nq;
-    a.nbase = (uint32_t)(z->m_abs * z->m);
+    a.nbase = (uint32_t)(z->m_abs / z->q * z->m);   // m_abs is a multiple of 32 q
+    a.den = z->q;
     if (!scan) {
         a.t_blk = n_out <= t_max ? n_out : t_max;
         CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->stream));
@@ -529,7 +587,7 @@ int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_
     int rc = chz_check_len(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(z->device);
-    const size_t ib = (size_t)z->n_src * bytes_per_source, ob = (size_t)z->n_ch * (bytes_per_source / z->m);
+    const size_t ib = (size_t)z->n_src * bytes_per_source, ob = (size_t)z->n_ch * (bytes_per_source / z->m * z->q);
     CHZ_TRY(z, z->st_wide.ensure(ib));
     CHZ_TRY(z, z->st_out.ensure(ob));
     CHZ_TRY(z, hipMemcpyAsync(z->st_wide.p, wide, ib, hipMemcpyHostToDevice, z->stream));
@@ -554,7 +612,7 @@ static int wideband_queue(iqd_t *e, iqd_channelizer *z, uint32_t first_ch, const
     uint32_t e_nch = 0, bb = 0, flags = 0;
     engine_geometry(e, &e_nch, &bb, &flags);
     if (first_ch >= e_nch || z->n_ch > e_nch - first_ch) return z->fail(IQD_EINVAL, "accept_wideband: bad engine channel range");
-    const size_t row = bytes_per_source / z->m;
+    const size_t row = bytes_per_source / z->m * z->q;
     if (row % bb != 0 && (row >= bb || row % 64 != 0))
         return z->fail(IQD_EINVAL, "accept_wideband: bytes_per_source / decimation must be a multiple of block_bytes, or one short block");
     const size_t nblk = row % bb == 0 ? row / bb : 1;
@@ -578,7 +636,7 @@ static int wideband_queue(iqd_t *e, iqd_channelizer *z, uint32_t first_ch, const
         // still, the channelizer steps back as well: the call's history went to the other buffer, so the stream stands
         // where it stood before the call, like the engine's.
         z->cur ^= 1;
-        z->m_abs -= bytes_per_source / (2 * z->m);
+        z->m_abs -= bytes_per_source / (2 * z->m) * z->q;
         return rc;
     }
     return IQD_OK;
@@ -594,7 +652,7 @@ int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const
     if (rc != IQD_OK) return rc;
     uint32_t e_nch = 0, bb = 0, flags = 0;
     engine_geometry(e, &e_nch, &bb, &flags);
-    const size_t row = bytes_per_source / z->m;
+    const size_t row = bytes_per_source / z->m * z->q;
     const size_t nblk = row % bb == 0 ? row / bb : 1;
     (void)hipSetDevice(z->device);
     const size_t n = z->n_ch, ib = (size_t)z->n_src * bytes_per_source;
@@ -638,6 +696,8 @@ int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_
 {
     if (!z) return IQD_EINVAL;
     if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
+    if (follow && z->q > 1)
+        return z->fail(IQD_EINVAL, "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow a scanner");
     for (uint32_t i = 0; i < n; i++) {
         uint8_t &f = z->follow[first + i];
         if (f == (follow ? 1 : 0)) continue;

@@ -28,6 +28,14 @@ constexpr uint32_t CHZ_NONE = 0xffffffffu;   // a padding slot of a tile
 constexpr uint32_t CHZ_PROTO_MAX = 1024;     // prototype taps (the scan walker keeps them in LDS, zero up to Kp)
 constexpr uint32_t CHZ_SCAN_MAGSUM = 2 * CHZ_WAVES * CHZ_TILE_CH * 4;   // the walker's per-block magnitude sums in LDS
 
+// Fractional decimation P / Q (Q = 2, 4, 8; chz_frac_kernel): the outputs m = rho + Q t of one residue rho are an integer
+// decimator by P (n = P t + floor(((rho + 1) P - 1) / Q)) with the tap set of branch ((rho + 1) P - 1) mod Q, so one MFMA
+// tile is 16 outputs of one residue; amat is [n_tiles][Q residues][nq][2 planes][64 lanes] and a store group is
+// chz_frac_group(Q) consecutive outputs, assembled from the Q residues in the wave's staging row.
+constexpr uint32_t chz_frac_group(uint32_t q) { return 16 * (q < 4 ? 4 : q); }
+constexpr uint32_t CHZ_FRAC_STAGE = CHZ_WAVES * CHZ_TILE_CH * 2 * chz_frac_group(8);   // the staging rows at Q = 8
+constexpr uint32_t CHZ_FRAC_WIN_MAX = CHZ_WIN_MAX - (CHZ_FRAC_STAGE - CHZ_WAVES * CHZ_TILE_CH * 2 * CHZ_GROUP);   // same LDS in all
+
 struct ChzTile {
     uint32_t ch[CHZ_TILE_CH];       // output row per slot, CHZ_NONE = padding (its taps are 0, nothing is stored)
     uint32_t inc[CHZ_TILE_CH];      // phase increment d_c
@@ -43,13 +51,14 @@ struct ChzLaunch {
     const uint8_t *hist;             // [n_sources][2 kp] raw bytes of samples [-kp, 0) of this call
     uint8_t *hist_next;              // the same after this call
     const uint32_t *phasor;          // [4096]: (uint16)c | s << 16
-    const uint4 *amat;               // [n_tiles][nq][2 planes][64 lanes] A operands
+    const uint4 *amat;               // [n_tiles][den residues][nq][2 planes][64 lanes] A operands
     const ChzTile *tiles;
     const ChzWg *wgs;
     uint8_t *out;                    // [n_ch][out_row]
     size_t bytes_per_source;
-    uint32_t n_sources, out_row, n_out, m, kp, nq, t_blk;
-    uint32_t nbase;                  // (outputs before this call * M) mod 2^32
+    uint32_t n_sources, out_row, n_out, m, kp, nq, t_blk;   // m: M, or P of a fractional decimation; kp, nq: per branch
+    uint32_t nbase;                  // (outputs before this call * M) mod 2^32; fractional: (outputs / Q) P mod 2^32
+    uint32_t den;                    // Q of a fractional channelizer (decimation m / den), 1 otherwise
 };
 
 // What the scan walker (chz_scan_kernel) reads besides ChzLaunch: a.wgs are its own workgroups (tiles of following
@@ -86,6 +95,8 @@ __host__ __device__ inline bool chz_tuning(uint32_t m, unsigned long long centre
 }
 
 hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s);
+// chz_frac_kernel alone, for a.den = 2, 4, 8 (iqd_chan_frac.hip); launch_channelizer adds the history kernel
+hipError_t launch_channelizer_frac(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s);
 // n_fixed_wgs workgroups of chz_kernel (a.wgs), n_scan_wgs of the walker (scan_wgs), then the history kernel
 hipError_t launch_channelizer_scan(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
                                    const ChzScanLaunch &s, hipStream_t st);

@@ -10,76 +10,15 @@
 //          byte pack into a per-wave LDS staging row of 8 channels x 128 bytes
 //   store  one 16-byte store per lane: 8 lanes write one channel's 128 contiguous bytes (whole sectors)
 // A second, tiny kernel writes each source's last Kp samples (the next call's history) with vector stores.
+// The device pieces shared with the fractional-rate kernel (iqd_chan_frac.hip) are in iqd_chan_dev.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "iqd_chan.h"
+#include "iqd_chan_dev.h"
 #include "iqd_chains.h"
 
 namespace iqd {
-
-typedef int chz_v4i __attribute__((ext_vector_type(4)));
-typedef short chz_s2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int32_t chz_sat(int32_t x, int32_t lo, int32_t hi) { return min(max(x, lo), hi); }
-
-__device__ __forceinline__ void chz_wave_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// B operand: 16 window bytes at LDS byte offset o (o even)
-__device__ __forceinline__ chz_v4i chz_b_operand(const uint8_t *win, uint32_t o)
-{
-    const uint32_t *w = (const uint32_t *)(win + (o & ~3u));
-    const uint32_t sh = o & 3u;
-    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-    chz_v4i b;
-    b.x = (int)__builtin_amdgcn_alignbyte(w1, w0, sh);
-    b.y = (int)__builtin_amdgcn_alignbyte(w2, w1, sh);
-    b.z = (int)__builtin_amdgcn_alignbyte(w3, w2, sh);
-    b.w = (int)__builtin_amdgcn_alignbyte(w4, w3, sh);
-    return b;
-}
-
-// one channel's output at one sample: the two rails' accumulators (lo / hi planes) -> two offset-binary bytes
-__device__ __forceinline__ uint32_t chz_epilogue(int32_t rlo, int32_t rhi, int32_t ilo, int32_t ihi, uint32_t p,
-                                                 int32_t rnd, uint32_t sh)
-{
-    // A = lo + 256 hi + 128 fits int32 (the tap bounds), but 256 hi alone need not: combined modulo 2^32
-    const int32_t Ar = (int32_t)((uint32_t)rlo + ((uint32_t)rhi << 8) + 128u);
-    const int32_t Ai = (int32_t)((uint32_t)ilo + ((uint32_t)ihi << 8) + 128u);
-    const int32_t ar = chz_sat(Ar >> 8, -32768, 32767);
-    const int32_t ai = chz_sat(Ai >> 8, -32768, 32767);
-    const int32_t c = (int16_t)(p & 0xffffu), s = (int16_t)(p >> 16);
-    const chz_s2 va = {(short)ar, (short)ai};
-    const chz_s2 vb = {(short)ai, (short)ar};
-    const chz_s2 cs = {(short)c, (short)s};
-    const chz_s2 cns = {(short)c, (short)-s};                          // |s| <= 32767: -s fits
-    const int32_t rr = __builtin_amdgcn_sdot2(va, cs, 0, false);       // ar c + ai s
-    const int32_t ri = __builtin_amdgcn_sdot2(vb, cns, 0, false);      // ai c - ar s
-    const int32_t yr = chz_sat((rr + rnd) >> sh, -128, 127), yi = chz_sat((ri + rnd) >> sh, -128, 127);
-    return (uint32_t)(yr + 128) | ((uint32_t)(yi + 128) << 8);
-}
-
-// Every thread of the workgroup: the window of outputs [m0, m0 + nloc) of one source - bytes [2 M m0 - 2 Kp, 2 M (m0 +
-// nloc)) of [history | this call], made signed - into LDS.
-__device__ __forceinline__ void chz_stage_window(const ChzLaunch &a, uint32_t source, uint32_t m0, uint32_t nloc, uint8_t *win)
-{
-    const uint32_t M = a.m, kp = a.kp;
-    const uint8_t *src = a.wide + (size_t)source * a.bytes_per_source;
-    const uint8_t *hsrc = a.hist + (size_t)source * 2 * kp;
-    const int64_t b0 = 2 * (int64_t)m0 * M - 2 * (int64_t)kp;   // 16-byte aligned, like the history's end
-    const uint32_t wbytes = 2 * (nloc * M + kp);
-    for (uint32_t i = threadIdx.x * 16; i < wbytes; i += blockDim.x * 16) {
-        const int64_t b = b0 + i;
-        uint4 v = b < 0 ? *(const uint4 *)(hsrc + 2 * kp + b) : *(const uint4 *)(src + b);
-        v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
-        *(uint4 *)(win + i) = v;
-    }
-}
 
 // One wave: its tile's outputs [m0, m0 + nloc) (nloc a multiple of 32) from the staged window, through the MFMA, the
 // epilogue and the 16-byte stores.  A: the tile's operands in registers (NQR > 0) or amat, read per group (NQR = 0).
@@ -353,7 +292,10 @@ hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s)
 {
     const dim3 grid((a.n_out + a.t_blk - 1) / a.t_blk, n_wgs);
     const size_t lds = CHZ_LDS_FIXED + 2 * ((size_t)a.t_blk * a.m + a.kp) + 16;
-    if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_kernel<CHZ_NQ_REG>, grid, dim3(512), lds, s, a);
+    if (a.den > 1) {
+        hipError_t e = launch_channelizer_frac(a, n_wgs, s);   // (iqd_chan_frac.hip)
+        if (e != hipSuccess) return e;
+    } else if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_kernel<CHZ_NQ_REG>, grid, dim3(512), lds, s, a);
     else hipLaunchKernelGGL(chz_kernel<0>, grid, dim3(512), lds, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

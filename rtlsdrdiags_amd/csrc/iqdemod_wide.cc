@@ -1,20 +1,21 @@
 // iqdemod_wide — many channels out of ONE wideband capture, straight over the C ABI (include/iqdemod.h): the one-receiver
 // counterpart of iqdemod_multi.  The capture is uint8 interleaved I/Q at decimation x 256 kS/s (an RTL-SDR at 2.048 MS/s
-// is decimation=8); every channel is cut out by the channelizer (iqd_channelizer_*) at its offset from the capture's
+// is decimation=8, one at 2.4 MS/s decimation=75/8); every channel is cut out by the channelizer (iqd_channelizer_*) at its offset from the capture's
 // centre and demodulated by one engine channel - one reference IqDataProcessor with its demodulators (Radio.cc:150-181).
 // PCM goes out as S16_LE at 8 kS/s (radioApp.cc:103-111), one file per channel.
 //
-//   iqdemod_wide in=cap.iq decimation=8 rate=2048000 offsets=<Hz>[,<Hz>...] modes=<m>[,<m>...] [gains=<L>[,<L>...]]
+//   iqdemod_wide in=cap.iq [decimation=8] rate=2048000 offsets=<Hz>[,<Hz>...] modes=<m>[,<m>...] [gains=<L>[,<L>...]]
 //                out=pcm_%d.s16 [blocks=K] [rotation=<r>] [centre=<Hz>] [scan=<start>,<end>,<step>[,...]]
 //                [squelch=<dBFS>[,<dBFS>...]] [freqlog=<file>]
 //
+//   decimation M, or P/Q with Q = 2, 4 or 8 (rate = 256000 P / Q); left out, it is rate / 256000 in lowest terms
 //   offsets    the channel's frequency minus the capture's centre, Hz (|offset| < rate / 2)
 //   modes      per channel, the list repeating (0 none 1 am 2 fm 3 wbfm 4 lsb 5 usb)
 //   gains      the channelizer's gain shift L per channel, 0..8 (6 dB each), the list repeating; default 0
 //   rotation   the engine's Fs/4 selector for every channel (+1, the reference's default, wants each offset at
 //              station + 64 kHz, like the reference's tuning, Radio.cc:617-618; 0 wants it on the station)
 //   blocks     32768-byte engine blocks per channel and call (default 4); a capture that ends inside a call ends with
-//              its whole blocks and then the rest, cut to a multiple of 64 x decimation bytes, as one short block
+//              its whole blocks and then the rest, cut to a multiple of 64 x decimation (64 P) bytes, as one short block
 //   centre     the capture's centre frequency, Hz (default 0): where scanning channels find their stations
 //   scan       per channel a scan grid of station frequencies, Hz (FrequencyScanner::setScanParameters, then start()),
 //              the triplets repeating like modes; such a channel follows its scanner (iqd_channelizer_follow_scanner):
@@ -66,7 +67,8 @@ std::vector<uint64_t> u64List(const char *s)
 int main(int argc, char **argv)
 {
   std::string in, out, freqlog;
-  uint32_t m = 0, blocks = 4;
+  uint32_t m = 0, den = 1, blocks = 4;
+  bool m_given = false;
   double rate = 0;
   int rotation = 1;
   uint64_t centre = 0;
@@ -76,7 +78,12 @@ int main(int argc, char **argv)
     const char *a = argv[i];
     if (!strncmp(a, "in=", 3)) in = a + 3;
     else if (!strncmp(a, "out=", 4)) out = a + 4;
-    else if (!strncmp(a, "decimation=", 11)) m = (uint32_t)atoi(a + 11);
+    else if (!strncmp(a, "decimation=", 11)) {
+      m = (uint32_t)atoi(a + 11);
+      const char *slash = strchr(a + 11, '/');
+      den = slash ? (uint32_t)atoi(slash + 1) : 1;
+      m_given = true;
+    }
     else if (!strncmp(a, "rate=", 5)) rate = atof(a + 5);
     else if (!strncmp(a, "offsets=", 8)) offsets = numList(a + 8);
     else if (!strncmp(a, "modes=", 6)) modes = numList(a + 6);
@@ -92,9 +99,22 @@ int main(int argc, char **argv)
       return 1;
     }
   }
-  if (in.empty() || out.empty() || m < 2 || rate <= 0 || offsets.empty() || modes.empty() || gains.empty() || !blocks ||
+  if (!m_given && rate > 0) {   // rate / 256000 = P / Q in lowest terms
+    const double r8 = rate / 32000.0;
+    if (r8 != floor(r8) || r8 < 16 || r8 > 512) {
+      fprintf(stderr, "iqdemod_wide: rate must be 256000 P / Q with Q = 1, 2, 4 or 8 and 2 <= P / Q <= 64 (or give decimation=P/Q)\n");
+      return 1;
+    }
+    m = (uint32_t)r8;
+    den = 8;
+    while (den > 1 && m % 2 == 0) {
+      m /= 2;
+      den /= 2;
+    }
+  }
+  if (in.empty() || out.empty() || m < 2 || den < 1 || rate <= 0 || offsets.empty() || modes.empty() || gains.empty() || !blocks ||
       scan.size() % 3 != 0) {
-    fprintf(stderr, "usage: iqdemod_wide in=cap.iq decimation=8 rate=2048000 offsets=<Hz,...> modes=<m,...> "
+    fprintf(stderr, "usage: iqdemod_wide in=cap.iq [decimation=8|75/8] rate=2048000 offsets=<Hz,...> modes=<m,...> "
                     "[gains=<L,...>] out=pcm_%%d.s16 [blocks=K] [rotation=r] [centre=Hz] [scan=start,end,step,...] "
                     "[squelch=dBFS,...] [freqlog=file]\n");
     return 1;
@@ -147,6 +167,7 @@ int main(int argc, char **argv)
   zc.n_sources = 1;
   zc.n_channels = n;
   zc.decimation = m;
+  zc.decimation_den = den;
   iqd_channelizer_t *z = nullptr;
   rc = iqd_channelizer_create(e, &zc, &z);
   if (rc == IQD_OK) rc = iqd_channelizer_set_channels(z, 0, n, source.data(), inc.data(), shift.data());
@@ -177,9 +198,10 @@ int main(int argc, char **argv)
     return 1;
   }
 
-  const size_t block = 32768 * (size_t)m, call = blocks * block, unit = 64 * (size_t)m;
+  // (wide bytes per engine block: 32768 m / den = 64 m (512 / den), whole calls of the channelizer)
+  const size_t block = 32768 / den * (size_t)m, call = blocks * block, unit = 64 * (size_t)m;
   std::vector<uint8_t> wide(call);
-  std::vector<int16_t> pcm((size_t)n * call / m / 64);
+  std::vector<int16_t> pcm((size_t)n * call / m * den / 64);
   std::vector<uint32_t> count(n);
   std::vector<uint8_t> open((size_t)n * blocks);
   uint64_t block_no = 0;
@@ -197,7 +219,7 @@ int main(int argc, char **argv)
       status = 3;
       return false;
     }
-    const size_t row = bytes / m / 64;
+    const size_t row = bytes / m * den / 64;
     for (uint32_t c = 0; c < n; c++)
       if (fwrite(&pcm[(size_t)c * row], 2, count[c], sinks[c]) != count[c]) {
         fprintf(stderr, "iqdemod_wide: write failed\n");

@@ -3,6 +3,7 @@
 per channel and call, M = 8, default taps.  Prints one JSON line:
 
     python tools/chan_bench.py [--steps K] [--settle-ms 100]
+    python tools/chan_bench.py --decimation 75 --den 8   (a fractional channelizer: a 2.4 MS/s capture, same outputs)
     python tools/chan_bench.py --scan [--steps K]      (scanner-driven channels, written to profiles/ as well)
 
   chan_ms            per call, host clock around iqd_channelizer_run_device + synchronize (median of K steps, after
@@ -50,18 +51,20 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=100.0)
     ap.add_argument("--chan-only", action="store_true", help="only the channelizer calls (counter runs)")
     ap.add_argument("--scan", action="store_true", help="scanner-driven channels (see above)")
+    ap.add_argument("--decimation", type=int, default=8, help="M, or P of a fractional decimation P / Q")
+    ap.add_argument("--den", type=int, default=1, help="Q of a fractional decimation (1, 2, 4, 8)")
     args = ap.parse_args()
     from rtlsdrdiags_amd import capi
     if args.scan:
         return scan_bench(capi, args)
 
-    M, n_src, n_ch, n_out = 8, 16, 4096, 1 << 16
-    bps = n_out * 2 * M
-    row = bps // M
+    M, Q, n_src, n_ch, n_out = args.decimation, args.den, 16, 4096, 1 << 16
+    bps = n_out * 2 * M // Q
+    row = 2 * n_out
     rng = np.random.default_rng(1)
     eng = capi.Engine(n_ch)
     eng.set_mode("fm")
-    z = capi.Channelizer(eng, M, n_ch, n_src)
+    z = capi.Channelizer(eng, M, n_ch, n_src, decimation_den=Q)
     z.set_channels(0, source=np.arange(n_ch) % n_src, phase_inc=rng.integers(0, 2 ** 32, n_ch, dtype=np.uint64),
                    gain_shift=np.full(n_ch, 3))
     d_in, d_out = eng.dev_alloc(n_src * bps), eng.dev_alloc(n_ch * row)
@@ -71,7 +74,8 @@ def main():
 
     chan = lambda: z.run_device(d_in, bps, d_out)
     chan_ms, chan_mean = timed(chan, eng.synchronize, args.steps, args.settle_ms)
-    line = {"workload": "channelizer 4096 ch / 16 sources / 2^16 outputs / M=8 / default taps", "chan_ms": round(chan_ms, 4),
+    line = {"workload": "channelizer 4096 ch / 16 sources / 2^16 outputs / M=%s / default taps" % (M if Q == 1 else "%d/%d" % (M, Q)),
+            "chan_ms": round(chan_ms, 4),
             "chan_mean_ms": round(chan_mean, 4)}
     if not args.chan_only:
         fm = lambda: eng.accept_device(d_out, row, d_pcm, d_cnt)
@@ -79,7 +83,7 @@ def main():
         fm_ms, _ = timed(fm, eng.synchronize, args.steps, args.settle_ms)
         both_ms, _ = timed(both, eng.synchronize, args.steps, args.settle_ms)
         line.update(fm_ms=round(fm_ms, 4), chan_fm_ms=round(both_ms, 4))
-    K = len(capi.channelizer_default_taps(M))
+    K = -(-len(capi.channelizer_default_taps(M, Q)) // Q)     # taps per branch
     nq = (K + 31) // 32
     tiles = n_src * ((n_ch // n_src + 7) // 8)
     mfma = tiles * (n_out // 16) * nq * 2              # v_mfma_i32_16x16x64_i8, two tap planes

@@ -4,7 +4,9 @@ against tests/chan_model.py; scanner-driven channels against tests/chan_scan_mod
     python tools/chan_fuzz.py [cases] [seed]
 
 Bound by a case count, so that a seed is the same cases on every machine.  One case in eight is a scan case
-(FUZZ_SCAN=1: every case, FUZZ_SCAN=0: none).  On the first difference it prints the whole configuration, leaves the
+(FUZZ_SCAN=1: every case, FUZZ_SCAN=0: none), and about one in six of the rest a fractional one (decimation P / Q, Q = 2,
+4, 8, against tests/chan_frac_model.py; FUZZ_FRAC=1: every such case, FUZZ_FRAC=0: none - a case kind is decided by the
+first draw of the case, so that a kept generator state replays the same kind).  On the first difference it prints the whole configuration, leaves the
 generator state of that case in fuzz_out/chan_fuzz_fail_state.json (FUZZ_STATE=<path>: there) and exits non-zero;
 FUZZ_REPLAY=<that file> python tools/chan_fuzz.py  runs that one case again.
 
@@ -18,6 +20,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np                                     # noqa: E402
 from rtlsdrdiags_amd import capi, synth                # noqa: E402
+from tests import chan_frac_model as fm                # noqa: E402
 from tests import chan_model as cm                     # noqa: E402
 from tests import chan_mutants as mu                   # noqa: E402
 from tests import chan_scan_model as sm                # noqa: E402
@@ -251,6 +254,120 @@ def plain_case(rng, ctx):
     return None if bad is None else "plain case: %s\n  %s" % (describe(cfg), bad)
 
 
+# ------------------------------------------------------------------------------------------------ fractional cases
+def frac_t_max(P, Q, kb):
+    """outputs per window of chz_frac_kernel (iqd_chan.cpp: chz_queue)"""
+    kp = (kb + 31) // 32 * 32
+    g = 16 * max(4, Q)
+    return min(1024, (12288 - kp) * Q // P) // g * g
+
+
+def draw_frac(rng):
+    """One fractional case, drawn without a GPU: decimation P / Q with gcd(P, Q) = 1 and 2 <= P / Q <= 64, a prototype of
+    up to 1024 Q taps within the per-branch bound (or the default one), calls in units of 64 P bytes with the operator
+    steps of the plain cases between them."""
+    Q = int(rng.choice([2, 4, 8]))
+    hi = 64 * Q if rng.random() < 0.25 else 12 * Q          # mostly modest ratios: the model's cost grows with P
+    P = int(rng.integers(Q, hi // 2)) * 2 + 1
+    r = rng.random()
+    if r < 0.35:
+        taps, h = None, capi.channelizer_default_taps(P, Q)
+    else:
+        K = int(rng.choice([1, Q - 1, Q, Q + 1, 32 * Q - 1, 32 * Q + 1, 1024 * Q - int(rng.integers(0, Q))])) if r < 0.6 \
+            else int(rng.integers(1, 1024 * Q + 1))
+        kb = -(-K // Q)
+        smax = min(32639, BOUND_SUM // kb)
+        sc = smax if rng.random() < 0.2 else int(2.0 ** rng.uniform(3, np.log2(smax)))
+        taps = h = rng.integers(-sc, sc + 1, K).astype(np.int16)
+    n_src = int(rng.integers(1, 4))
+    n_ch = draw_count(rng)
+    src = rng.integers(0, n_src, n_ch).astype(np.uint32)
+    inc = np.array([draw_inc(rng) for _ in range(n_ch)], np.uint64)
+    shift = rng.integers(0, 9, n_ch).astype(np.uint8)
+    tm = frac_t_max(P, Q, -(-len(h) // Q))
+    calls = []
+    for i in range(int(rng.integers(1, 7))):
+        u = 1 if rng.random() < 0.4 else int(rng.integers(2, 7))
+        if rng.random() < 0.15 and not any(c["units"] > 8 for c in calls):
+            u = tm // (32 * Q) + int(rng.integers(1, 4))    # several windows
+        ops = []
+        if calls and rng.random() < 0.5:
+            what = int(rng.integers(0, 4))
+            if what == 0:
+                first = int(rng.integers(0, n_ch))
+                n = int(rng.integers(1, min(4, n_ch - first) + 1))
+                ops.append(("retune", first, [draw_inc(rng) for _ in range(n)], [int(v) for v in rng.integers(0, 9, n)]))
+            elif what == 1:
+                ops.append(("move", int(rng.integers(0, n_ch)), int(rng.integers(0, n_src))))
+            elif what == 2:
+                ops.append(("reset",))
+            else:
+                ops.append(("form",))
+        calls.append({"units": u, "ops": ops})
+    total = sum(c["units"] for c in calls) * 32 * P
+    kinds, wide = [], []
+    for s in range(n_src):
+        k, w = draw_input(rng, -(-P // Q), total)
+        kinds.append(k)
+        wide.append(w)
+    work = 4.0 * -(-len(h) // Q) * sum(c["units"] for c in calls) * 32 * Q
+    n_check = int(max(min(4, n_ch), min(n_ch if n_ch <= 64 else 32, MODEL_BUDGET // work)))
+    check = np.arange(n_ch) if n_check >= n_ch else np.unique(np.concatenate(
+        [[0, n_ch - 1], rng.choice(n_ch, n_check, replace=False)]))
+    return {"M": P, "Q": Q, "K": len(h), "taps": taps, "h": h, "n_src": n_src, "n_ch": n_ch, "src": src, "inc": inc,
+            "shift": shift, "calls": calls, "kinds": kinds, "wide": np.stack(wide), "check": check,
+            "device_form": bool(rng.random() < 0.5)}
+
+
+def run_frac(cfg, ctx):
+    """Runs a fractional case's script through iqd_channelizer_run / run_device; None, or what differed."""
+    eng, Pt, P, Q = ctx.eng, ctx.P, cfg["M"], cfg["Q"]
+    z = capi.Channelizer(eng, P, cfg["n_ch"], n_sources=cfg["n_src"], taps=cfg["taps"], decimation_den=Q)
+    z.set_channels(0, source=cfg["src"], phase_inc=cfg["inc"], gain_shift=cfg["shift"])
+    bad = None
+    # walk() counts a call's outputs as for an integer decimation by P: Q times as many here
+    for i, device, ops, epoch, t0, nt, src, inc, shift in walk(cfg):
+        m0, n_out = t0 * Q, nt * Q
+        for op in ops:
+            if op[0] == "retune":
+                z.set_channels(op[1], phase_inc=op[2], gain_shift=op[3])
+            elif op[0] == "move":
+                z.set_channels(op[1], source=[op[2]])
+            elif op[0] == "reset":
+                z.reset()
+        piece = np.ascontiguousarray(epoch[:, 2 * P * t0:])
+        if device:
+            d_in, d_out = eng.dev_alloc(piece.nbytes), eng.dev_alloc(cfg["n_ch"] * 2 * n_out)
+            eng.dev_upload(d_in, piece)
+            z.run_device(d_in, piece.shape[1], d_out)
+            eng.synchronize()
+            got = eng.dev_download(d_out, cfg["n_ch"] * 2 * n_out).reshape(cfg["n_ch"], -1)
+            eng.dev_free(d_in)
+            eng.dev_free(d_out)
+        else:
+            got = z.run(piece)
+        ck = cfg["check"]
+        want = fm.channelize(epoch, cfg["h"], P, Q, src[ck], inc[ck], shift[ck], Pt, m_range=(m0, m0 + n_out))
+        for j, c in enumerate(ck):
+            if not np.array_equal(got[c], want[j]):
+                d = np.flatnonzero(got[c] != want[j])
+                bad = ("call %d (%s form, %d outputs from output %d of the epoch): channel %d (source %d inc 0x%08x L %d) "
+                       "differs in %d bytes, first at byte %d (outputs %s): got %s, model %s" % (
+                           i, "device" if device else "host", n_out, m0, c, src[c], inc[c], shift[c], len(d), d[0],
+                           np.unique(d // 2)[:12].tolist(), got[c][d[:8]].tolist(), want[j][d[:8]].tolist()))
+                break
+        if bad:
+            break
+    z.close()
+    return bad
+
+
+def frac_case(rng, ctx):
+    cfg = draw_frac(rng)
+    bad = run_frac(cfg, ctx)
+    return None if bad is None else "fractional case (decimation %d/%d): %s\n  %s" % (cfg["M"], cfg["Q"], describe(cfg), bad)
+
+
 # ------------------------------------------------------------------------------------------------------ scan cases
 BASE_HZ = 1_700_000_000
 
@@ -472,11 +589,15 @@ def main():
     rng = np.random.default_rng(seed)
     from oracle import bindings
     ctx = Context(bindings.Oracle())
-    mode = os.environ.get("FUZZ_SCAN")
+    mode, fmode = os.environ.get("FUZZ_SCAN"), os.environ.get("FUZZ_FRAC")
 
     def one():
-        scan = mode == "1" or (mode is None and rng.random() < 0.125)
-        return scan, (scan_case(rng, ctx) if scan else plain_case(rng, ctx))
+        r = rng.random() if mode is None else 1.0
+        scan = mode == "1" or (mode is None and r < 0.125)
+        if scan:
+            return scan, scan_case(rng, ctx)
+        frac = fmode == "1" or (fmode is None and r < 0.27)     # (FUZZ_SCAN=0 alone: plain cases only, as ever)
+        return scan, (frac_case(rng, ctx) if frac else plain_case(rng, ctx))
 
     if os.environ.get("FUZZ_REPLAY"):
         rng.bit_generator.state = json.load(open(os.environ["FUZZ_REPLAY"]))
