@@ -15,43 +15,22 @@
 
 #include "iqdemod.h"
 #include "iqd_chan.h"
+#include "iqd_hipres.h"
 
 using namespace iqd;
 
 namespace {
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // Page-locked staging of a tap upload: the copies read it after the host call returned, so a slot is refilled only once
 // the event behind its last copies has passed (two slots: the wait is for the upload before the previous one).
 struct Staging {
-    void *h = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;
+    PinnedArray<uint8_t> h;
+    Event done;
     bool pending = false;
     hipError_t ensure(size_t bytes)
     {
         if (!done) {
-            hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+            hipError_t e = hipEventCreateWithFlags(done.put(), hipEventDisableTiming);
             if (e != hipSuccess) return e;
         }
         if (pending) {
@@ -59,22 +38,7 @@ struct Staging {
             if (e != hipSuccess) return e;
             pending = false;
         }
-        if (bytes <= cap) return hipSuccess;
-        if (h) (void)hipHostFree(h);
-        h = nullptr;
-        cap = 0;
-        hipError_t e = hipHostMalloc(&h, bytes, hipHostMallocDefault);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    void release()
-    {
-        if (done) {
-            if (pending) (void)hipEventSynchronize(done);
-            (void)hipEventDestroy(done);
-        }
-        if (h) (void)hipHostFree(h);
-        *this = Staging();
+        return bytes <= h.n ? hipSuccess : h.alloc(bytes);
     }
 };
 
@@ -119,8 +83,8 @@ struct iqd_channelizer {
     uint32_t n_fixed_tiles = 0;                   // tiles [0, n_fixed_tiles) hold fixed channels, the rest following ones
     std::vector<uint32_t> slot_of;                // [n_ch]: tile * 8 + slot
     std::vector<uint8_t> amat;                    // [n_tiles][q residues][nq][2][64][16]
-    Buf d_amat, d_tiles, d_wgs, d_swgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
-    Buf w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
+    DevBufExact d_amat, d_tiles, d_wgs, d_swgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
+    DevBufExact w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
     Staging stg[2];                               // tap uploads
     int stg_cur = 0;
     int cur = 0;
@@ -285,7 +249,7 @@ static int chz_upload(iqd_channelizer *z)
     }
     Staging &st = z->stg[z->stg_cur];
     CHZ_TRY(z, st.ensure(bytes ? bytes : 16));
-    uint8_t *h = (uint8_t *)st.h;
+    uint8_t *h = st.h;
     size_t at = 0;
     auto copy = [&](void *dst, const void *src, size_t n) {
         memcpy(h + at, src, n);
@@ -295,8 +259,8 @@ static int chz_upload(iqd_channelizer *z)
     };
     for (const Run &r : runs) {
         const size_t na = r.first < z->n_fixed_tiles ? std::min<size_t>(r.n, z->n_fixed_tiles - r.first) : 0;
-        if (na) CHZ_TRY(z, copy((uint8_t *)z->d_amat.p + r.first * tile_bytes, &z->amat[r.first * tile_bytes], na * tile_bytes));
-        CHZ_TRY(z, copy((ChzTile *)z->d_tiles.p + r.first, &z->tiles[r.first], r.n * sizeof(ChzTile)));
+        if (na) CHZ_TRY(z, copy(z->d_amat.as<uint8_t>() + r.first * tile_bytes, &z->amat[r.first * tile_bytes], na * tile_bytes));
+        CHZ_TRY(z, copy(z->d_tiles.as<ChzTile>() + r.first, &z->tiles[r.first], r.n * sizeof(ChzTile)));
     }
     if (regroup && !z->wgs.empty()) CHZ_TRY(z, copy(z->d_wgs.p, z->wgs.data(), z->wgs.size() * sizeof(ChzWg)));
     if (regroup && !z->swgs.empty()) CHZ_TRY(z, copy(z->d_swgs.p, z->swgs.data(), z->swgs.size() * sizeof(ChzWg)));
@@ -464,12 +428,7 @@ void iqd_channelizer_destroy(iqd_channelizer_t *z)
 {
     if (!z) return;
     (void)hipSetDevice(z->device);
-    (void)hipStreamSynchronize(z->stream);
-    for (Buf *b : {&z->d_amat, &z->d_tiles, &z->d_wgs, &z->d_swgs, &z->d_phasor, &z->d_proto, &z->d_centre, &z->d_hist[0], &z->d_hist[1], &z->st_wide, &z->st_out,
-                   &z->w_rows, &z->w_pcm, &z->w_cnt, &z->w_mag, &z->w_sp})
-        b->release();
-    z->stg[0].release();
-    z->stg[1].release();
+    (void)hipStreamSynchronize(z->stream);   // (the tap uploads' events lie on it)
     delete z;
 }
 
@@ -528,12 +487,12 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
                 chz_frac_group(z->q) * chz_frac_group(z->q);
     ChzLaunch a{};
     a.wide = (const uint8_t *)wide_dev;
-    a.hist = (const uint8_t *)z->d_hist[z->cur].p;
-    a.hist_next = (uint8_t *)z->d_hist[z->cur ^ 1].p;
-    a.phasor = (const uint32_t *)z->d_phasor.p;
-    a.amat = (const uint4 *)z->d_amat.p;
-    a.tiles = (const ChzTile *)z->d_tiles.p;
-    a.wgs = (const ChzWg *)z->d_wgs.p;
+    a.hist = z->d_hist[z->cur].as<uint8_t>();
+    a.hist_next = z->d_hist[z->cur ^ 1].as<uint8_t>();
+    a.phasor = z->d_phasor.as<uint32_t>();
+    a.amat = z->d_amat.as<uint4>();
+    a.tiles = z->d_tiles.as<ChzTile>();
+    a.wgs = z->d_wgs.as<ChzWg>();
     a.out = (uint8_t *)out_dev;
     a.bytes_per_source = bytes_per_source;
     a.n_sources = z->n_src;
@@ -544,25 +503,20 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
     a.nq = z->nq;
     a.nbase = (uint32_t)(z->m_abs / z->q * z->m);   // m_abs is a multiple of 32 q
     a.den = z->q;
-    if (!scan) {
-        a.t_blk = n_out <= t_max ? n_out : t_max;
-        CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->stream));
-    } else {
+    a.t_blk = n_out <= t_max ? n_out : t_max;
+    if (scan) {
         if (z->centre_dirty) {
             CHZ_TRY(z, hipMemcpyAsync(z->d_centre.p, z->centre.data(), (size_t)z->n_src * 8, hipMemcpyHostToDevice, z->stream));
             CHZ_TRY(z, hipStreamSynchronize(z->stream));   // (the host vector may change once this returns)
             z->centre_dirty = false;
         }
-        scan->proto = (const int16_t *)z->d_proto.p;
-        scan->centre = (const unsigned long long *)z->d_centre.p;
+        scan->proto = z->d_proto.as<int16_t>();
+        scan->centre = z->d_centre.as<unsigned long long>();
         scan->waves = z->scan_waves;
         scan->wpt = z->scan_wpt;
-        // chz_kernel's windows as before; the walker's stay inside one block
-        a.t_blk = n_out <= t_max ? n_out : t_max;
-        scan->t_blk = scan->block_out <= t_max ? scan->block_out : t_max;
-        CHZ_TRY(z, launch_channelizer_scan(a, (uint32_t)z->wgs.size(), (const ChzWg *)z->d_swgs.p, (uint32_t)z->swgs.size(),
-                                           *scan, z->stream));
+        scan->t_blk = scan->block_out <= t_max ? scan->block_out : t_max;   // the walker's windows stay inside one block
     }
+    CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->d_swgs.as<ChzWg>(), scan ? (uint32_t)z->swgs.size() : 0u, scan, z->stream));
     z->cur ^= 1;
     z->m_abs += n_out;
     return IQD_OK;

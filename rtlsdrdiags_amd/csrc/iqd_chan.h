@@ -94,12 +94,12 @@ __host__ __device__ inline bool chz_tuning(uint32_t m, unsigned long long centre
     return true;
 }
 
-hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s);
+// One call: n_fixed_wgs workgroups of the fixed channels' kernel (a.wgs; chz_frac_kernel when a.den > 1, else chz_kernel),
+// n_scan_wgs of the walker (scan_wgs, with scan; none: 0 and NULL), then the history kernel
+hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
+                              const ChzScanLaunch *scan, hipStream_t st);
 // chz_frac_kernel alone, for a.den = 2, 4, 8 (iqd_chan_frac.hip); launch_channelizer adds the history kernel
 hipError_t launch_channelizer_frac(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s);
-// n_fixed_wgs workgroups of chz_kernel (a.wgs), n_scan_wgs of the walker (scan_wgs), then the history kernel
-hipError_t launch_channelizer_scan(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
-                                   const ChzScanLaunch &s, hipStream_t st);
 
 // host-only spec pieces (iqd_chan.cpp)
 void chz_phasor_table(int16_t *out /* [8192] (c, s) pairs */);

@@ -288,40 +288,28 @@ __global__ void chz_history_kernel(const ChzLaunch a)
     a.hist_next[t] = b < 0 ? a.hist[(size_t)s * hb + hb + b] : a.wide[(size_t)s * a.bytes_per_source + b];
 }
 
-hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s)
+hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
+                              const ChzScanLaunch *scan, hipStream_t st)
 {
-    const dim3 grid((a.n_out + a.t_blk - 1) / a.t_blk, n_wgs);
+    const dim3 grid((a.n_out + a.t_blk - 1) / a.t_blk, n_fixed_wgs);
     const size_t lds = CHZ_LDS_FIXED + 2 * ((size_t)a.t_blk * a.m + a.kp) + 16;
-    if (a.den > 1) {
-        hipError_t e = launch_channelizer_frac(a, n_wgs, s);   // (iqd_chan_frac.hip)
-        if (e != hipSuccess) return e;
-    } else if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_kernel<CHZ_NQ_REG>, grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL(chz_kernel<0>, grid, dim3(512), lds, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const uint32_t nh = a.n_sources * 2 * a.kp;
-    hipLaunchKernelGGL(chz_history_kernel, dim3((nh + 255) / 256), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_channelizer_scan(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
-                                   const ChzScanLaunch &s, hipStream_t st)
-{
     if (n_fixed_wgs) {
-        const dim3 grid((a.n_out + a.t_blk - 1) / a.t_blk, n_fixed_wgs);
-        const size_t lds = CHZ_LDS_FIXED + 2 * ((size_t)a.t_blk * a.m + a.kp) + 16;
-        if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_kernel<CHZ_NQ_REG>, grid, dim3(512), lds, st, a);
+        if (a.den > 1) {
+            hipError_t e = launch_channelizer_frac(a, n_fixed_wgs, st);   // (iqd_chan_frac.hip)
+            if (e != hipSuccess) return e;
+        } else if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_kernel<CHZ_NQ_REG>, grid, dim3(512), lds, st, a);
         else hipLaunchKernelGGL(chz_kernel<0>, grid, dim3(512), lds, st, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (n_scan_wgs) {
+    if (scan && n_scan_wgs) {
+        const ChzScanLaunch &s = *scan;
         ChzLaunch b = a;
         b.wgs = scan_wgs;
-        const size_t lds = CHZ_LDS_FIXED + 2 * CHZ_PROTO_MAX + CHZ_SCAN_MAGSUM + 2 * ((size_t)s.t_blk * a.m + a.kp) + 16;
+        const size_t scan_lds = CHZ_LDS_FIXED + 2 * CHZ_PROTO_MAX + CHZ_SCAN_MAGSUM + 2 * ((size_t)s.t_blk * a.m + a.kp) + 16;
         const dim3 block(64 * s.waves * s.wpt);
-        if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_scan_kernel<CHZ_NQ_REG>, dim3(n_scan_wgs), block, lds, st, b, s);
-        else hipLaunchKernelGGL(chz_scan_kernel<0>, dim3(n_scan_wgs), block, lds, st, b, s);
+        if (a.nq <= CHZ_NQ_REG) hipLaunchKernelGGL(chz_scan_kernel<CHZ_NQ_REG>, dim3(n_scan_wgs), block, scan_lds, st, b, s);
+        else hipLaunchKernelGGL(chz_scan_kernel<0>, dim3(n_scan_wgs), block, scan_lds, st, b, s);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -1,6 +1,6 @@
 // The plan of one accept call: which kernels run for which demodulator family, on how many workgroups, cut into which
 // segments - decided ONCE, on the host, from plain data, before anything is queued (plan, then execute).
-// iqd_engine.cpp describes the call (describe_call), plan_call() decides, the queue_* functions only carry the plan out.
+// iqd_accept.cpp describes the call (describe_call), plan_call() decides, the queue_* functions only carry the plan out.
 // No HIP in here: tests/emu compiles this file for the CPU tier (tests/test_host_planning.py enumerates plans).
 #pragma once
 #include <stddef.h>
