@@ -419,6 +419,36 @@ int iqd_channelizer_tuning(uint32_t decimation, uint64_t source_centre_hz, uint6
 int iqd_accept_wideband_device(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const void *wide_dev, size_t bytes_per_source,
                                void *rows_dev, void *pcm_dev, void *pcm_count_dev, void *magnitude_dev, void *signal_present_dev);
 
+/* Band survey: where in the capture are the signals?  Per block and per point of a grid, the magnitude the squelch would
+ * see - without placing channels, writing rows or running an accept.
+ *
+ *   point p   a virtual channel measured on EVERY source: increment d_p, gain shift L_p in [0, 8] (gain_shift == NULL: 0).
+ *             iqd_channelizer_set_survey(z, n_points, ...): 0 <= n_points <= 4096, 0 clears the survey.  The points are
+ *             independent of set_channels, of the following flags and of each other; iqd_channelizer_reset keeps them.
+ *   result    magnitude[n_sources][n_blocks][n_points] uint32, n_blocks = row_bytes / block_bytes, row_bytes =
+ *             bytes_per_source / M (bytes_per_source Q / P).  Entry (s, b, p) = floor(S / (block_bytes / 2)), S the sum
+ *             over the block_bytes / 2 outputs of block b of SignalDetector's per-sample magnitude of the byte pair that a
+ *             channel (source s, d_p, L_p) gets from the spec above (the fractional one for decimation_den > 1):
+ *             a = |I - 128|, b = |Q - 128| (|-128| = 128), max(a, b) + (min(a, b) >> 1).  That is exactly the magnitude
+ *             iqd_accept_wideband reports for such a channel with an engine whose block is block_bytes.
+ *   state     a survey looks and does not touch: it reads the channelizer's current history and sample count and advances
+ *             neither, so survey(x) followed by run(x) / accept_wideband(x) see the same samples.  Surveying bytes that
+ *             were already run is the caller's error (they would be measured as if they followed themselves).
+ *   lengths   bytes_per_source as for a run (a multiple of 64 M, of 64 P for fractional rates).  block_bytes, in row bytes:
+ *             a multiple of 64 (decimation_den <= 1) or of 256 (decimation_den > 1), a divisor of row_bytes, at most 2^24.
+ *             wide_dev and magnitude_dev: device memory, 16-byte aligned.
+ *   refusals  IQD_EINVAL before anything is queued: any of the above violated, no points set, or any channel following
+ *             its scanner.
+ * The _device form is queued on the engine's stream and returns once queued; the host form returns when done.
+ * iqd_magnitude_dbfs: host only, no GPU - the level the squelch compares (convertMagnitudeToDbFs: table entry of
+ * min(magnitude, 127), minus 42), before any gain is subtracted, so that survey values can be held against thresholds. */
+int iqd_channelizer_set_survey(iqd_channelizer_t *z, uint32_t n_points, const uint32_t *phase_inc, const uint8_t *gain_shift);
+int iqd_channelizer_survey_device(iqd_channelizer_t *z, const void *wide_dev, size_t bytes_per_source, uint32_t block_bytes,
+                                  void *magnitude_dev);
+int iqd_channelizer_survey(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_per_source, uint32_t block_bytes,
+                           uint32_t *magnitude);
+int32_t iqd_magnitude_dbfs(uint32_t magnitude);
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

@@ -70,6 +70,7 @@ EXPORTS = [
     "iqd_channelizer_run_device", "iqd_channelizer_run", "iqd_accept_wideband", "iqd_channelizer_phasor_table",
     "iqd_channelizer_default_taps", "iqd_channelizer_set_source_frequency", "iqd_channelizer_follow_scanner",
     "iqd_channelizer_tuning", "iqd_accept_wideband_device", "iqd_channelizer_default_taps_q",
+    "iqd_channelizer_set_survey", "iqd_channelizer_survey_device", "iqd_channelizer_survey", "iqd_magnitude_dbfs",
 ]
 
 _LIB = None
@@ -158,6 +159,11 @@ def _lib():
     L.iqd_channelizer_follow_scanner.argtypes = [vp, u32, u32, C.c_int]
     L.iqd_channelizer_tuning.argtypes = [u32, u64, u64, C.c_int, C.POINTER(u32)]
     L.iqd_accept_wideband_device.argtypes = [vp, vp, u32, vp, sz, vp, vp, vp, vp, vp]
+    L.iqd_channelizer_set_survey.argtypes = [vp, u32, vp, vp]
+    L.iqd_channelizer_survey_device.argtypes = [vp, vp, sz, u32, vp]
+    L.iqd_channelizer_survey.argtypes = [vp, vp, sz, u32, vp]
+    L.iqd_magnitude_dbfs.argtypes = [u32]
+    L.iqd_magnitude_dbfs.restype = C.c_int32
     _LIB = L
     return L
 
@@ -573,9 +579,17 @@ def channelizer_tuning(decimation, source_centre_hz, station_hz, rotation=1):
     return inc.value
 
 
+def magnitude_dbfs(m):
+    """iqd_magnitude_dbfs (host only): the squelch's level of a block magnitude, before any gain is subtracted."""
+    return int(_lib().iqd_magnitude_dbfs(int(m)))
+
+
 def phase_inc(offset_hz, fs):
     """The channelizer's phase increment for a channel at offset_hz from the capture's centre (f = int32(d) / 2^32 fs)."""
     return int(round(float(offset_hz) / float(fs) * 2.0 ** 32)) & 0xffffffff
+
+
+_phase_inc = phase_inc      # (methods below take a `phase_inc` argument of their own)
 
 
 class Channelizer:
@@ -587,6 +601,7 @@ class Channelizer:
         self._h = None
         self.decimation, self.n_channels, self.n_sources = int(decimation), int(n_channels), int(n_sources)
         self.decimation_den = int(decimation_den) or 1
+        self.n_points = 0                                        # survey points (set_survey)
         self._taps = None if taps is None else np.ascontiguousarray(taps, np.int16)
         cfg = ChannelizerConfig(self.n_sources, self.n_channels, self.decimation,
                                 0 if self._taps is None else len(self._taps),
@@ -602,7 +617,7 @@ class Channelizer:
         """Retunes channels [first, first + n): offsets in Hz with the capture's rate fs, or raw increments; a field left
         None keeps its value."""
         if offset_hz is not None:
-            phase_inc = [globals()["phase_inc"](f, fs) for f in np.atleast_1d(offset_hz)]
+            phase_inc = [_phase_inc(f, fs) for f in np.atleast_1d(offset_hz)]
         arrs = [None if v is None else np.atleast_1d(np.asarray(v)) for v in (source, phase_inc, gain_shift)]
         if n is None:
             n = max(len(a) for a in arrs if a is not None)
@@ -623,6 +638,34 @@ class Channelizer:
     def run_device(self, wide_dev, bytes_per_source, out_dev):
         self._e._check(self._L.iqd_channelizer_run_device(self._h, C.c_void_p(wide_dev), int(bytes_per_source),
                                                           C.c_void_p(out_dev)))
+
+    def set_survey(self, offset_hz=None, fs=None, phase_inc=None, gain_shift=None):
+        """The survey's points, measured on every source: offsets in Hz with the capture's rate fs, or raw increments;
+        gain_shift one value or one per point (default 0).  No points (an empty list) clears the survey."""
+        if offset_hz is not None:
+            phase_inc = [_phase_inc(f, fs) for f in np.atleast_1d(offset_hz)]
+        inc = np.atleast_1d(np.asarray([] if phase_inc is None else phase_inc))
+        inc = np.ascontiguousarray(inc.astype(np.uint64) & 0xffffffff, np.uint32)
+        sh = None if gain_shift is None else np.ascontiguousarray(np.broadcast_to(np.atleast_1d(np.asarray(gain_shift)), len(inc)), np.uint8)
+        self._e._check(self._L.iqd_channelizer_set_survey(self._h, len(inc), _np_ptr(inc) if len(inc) else None,
+                                                          _np_ptr(sh) if sh is not None and len(inc) else None))
+        self.n_points = len(inc)
+
+    def survey(self, wide_u8, block_bytes):
+        """[n_sources, bytes_per_source] uint8 -> [n_sources, n_blocks, n_points] uint32: per block of block_bytes row
+        bytes, the magnitude the squelch would see on each survey point.  Advances nothing."""
+        wide = np.ascontiguousarray(wide_u8, dtype=np.uint8).reshape(self.n_sources, -1)
+        block_bytes = int(block_bytes)
+        row = wide.shape[1] // self.decimation * self.decimation_den
+        out = np.zeros((self.n_sources, row // block_bytes if block_bytes > 0 else 0, self.n_points), np.uint32)
+        guard = out if out.size else np.zeros(4, np.uint32)      # (a refused call gets a valid pointer all the same)
+        self._e._check(self._L.iqd_channelizer_survey(self._h, _np_ptr(wide), wide.shape[1], block_bytes & 0xffffffff, _np_ptr(guard)))
+        return out
+
+    def survey_device(self, wide_dev, bytes_per_source, block_bytes, magnitude_dev):
+        """iqd_channelizer_survey_device: device pointers (integers), queued on the engine's stream."""
+        self._e._check(self._L.iqd_channelizer_survey_device(self._h, C.c_void_p(wide_dev), int(bytes_per_source),
+                                                             int(block_bytes), C.c_void_p(magnitude_dev)))
 
     def reset(self):
         self._e._check(self._L.iqd_channelizer_reset(self._h))

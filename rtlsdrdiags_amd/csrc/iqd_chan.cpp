@@ -16,6 +16,7 @@
 #include "iqdemod.h"
 #include "iqd_chan.h"
 #include "iqd_hipres.h"
+#include "iqd_host.h"
 
 using namespace iqd;
 
@@ -85,6 +86,13 @@ struct iqd_channelizer {
     std::vector<uint8_t> amat;                    // [n_tiles][q residues][nq][2][64][16]
     DevBufExact d_amat, d_tiles, d_wgs, d_swgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
     DevBufExact w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
+    // the band survey: points measured on every source, in tiles of 8 of their own (iqd_chan_survey.hip)
+    std::vector<uint32_t> sv_inc;
+    std::vector<uint8_t> sv_shift;
+    std::vector<ChzTile> sv_tiles;                // ch[l]: the point index
+    std::vector<uint8_t> sv_amat;                 // [n_tiles][q residues][nq][2][64][16]
+    bool sv_dirty = false;                        // packed, not uploaded yet
+    DevBufExact d_sv_amat, d_sv_tiles, sv_mag;    // sv_mag: the host form's result
     Staging stg[2];                               // tap uploads
     int stg_cur = 0;
     int cur = 0;
@@ -120,16 +128,22 @@ void chz_channel_taps(const int16_t *h, uint32_t k, uint32_t inc, const int16_t 
 
 }  // namespace iqd
 
-// branch r of the prototype: h_r[k] = h[k q + r], k < ceil((K - r) / q) (q = 1: the prototype itself)
-static void chz_new_taps(iqd_channelizer *z, uint32_t c)
+// complex taps of increment inc on every branch, gr / gi [q][kb]: branch r of the prototype is h_r[k] = h[k q + r],
+// k < ceil((K - r) / q) (q = 1: the prototype itself)
+static void chz_branch_taps(const iqd_channelizer *z, uint32_t inc, int16_t *gr, int16_t *gi)
 {
     std::vector<int16_t> hr(z->kb);
     for (uint32_t r = 0; r < z->q; r++) {
         const uint32_t kr = z->k > r ? (z->k - r + z->q - 1) / z->q : 0;
         for (uint32_t k = 0; k < kr; k++) hr[k] = z->h[(size_t)k * z->q + r];
-        const size_t at = ((size_t)c * z->q + r) * z->kb;
-        chz_channel_taps(hr.data(), kr, z->inc[c], z->phasor.data(), &z->gr[at], &z->gi[at]);
+        chz_channel_taps(hr.data(), kr, inc, z->phasor.data(), gr + (size_t)r * z->kb, gi + (size_t)r * z->kb);
     }
+}
+
+static void chz_new_taps(iqd_channelizer *z, uint32_t c)
+{
+    const size_t at = (size_t)c * z->q * z->kb;
+    chz_branch_taps(z, z->inc[c], &z->gr[at], &z->gi[at]);
     z->ch_dirty[c] = 1;
     z->any_dirty = true;
 }
@@ -179,18 +193,13 @@ static void chz_group(iqd_channelizer *z)
     std::fill(z->ch_dirty.begin(), z->ch_dirty.end(), 1);
 }
 
-// A operands of one tile slot (iqd_chan.h): rows 2 l (Ar) and 2 l + 1 (Ai), both planes, every K-chunk, for every output
-// residue res (its branch: ((res + 1) m - 1) mod q)
-static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
+// A operands of one tile slot (iqd_chan.h) into amat: rows 2 l (Ar) and 2 l + 1 (Ai), both planes, every K-chunk, for
+// every output residue res (its branch: ((res + 1) m - 1) mod q).  gr / gi [q][kb]: the slot's taps, NULL = padding (zeros)
+static void chz_pack_rows(const iqd_channelizer *z, uint8_t *amat, uint32_t tile, uint32_t l, const int16_t *gr, const int16_t *gi)
 {
-    ChzTile &t = z->tiles[tile];
-    const uint32_t c = t.ch[l];
-    t.inc[l] = c == CHZ_NONE ? 0 : z->inc[c];
-    t.shift[l] = c == CHZ_NONE ? 0 : z->shift[c];
-    if (tile >= z->n_fixed_tiles) return;   // a following channel: the walker builds its operands itself, per block
     for (uint32_t res = 0; res < z->q; res++) {
         const uint32_t br = (uint32_t)((((uint64_t)res + 1) * z->m - 1) % z->q);
-        const size_t taps = c == CHZ_NONE ? 0 : ((size_t)c * z->q + br) * z->kb;
+        const size_t taps = (size_t)br * z->kb;
         for (uint32_t row = 0; row < 2; row++) {
             const uint32_t rho = 2 * l + row;
             for (uint32_t q = 0; q < z->nq; q++)
@@ -199,19 +208,30 @@ static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
                         const uint32_t kappa = 64 * q + 16 * g + j, comp = kappa & 1;
                         const uint32_t kk = z->kp - 1 - kappa / 2;
                         int32_t v = 0;
-                        if (c != CHZ_NONE && kk < z->kb) {
-                            const int32_t r = z->gr[taps + kk], i = z->gi[taps + kk];
+                        if (gr && kk < z->kb) {
+                            const int32_t r = gr[taps + kk], i = gi[taps + kk];
                             v = row == 0 ? (comp == 0 ? r : -i) : (comp == 0 ? i : r);
                         }
                         const int8_t lo = (int8_t)(v & 0xff);
                         const int8_t hi = (int8_t)((v - lo) / 256);
                         const size_t lane = rho + 16 * g;
                         for (uint32_t p = 0; p < 2; p++)
-                            z->amat[(((((size_t)tile * z->q + res) * z->nq + q) * 2 + p) * 64 + lane) * 16 + j] =
+                            amat[(((((size_t)tile * z->q + res) * z->nq + q) * 2 + p) * 64 + lane) * 16 + j] =
                                 (uint8_t)(p == 0 ? lo : hi);
                     }
         }
     }
+}
+
+static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
+{
+    ChzTile &t = z->tiles[tile];
+    const uint32_t c = t.ch[l];
+    t.inc[l] = c == CHZ_NONE ? 0 : z->inc[c];
+    t.shift[l] = c == CHZ_NONE ? 0 : z->shift[c];
+    if (tile >= z->n_fixed_tiles) return;   // a following channel: the walker builds its operands itself, per block
+    const size_t taps = c == CHZ_NONE ? 0 : (size_t)c * z->q * z->kb;
+    chz_pack_rows(z, z->amat.data(), tile, l, c == CHZ_NONE ? nullptr : &z->gr[taps], c == CHZ_NONE ? nullptr : &z->gi[taps]);
 }
 
 // Packs the tiles that hold a channel with new parameters and queues their upload on the engine's stream (runs of
@@ -472,6 +492,15 @@ static int chz_check_len(iqd_channelizer *z, size_t bytes_per_source)
     return IQD_OK;
 }
 
+// the most outputs of one window
+static uint32_t chz_t_max(const iqd_channelizer *z)
+{
+    if (z->q > 1)   // windows of whole store groups: 2 (t_max m / q + kp) <= CHZ_FRAC_WIN_MAX
+        return std::min<uint32_t>(1024, (uint32_t)((uint64_t)(CHZ_FRAC_WIN_MAX / 2 - z->kp) * z->q / z->m)) /
+               chz_frac_group(z->q) * chz_frac_group(z->q);
+    return std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - z->kp) / z->m) / CHZ_GROUP * CHZ_GROUP;
+}
+
 // Queues one call: chz_kernel for the fixed channels, the walker for the following ones (scan != NULL), the history.
 static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_source, void *out_dev, ChzScanLaunch *scan)
 {
@@ -481,10 +510,7 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
         if (rc != IQD_OK) return rc;
     }
     const uint32_t n_out = (uint32_t)(bytes_per_source / (2 * z->m) * z->q);   // a multiple of 32 q
-    uint32_t t_max = std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - z->kp) / z->m) / CHZ_GROUP * CHZ_GROUP;
-    if (z->q > 1)   // windows of whole store groups: 2 (t_max m / q + kp) <= CHZ_FRAC_WIN_MAX
-        t_max = std::min<uint32_t>(1024, (uint32_t)((uint64_t)(CHZ_FRAC_WIN_MAX / 2 - z->kp) * z->q / z->m)) /
-                chz_frac_group(z->q) * chz_frac_group(z->q);
+    const uint32_t t_max = chz_t_max(z);
     ChzLaunch a{};
     a.wide = (const uint8_t *)wide_dev;
     a.hist = z->d_hist[z->cur].as<uint8_t>();
@@ -550,6 +576,149 @@ int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_
     CHZ_TRY(z, hipMemcpyAsync(out, z->st_out.p, ob, hipMemcpyDeviceToHost, z->stream));
     CHZ_TRY(z, hipStreamSynchronize(z->stream));
     return IQD_OK;
+}
+
+int iqd_channelizer_set_survey(iqd_channelizer_t *z, uint32_t n_points, const uint32_t *phase_inc, const uint8_t *gain_shift)
+{
+    if (!z) return IQD_EINVAL;
+    if (n_points > 4096) return z->fail(IQD_EINVAL, "channelizer: a survey has at most 4096 points");
+    if (n_points && !phase_inc) return z->fail(IQD_EINVAL, "channelizer: NULL survey increments");
+    for (uint32_t i = 0; gain_shift && i < n_points; i++)
+        if (gain_shift[i] > 8) return z->fail(IQD_EINVAL, "channelizer: gain shift must be 0..8");
+    z->sv_inc.assign(phase_inc, phase_inc + n_points);
+    z->sv_shift.assign(n_points, 0);
+    if (gain_shift) z->sv_shift.assign(gain_shift, gain_shift + n_points);
+    const uint32_t n_tiles = (n_points + CHZ_TILE_CH - 1) / CHZ_TILE_CH;
+    z->sv_tiles.assign(n_tiles, ChzTile{});
+    z->sv_amat.assign((size_t)n_tiles * z->q * z->nq * 2 * 64 * 16, 0);
+    std::vector<int16_t> gr((size_t)z->q * z->kb), gi((size_t)z->q * z->kb);
+    for (uint32_t t = 0; t < n_tiles; t++)
+        for (uint32_t l = 0; l < CHZ_TILE_CH; l++) {
+            const uint32_t p = t * CHZ_TILE_CH + l;
+            ChzTile &T = z->sv_tiles[t];
+            T.ch[l] = p < n_points ? p : CHZ_NONE;
+            T.inc[l] = p < n_points ? z->sv_inc[p] : 0;
+            T.shift[l] = p < n_points ? z->sv_shift[p] : 0;
+            if (p >= n_points) continue;                  // (padding: the zeros of assign)
+            std::fill(gr.begin(), gr.end(), 0);
+            std::fill(gi.begin(), gi.end(), 0);
+            chz_branch_taps(z, T.inc[l], gr.data(), gi.data());
+            chz_pack_rows(z, z->sv_amat.data(), t, l, gr.data(), gi.data());
+        }
+    z->sv_dirty = n_points != 0;
+    return IQD_OK;
+}
+
+// the survey's point tiles to the device, through a staging slot like the channels' taps
+static int chz_survey_upload(iqd_channelizer *z)
+{
+    const size_t ab = z->sv_amat.size(), tb = z->sv_tiles.size() * sizeof(ChzTile);
+    CHZ_TRY(z, z->d_sv_amat.ensure(ab));
+    CHZ_TRY(z, z->d_sv_tiles.ensure(tb));
+    Staging &st = z->stg[z->stg_cur];
+    CHZ_TRY(z, st.ensure(ab + tb));
+    uint8_t *h = st.h;
+    memcpy(h, z->sv_amat.data(), ab);
+    memcpy(h + ab, z->sv_tiles.data(), tb);
+    CHZ_TRY(z, hipMemcpyAsync(z->d_sv_amat.p, h, ab, hipMemcpyHostToDevice, z->stream));
+    CHZ_TRY(z, hipMemcpyAsync(z->d_sv_tiles.p, h + ab, tb, hipMemcpyHostToDevice, z->stream));
+    CHZ_TRY(z, hipEventRecord(st.done, z->stream));
+    st.pending = true;
+    z->stg_cur ^= 1;
+    z->sv_dirty = false;
+    return IQD_OK;
+}
+
+// every refusal of a survey that does not depend on the buffers
+static int chz_survey_check(iqd_channelizer *z, size_t bytes_per_source, uint32_t block_bytes)
+{
+    if (z->sv_inc.empty()) return z->fail(IQD_EINVAL, "channelizer: no survey points set");
+    if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: no survey while a channel follows its scanner");
+    int rc = chz_check_len(z, bytes_per_source);
+    if (rc != IQD_OK) return rc;
+    const uint32_t unit = z->q > 1 ? 256 : 64;
+    if (block_bytes == 0 || block_bytes % unit != 0 || block_bytes > (1u << 24))
+        return z->fail(IQD_EINVAL, z->q > 1 ? "channelizer: a survey's block_bytes must be a multiple of 256, at most 2^24"
+                                            : "channelizer: a survey's block_bytes must be a multiple of 64, at most 2^24");
+    const size_t row = bytes_per_source / z->m * z->q;
+    if (row % block_bytes != 0) return z->fail(IQD_EINVAL, "channelizer: a survey's block_bytes must divide the row length");
+    const uint64_t n_res = (uint64_t)z->n_src * (row / block_bytes) * z->sv_inc.size();
+    const uint32_t n_out = (uint32_t)(row / 2), t_blk = std::min(n_out, chz_t_max(z));
+    const uint64_t n_wgs = (uint64_t)z->n_src * ((n_out + t_blk - 1) / t_blk) * ((z->sv_tiles.size() + CHZ_WAVES - 1) / CHZ_WAVES);
+    if (n_res > 0x3fffffffull || n_wgs > 0x7fffffffull) return z->fail(IQD_EINVAL, "channelizer: survey too large for one call");
+    return IQD_OK;
+}
+
+int iqd_channelizer_survey_device(iqd_channelizer_t *z, const void *wide_dev, size_t bytes_per_source, uint32_t block_bytes,
+                                  void *magnitude_dev)
+{
+    if (!z) return IQD_EINVAL;
+    if (!wide_dev || !magnitude_dev) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
+    if ((((uintptr_t)wide_dev) | ((uintptr_t)magnitude_dev)) & 15) return z->fail(IQD_EINVAL, "channelizer: buffers must be 16-byte aligned");
+    int rc = chz_survey_check(z, bytes_per_source, block_bytes);
+    if (rc != IQD_OK) return rc;
+    (void)hipSetDevice(z->device);
+    if (z->sv_dirty) {
+        rc = chz_survey_upload(z);
+        if (rc != IQD_OK) return rc;
+    }
+    const uint32_t n_out = (uint32_t)(bytes_per_source / (2 * z->m) * z->q);
+    ChzLaunch a{};
+    a.wide = (const uint8_t *)wide_dev;
+    a.hist = z->d_hist[z->cur].as<uint8_t>();     // read only: a survey looks and does not touch
+    a.phasor = z->d_phasor.as<uint32_t>();
+    a.amat = z->d_sv_amat.as<uint4>();
+    a.tiles = z->d_sv_tiles.as<ChzTile>();
+    a.bytes_per_source = bytes_per_source;
+    a.n_sources = z->n_src;
+    a.n_out = n_out;
+    a.m = z->m;
+    a.kp = z->kp;
+    a.nq = z->nq;
+    a.nbase = (uint32_t)(z->m_abs / z->q * z->m);
+    a.den = z->q;
+    a.t_blk = std::min(n_out, chz_t_max(z));
+    ChzSurveyLaunch s{};
+    s.sums = (uint32_t *)magnitude_dev;
+    s.n_points = (uint32_t)z->sv_inc.size();
+    s.n_tiles = (uint32_t)z->sv_tiles.size();
+    s.block_out = block_bytes / 2;
+    s.n_blocks = n_out / s.block_out;
+    s.n_win = (n_out + a.t_blk - 1) / a.t_blk;
+    s.rows = (s.n_tiles + CHZ_WAVES - 1) / CHZ_WAVES;
+    CHZ_TRY(z, hipMemsetAsync(magnitude_dev, 0, (size_t)z->n_src * s.n_blocks * s.n_points * 4, z->stream));
+    CHZ_TRY(z, launch_channelizer_survey(a, s, z->stream));
+    return IQD_OK;
+}
+
+int iqd_channelizer_survey(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_per_source, uint32_t block_bytes, uint32_t *magnitude)
+{
+    if (!z) return IQD_EINVAL;
+    if (!wide || !magnitude) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
+    int rc = chz_survey_check(z, bytes_per_source, block_bytes);
+    if (rc != IQD_OK) return rc;
+    (void)hipSetDevice(z->device);
+    const size_t ib = (size_t)z->n_src * bytes_per_source;
+    const size_t ob = (size_t)z->n_src * (bytes_per_source / z->m * z->q / block_bytes) * z->sv_inc.size() * 4;
+    CHZ_TRY(z, z->st_wide.ensure(ib));
+    CHZ_TRY(z, z->sv_mag.ensure(ob));
+    CHZ_TRY(z, hipMemcpyAsync(z->st_wide.p, wide, ib, hipMemcpyHostToDevice, z->stream));
+    rc = iqd_channelizer_survey_device(z, z->st_wide.p, bytes_per_source, block_bytes, z->sv_mag.p);
+    if (rc != IQD_OK) return rc;
+    CHZ_TRY(z, hipMemcpyAsync(magnitude, z->sv_mag.p, ob, hipMemcpyDeviceToHost, z->stream));
+    CHZ_TRY(z, hipStreamSynchronize(z->stream));
+    return IQD_OK;
+}
+
+// DbfsCalculator's table as the squelch reads it (build_consts' db_table, magnitude_dbfs in iqd_chains.h)
+int32_t iqd_magnitude_dbfs(uint32_t magnitude)
+{
+    static const std::vector<int32_t> table = [] {
+        Consts c;
+        build_consts(c);
+        return std::vector<int32_t>(c.db_table, c.db_table + 128);
+    }();
+    return table[magnitude > 127u ? 127u : magnitude] - 42;
 }
 
 // Checks and queues one wideband accept: the rows into rows_dev, then iqd_accept_iq_device on them.  With following

@@ -80,6 +80,16 @@ struct ChzScanLaunch {
     uint32_t wpt;                          // waves per tile (waves * wpt <= CHZ_WAVES)
 };
 
+// The band survey (chz_survey_kernel, iqd_chan_survey.hip) beside ChzLaunch: a.tiles / a.amat are the survey's point tiles
+// (ChzTile::ch is the point index), shared by all sources; a.wgs and a.out are unused.  Workgroup x of the grid is
+// (source, window, row of CHZ_WAVES point tiles) = (x / (n_win rows), x / rows % n_win, x % rows).
+struct ChzSurveyLaunch {
+    uint32_t *sums;                        // [n_sources][n_blocks][n_points], zero before the launch; the result after it
+    uint32_t n_points, n_tiles;            // n_tiles = ceil(n_points / 8)
+    uint32_t n_blocks, block_out;          // blocks per row, outputs per block (n_blocks block_out = a.n_out)
+    uint32_t n_win, rows;                  // windows of a.t_blk outputs per source; ceil(n_tiles / CHZ_WAVES)
+};
+
 // iqd_channelizer_tuning: the increment of a channel whose station is `station` Hz (centre station + 64000 r) cut from a
 // source centred on `centre` Hz at Fs = 256000 M; false when out of band.  Host and device share this one statement.
 __host__ __device__ inline bool chz_tuning(uint32_t m, unsigned long long centre, unsigned long long station, int32_t r,
@@ -100,6 +110,8 @@ hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_fixed_wgs, const Ch
                               const ChzScanLaunch *scan, hipStream_t st);
 // chz_frac_kernel alone, for a.den = 2, 4, 8 (iqd_chan_frac.hip); launch_channelizer adds the history kernel
 hipError_t launch_channelizer_frac(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s);
+// chz_survey_kernel for a.den = 1, 2, 4, 8 and the kernel that divides the sums (iqd_chan_survey.hip)
+hipError_t launch_channelizer_survey(const ChzLaunch &a, const ChzSurveyLaunch &s, hipStream_t st);
 
 // host-only spec pieces (iqd_chan.cpp)
 void chz_phasor_table(int16_t *out /* [8192] (c, s) pairs */);

@@ -1,5 +1,6 @@
-// Device pieces of the wideband channelizer shared by chz_kernel / chz_scan_kernel (iqd_chan.hip) and the fractional-rate
-// chz_frac_kernel (iqd_chan_frac.hip): the B operand read, the epilogue of one output, the window staging.
+// Device pieces of the wideband channelizer shared by chz_kernel / chz_scan_kernel (iqd_chan.hip), the fractional-rate
+// chz_frac_kernel (iqd_chan_frac.hip) and chz_survey_kernel (iqd_chan_survey.hip): the B operand read, the epilogue of one
+// output, the window staging.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -7,6 +7,7 @@
 //   iqdemod_wide in=cap.iq [decimation=8] rate=2048000 offsets=<Hz>[,<Hz>...] modes=<m>[,<m>...] [gains=<L>[,<L>...]]
 //                out=pcm_%d.s16 [blocks=K] [rotation=<r>] [centre=<Hz>] [scan=<start>,<end>,<step>[,...]]
 //                [squelch=<dBFS>[,<dBFS>...]] [freqlog=<file>]
+//                [survey=<first_offset_Hz>,<step_Hz>,<count> [surveyshift=<L>] surveylog=<file>]
 //
 //   decimation M, or P/Q with Q = 2, 4 or 8 (rate = 256000 P / Q); left out, it is rate / 256000 in lowest terms
 //   offsets    the channel's frequency minus the capture's centre, Hz (|offset| < rate / 2)
@@ -24,6 +25,13 @@
 //   squelch    per channel the squelch threshold, dBFS, the list repeating (default: the engine's)
 //   freqlog    one line per block and channel: block (from 0, over the whole capture), channel, the station frequency
 //              the block was cut at (a fixed channel: centre + offset - 64000 rotation), 1 if the squelch let it through
+//   survey     a grid of count offsets first, first + step, ... (the increments as for offsets; count <= 4096): every
+//              accept is surveyed before it is run (iqd_channelizer_survey, one block per 32768-byte engine block, the
+//              short block at the capture's end as one block - left out, with a notice, where its length is no admissible
+//              survey block).  surveylog gets one line per block and point: block (from 0, over the whole capture), the
+//              point's offset in Hz, the block magnitude, its level in dBFS (iqd_magnitude_dbfs; no gain applied).
+//              surveyshift: the gain shift L of every point (default 0).  With survey=, offsets= (and modes=, out=) may
+//              be left out: then nothing is demodulated and no PCM files are written.  Not together with scan=.
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
 #include <math.h>
 #include <stdint.h>
@@ -66,7 +74,7 @@ std::vector<uint64_t> u64List(const char *s)
 
 int main(int argc, char **argv)
 {
-  std::string in, out, freqlog;
+  std::string in, out, freqlog, surveylog;
   uint32_t m = 0, den = 1, blocks = 4;
   bool m_given = false;
   double rate = 0;
@@ -74,6 +82,8 @@ int main(int argc, char **argv)
   uint64_t centre = 0;
   std::vector<double> offsets, modes, gains{0}, squelch;
   std::vector<uint64_t> scan;
+  std::vector<double> survey;
+  uint32_t surveyshift = 0;
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
     if (!strncmp(a, "in=", 3)) in = a + 3;
@@ -94,6 +104,9 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "scan=", 5)) scan = u64List(a + 5);
     else if (!strncmp(a, "squelch=", 8)) squelch = numList(a + 8);
     else if (!strncmp(a, "freqlog=", 8)) freqlog = a + 8;
+    else if (!strncmp(a, "survey=", 7)) survey = numList(a + 7);
+    else if (!strncmp(a, "surveyshift=", 12)) surveyshift = (uint32_t)atoi(a + 12);
+    else if (!strncmp(a, "surveylog=", 10)) surveylog = a + 10;
     else {
       fprintf(stderr, "iqdemod_wide: unknown argument %s\n", a);
       return 1;
@@ -112,14 +125,32 @@ int main(int argc, char **argv)
       den /= 2;
     }
   }
-  if (in.empty() || out.empty() || m < 2 || den < 1 || rate <= 0 || offsets.empty() || modes.empty() || gains.empty() || !blocks ||
-      scan.size() % 3 != 0) {
-    fprintf(stderr, "usage: iqdemod_wide in=cap.iq [decimation=8|75/8] rate=2048000 offsets=<Hz,...> modes=<m,...> "
-                    "[gains=<L,...>] out=pcm_%%d.s16 [blocks=K] [rotation=r] [centre=Hz] [scan=start,end,step,...] "
-                    "[squelch=dBFS,...] [freqlog=file]\n");
+  const bool surveying = !survey.empty();
+  const bool survey_ok = !surveying || (survey.size() == 3 && survey[2] >= 1 && survey[2] <= 4096 && surveyshift <= 8 && !surveylog.empty());
+  const bool demod_ok = !offsets.empty() ? !out.empty() && !modes.empty() : surveying;
+  if (surveying && !scan.empty()) {   // (iqd_channelizer_survey refuses while a channel follows its scanner)
+    fprintf(stderr, "iqdemod_wide: survey= cannot be combined with scan=: a survey is refused while a channel follows its scanner\n");
     return 1;
   }
-  const uint32_t n = (uint32_t)offsets.size();
+  if (in.empty() || !demod_ok || !survey_ok || m < 2 || den < 1 || rate <= 0 || gains.empty() || !blocks || scan.size() % 3 != 0) {
+    fprintf(stderr, "usage: iqdemod_wide in=cap.iq [decimation=8|75/8] rate=2048000 offsets=<Hz,...> modes=<m,...> "
+                    "[gains=<L,...>] out=pcm_%%d.s16 [blocks=K] [rotation=r] [centre=Hz] [scan=start,end,step,...] "
+                    "[squelch=dBFS,...] [freqlog=file] [survey=first_Hz,step_Hz,count [surveyshift=L] surveylog=file]\n");
+    return 1;
+  }
+  const uint32_t n = (uint32_t)offsets.size();   // 0: survey only
+  const uint32_t n_pts = surveying ? (uint32_t)survey[2] : 0;
+  std::vector<uint32_t> sv_inc(n_pts);
+  std::vector<uint8_t> sv_shift(n_pts, (uint8_t)surveyshift);
+  std::vector<double> sv_off(n_pts);
+  for (uint32_t p = 0; p < n_pts; p++) {
+    sv_off[p] = survey[0] + p * survey[1];
+    if (fabs(sv_off[p]) >= rate / 2) {
+      fprintf(stderr, "iqdemod_wide: survey offset %.0f Hz outside +-rate/2\n", sv_off[p]);
+      return 1;
+    }
+    sv_inc[p] = (uint32_t)(int32_t)llround(sv_off[p] / rate * 4294967296.0);
+  }
   std::vector<uint32_t> source(n, 0), inc(n);
   std::vector<uint8_t> shift(n);
   for (uint32_t c = 0; c < n; c++) {
@@ -147,6 +178,11 @@ int main(int argc, char **argv)
       return 1;
     }
   }
+  FILE *slog = nullptr;
+  if (surveying && !(slog = fopen(surveylog.c_str(), "w"))) {
+    fprintf(stderr, "iqdemod_wide: cannot create %s\n", surveylog.c_str());
+    return 1;
+  }
   FILE *flog = nullptr;
   if (!freqlog.empty() && !(flog = fopen(freqlog.c_str(), "w"))) {
     fprintf(stderr, "iqdemod_wide: cannot create %s\n", freqlog.c_str());
@@ -155,7 +191,7 @@ int main(int argc, char **argv)
 
   iqd_config cfg{};
   cfg.abi_version = IQD_ABI_VERSION;
-  cfg.n_channels = n;
+  cfg.n_channels = n ? n : 1;
   cfg.device = -1;
   iqd_t *e = nullptr;
   int rc = iqd_create(&cfg, &e);
@@ -165,14 +201,15 @@ int main(int argc, char **argv)
   }
   iqd_channelizer_config zc{};
   zc.n_sources = 1;
-  zc.n_channels = n;
+  zc.n_channels = n ? n : 1;   // (survey only: one channel at offset 0 carries the stream's history along)
   zc.decimation = m;
   zc.decimation_den = den;
   iqd_channelizer_t *z = nullptr;
   rc = iqd_channelizer_create(e, &zc, &z);
-  if (rc == IQD_OK) rc = iqd_channelizer_set_channels(z, 0, n, source.data(), inc.data(), shift.data());
+  if (rc == IQD_OK && n) rc = iqd_channelizer_set_channels(z, 0, n, source.data(), inc.data(), shift.data());
+  if (rc == IQD_OK && surveying) rc = iqd_channelizer_set_survey(z, n_pts, sv_inc.data(), sv_shift.data());
   for (uint32_t c = 0; c < n && rc == IQD_OK; c++) rc = iqd_set_mode(e, c, 1, (int)modes[c % modes.size()]);
-  if (rc == IQD_OK) rc = iqd_set_rotation(e, 0, n, rotation);
+  if (rc == IQD_OK && n) rc = iqd_set_rotation(e, 0, n, rotation);
   for (uint32_t c = 0; c < n && rc == IQD_OK && !squelch.empty(); c++)
     rc = iqd_set_squelch(e, c, 1, (int32_t)squelch[c % squelch.size()]);
   // scanning channels: their scanners and the channelizer's following flags
@@ -202,6 +239,8 @@ int main(int argc, char **argv)
   const size_t block = 32768 / den * (size_t)m, call = blocks * block, unit = 64 * (size_t)m;
   std::vector<uint8_t> wide(call);
   std::vector<int16_t> pcm((size_t)n * call / m * den / 64);
+  std::vector<uint32_t> sv_mag((size_t)blocks * n_pts);
+  std::vector<uint8_t> sv_rows(n ? 0 : call / m * den);
   std::vector<uint32_t> count(n);
   std::vector<uint8_t> open((size_t)n * blocks);
   uint64_t block_no = 0;
@@ -209,7 +248,34 @@ int main(int argc, char **argv)
   // one accept of `bytes` (whole engine blocks, or ONE short block: include/iqdemod.h), its PCM and its log lines out
   auto feed = [&](const uint8_t *p, size_t bytes) {
     const size_t nblk = bytes % block == 0 ? bytes / block : 1;
-    int r = iqd_accept_wideband(e, z, 0, p, bytes, pcm.data(), count.data(), nullptr, flog ? open.data() : nullptr);
+    int r = IQD_OK;
+    if (surveying) {   // before the run: a survey reads the state the accept starts from
+      const size_t bb = bytes / m * den / nblk;   // row bytes per block
+      if (bb % (den > 1 ? 256 : 64) != 0) {
+        fprintf(stderr, "iqdemod_wide: the short block of %zu row bytes is not surveyed\n", bb);
+      } else {
+        r = iqd_channelizer_survey(z, p, bytes, (uint32_t)bb, sv_mag.data());
+        for (size_t b = 0; r == IQD_OK && b < nblk; b++)
+          for (uint32_t q = 0; q < n_pts; q++) {
+            const uint32_t mg = sv_mag[b * n_pts + q];
+            fprintf(slog, "%llu %lld %u %d\n", (unsigned long long)(block_no + b), (long long)llround(sv_off[q]), mg,
+                    (int)iqd_magnitude_dbfs(mg));
+          }
+      }
+    }
+    // survey only: nothing is demodulated, but the stream moves on - the one channel at offset 0 is run (its row comes
+    // back to the host and is dropped: 1 / M of the capture's bytes, the price of advancing the history over the C ABI)
+    if (r == IQD_OK && !n) {
+      r = iqd_channelizer_run(z, p, bytes, sv_rows.data());
+      if (r != IQD_OK) {
+        fprintf(stderr, "iqdemod_wide: survey: %s (%s)\n", iqd_strerror(r), iqd_last_error(e));
+        status = 3;
+        return false;
+      }
+      block_no += nblk;
+      return true;
+    }
+    if (r == IQD_OK) r = iqd_accept_wideband(e, z, 0, p, bytes, pcm.data(), count.data(), nullptr, flog ? open.data() : nullptr);
     if (r == IQD_OK && flog) {
       trace.resize((size_t)n * nblk);
       r = iqd_get_frequency_trace(e, 0, n, trace.data(), nblk);
@@ -246,6 +312,7 @@ int main(int argc, char **argv)
   }
   fclose(f);
   if (flog) fclose(flog);
+  if (slog) fclose(slog);
   for (FILE *s : sinks) fclose(s);
   iqd_channelizer_destroy(z);
   iqd_destroy(e);

@@ -5,6 +5,7 @@ per channel and call, M = 8, default taps.  Prints one JSON line:
     python tools/chan_bench.py [--steps K] [--settle-ms 100]
     python tools/chan_bench.py --decimation 75 --den 8   (a fractional channelizer: a 2.4 MS/s capture, same outputs)
     python tools/chan_bench.py --scan [--steps K]      (scanner-driven channels, written to profiles/ as well)
+    python tools/chan_bench.py --survey [--decimation 75 --den 8]   (the band survey against rows of real channels)
 
   chan_ms            per call, host clock around iqd_channelizer_run_device + synchronize (median of K steps, after
                      about --settle-ms of the same call untimed, like bench.py's clock settle)
@@ -18,7 +19,13 @@ the channels fixed (chz_kernel); rows_accept_ms: the accept on the rows alone, a
 rows_accept_ms, an estimate of the walker's share (the two are timed in separate loops).  The walker kernel's own time
 comes from a kernel trace of this run: rocprofv3 --kernel-trace (profiles/chan_scan_kernel_trace.json).  The same for 16
 following channels (one source), and host_loop_ms: today's host-driven loop for those 16 - one-block calls of
-iqd_channelizer_run + iqd_accept_iq with iqd_scanner_get + iqd_channelizer_tuning before each block."""
+iqd_channelizer_run + iqd_accept_iq with iqd_scanner_get + iqd_channelizer_tuning before each block.
+
+--survey: 16 sources, 2^16 outputs each, a 12.5 kHz grid of 163 points per source (2608 virtual channels), block_bytes
+32768.  survey_ms: iqd_channelizer_survey_device + synchronize; grid_run_ms: iqd_channelizer_run_device for 2608 real
+channels on the same grid - the cheapest other way to the same bytes, before any accept.  The two alternate three times in
+the one process; the medians of each round are listed, and survey_over_grid_run is the ratio of their medians
+(profiles/chan_survey_bench.json keeps one session's lines beside the parent build's: DESIGN 4.10.3)."""
 import argparse
 import json
 import os
@@ -51,12 +58,16 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=100.0)
     ap.add_argument("--chan-only", action="store_true", help="only the channelizer calls (counter runs)")
     ap.add_argument("--scan", action="store_true", help="scanner-driven channels (see above)")
+    ap.add_argument("--survey", action="store_true", help="the band survey against run_device on the same grid (see above)")
+    ap.add_argument("--grid-only", action="store_true", help="with --survey: only grid_run_ms (a build without the survey)")
     ap.add_argument("--decimation", type=int, default=8, help="M, or P of a fractional decimation P / Q")
     ap.add_argument("--den", type=int, default=1, help="Q of a fractional decimation (1, 2, 4, 8)")
     args = ap.parse_args()
     from rtlsdrdiags_amd import capi
     if args.scan:
         return scan_bench(capi, args)
+    if args.survey:
+        return survey_bench(capi, args)
 
     M, Q, n_src, n_ch, n_out = args.decimation, args.den, 16, 4096, 1 << 16
     bps = n_out * 2 * M // Q
@@ -94,6 +105,40 @@ def main():
                 hbm_share=round(hbm / 8e12 * 1e3 / chan_ms, 3), mfma_share=round(ops / 5e15 * 1e3 / chan_ms, 3))
     print(json.dumps(line))
     z.close()
+    eng.close()
+
+
+def survey_bench(capi, args):
+    from rtlsdrdiags_amd import synth
+    M, Q, n_src, n_out, n_pts, bb = args.decimation, args.den, 16, 1 << 16, 163, 32768
+    fs = 256000.0 * M / Q
+    bps, row = n_out * 2 * M // Q, 2 * n_out
+    offs = [12500.0 * (p - n_pts // 2) for p in range(n_pts)]
+    eng = capi.Engine(1)
+    d_in = eng.dev_alloc(n_src * bps)
+    eng.dev_upload(d_in, np.concatenate([synth.white_u8(bps // 2, seed=s) for s in range(n_src)]))
+    zg = capi.Channelizer(eng, M, n_src * n_pts, n_src, decimation_den=Q)
+    zg.set_channels(0, source=np.repeat(np.arange(n_src), n_pts), offset_hz=offs * n_src, fs=fs,
+                    gain_shift=np.full(n_src * n_pts, 3))
+    d_out = eng.dev_alloc(n_src * n_pts * row)
+    grid = lambda: zg.run_device(d_in, bps, d_out)
+    survey = None
+    if not args.grid_only:
+        zs = capi.Channelizer(eng, M, 1, n_src, decimation_den=Q)
+        zs.set_survey(offset_hz=offs, fs=fs, gain_shift=3)
+        d_mag = eng.dev_alloc(n_src * (row // bb) * n_pts * 4)
+        survey = lambda: zs.survey_device(d_in, bps, bb, d_mag)
+    g, s = [], []
+    for _ in range(3):
+        g.append(round(timed(grid, eng.synchronize, args.steps, args.settle_ms)[0], 4))
+        if survey:
+            s.append(round(timed(survey, eng.synchronize, args.steps, args.settle_ms)[0], 4))
+    line = {"workload": "band survey, 16 sources / 2^16 outputs / %d points on a 12.5 kHz grid / M=%s / block_bytes %d"
+                        % (n_pts, M if Q == 1 else "%d/%d" % (M, Q), bb),
+            "grid_run_ms": g, "grid_run_rows_bytes": n_src * n_pts * row}
+    if survey:
+        line.update(survey_ms=s, survey_over_grid_run=round(float(np.median(s)) / float(np.median(g)), 4))
+    print(json.dumps(line))
     eng.close()
 
 

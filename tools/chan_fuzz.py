@@ -10,6 +10,10 @@ first draw of the case, so that a kept generator state replays the same kind).  
 generator state of that case in fuzz_out/chan_fuzz_fail_state.json (FUZZ_STATE=<path>: there) and exits non-zero;
 FUZZ_REPLAY=<that file> python tools/chan_fuzz.py  runs that one case again.
 
+About one case in ten is a survey case (FUZZ_SURVEY=1: every case, FUZZ_SURVEY=0: none): a plain or a fractional case with
+a band survey (iqd_channelizer_survey*, against tests/chan_survey_model.py) drawn before some of its calls, each followed by
+the call itself, so that a survey that moved the channelizer's state shows in the rows.
+
 A plain case is drawn without a GPU (draw_plain) and then run (run_plain), so that a CPU test can hold the fixed slices
 of tests/test_gpu_chan_fuzz.py to the mutants of tests/chan_mutants.py before they go to the GPU (first_channel_kills)."""
 import json
@@ -24,11 +28,13 @@ from tests import chan_frac_model as fm                # noqa: E402
 from tests import chan_model as cm                     # noqa: E402
 from tests import chan_mutants as mu                   # noqa: E402
 from tests import chan_scan_model as sm                # noqa: E402
+from tests import chan_survey_model as svm             # noqa: E402
 
 K_EDGES = (1, 31, 32, 33, 255, 256, 257, 1023, 1024)
 INC_EDGES = (0, 1, 2 ** 31, 2 ** 31 - 1, 2 ** 32 - 1)
 BOUND_SUM = (2 ** 31 - 256) // 256
-SLICES = {"plain": ((9101, 150), (9102, 150)), "scan": (9103, 40)}   # (seed, cases): tests/test_gpu_chan_fuzz.py's
+SLICES = {"plain": ((9101, 150), (9102, 150)), "scan": (9103, 40),   # (seed, cases): tests/test_gpu_chan_fuzz.py's
+          "survey": (9104, 40)}                                       # tests/test_gpu_chan_survey_fuzz.py's
 MODEL_BUDGET = 4e7        # tap x wideband-sample products the model may spend per case (chan_model convolves at the
 #                           wide rate: K M outputs per channel); fewer channels are compared when a case is past it
 
@@ -208,8 +214,9 @@ class Context:
         self.eng.close()
 
 
-def run_plain(cfg, ctx):
-    """Runs the case's script through iqd_channelizer_run / run_device; None, or what differed."""
+def run_plain(cfg, ctx, before_call=None):
+    """Runs the case's script through iqd_channelizer_run / run_device; None, or what differed.  before_call(z, i, device,
+    piece, epoch, m0, n_out): a step before call i (a survey case's), returning None or what differed."""
     eng, P, M = ctx.eng, ctx.P, cfg["M"]
     z = capi.Channelizer(eng, M, cfg["n_ch"], n_sources=cfg["n_src"], taps=cfg["taps"])
     z.set_channels(0, source=cfg["src"], phase_inc=cfg["inc"], gain_shift=cfg["shift"])
@@ -223,6 +230,10 @@ def run_plain(cfg, ctx):
             elif op[0] == "reset":
                 z.reset()
         piece = np.ascontiguousarray(epoch[:, 2 * M * m0:])
+        if before_call:
+            bad = before_call(z, i, device, piece, epoch, m0, n_out)
+            if bad:
+                break
         if device:
             d_in, d_out = eng.dev_alloc(piece.nbytes), eng.dev_alloc(cfg["n_ch"] * 2 * n_out)
             eng.dev_upload(d_in, piece)
@@ -319,8 +330,9 @@ def draw_frac(rng):
             "device_form": bool(rng.random() < 0.5)}
 
 
-def run_frac(cfg, ctx):
-    """Runs a fractional case's script through iqd_channelizer_run / run_device; None, or what differed."""
+def run_frac(cfg, ctx, before_call=None):
+    """Runs a fractional case's script through iqd_channelizer_run / run_device; None, or what differed (before_call: as
+    in run_plain)."""
     eng, Pt, P, Q = ctx.eng, ctx.P, cfg["M"], cfg["Q"]
     z = capi.Channelizer(eng, P, cfg["n_ch"], n_sources=cfg["n_src"], taps=cfg["taps"], decimation_den=Q)
     z.set_channels(0, source=cfg["src"], phase_inc=cfg["inc"], gain_shift=cfg["shift"])
@@ -336,6 +348,10 @@ def run_frac(cfg, ctx):
             elif op[0] == "reset":
                 z.reset()
         piece = np.ascontiguousarray(epoch[:, 2 * P * t0:])
+        if before_call:
+            bad = before_call(z, i, device, piece, epoch, m0, n_out)
+            if bad:
+                break
         if device:
             d_in, d_out = eng.dev_alloc(piece.nbytes), eng.dev_alloc(cfg["n_ch"] * 2 * n_out)
             eng.dev_upload(d_in, piece)
@@ -366,6 +382,67 @@ def frac_case(rng, ctx):
     cfg = draw_frac(rng)
     bad = run_frac(cfg, ctx)
     return None if bad is None else "fractional case (decimation %d/%d): %s\n  %s" % (cfg["M"], cfg["Q"], describe(cfg), bad)
+
+
+# ---------------------------------------------------------------------------------------------------- survey cases
+def survey_case(rng, ctx):
+    """A plain or a fractional case (drawn as ever) with survey steps between its calls: the points are set before the
+    first call - now and then again, or cleared and set again, later - and before about two calls in three the call's
+    bytes are surveyed first, in the form the call takes, at a block size drawn from the admissible ones."""
+    frac = rng.random() < 0.35
+    cfg = draw_frac(rng) if frac else draw_plain(rng)
+    M, Q, h, n_src = cfg["M"], cfg.get("Q", 1), cfg["h"], cfg["n_src"]
+    units = sum(c["units"] for c in cfg["calls"])
+    work = 4.0 * -(-len(h) // Q) * (M if Q == 1 else Q) * units * 32 * n_src      # the model's cost per point
+    n_pts = int(min(int(rng.choice([1, 7, 8, 9, 17, 65])), max(1, MODEL_BUDGET // work)))
+    draw_pts = lambda: ([draw_inc(rng) for _ in range(n_pts)], [int(v) for v in rng.integers(0, 9, n_pts)])   # noqa: E731
+    pts = [draw_pts()]
+    steps = []
+    for i, call in enumerate(cfg["calls"]):
+        n_out = call["units"] * 32 * Q
+        step = 128 if Q > 1 else 32
+        sizes = [b for b in range(step, n_out + 1, step) if n_out % b == 0]
+        new = i > 0 and rng.random() < 0.2
+        if new:
+            pts.append(draw_pts())
+        steps.append({"points": len(pts) - 1 if new or i == 0 else None, "clear_first": bool(new and rng.random() < 0.5),
+                      "block_out": int(rng.choice(sizes)) if sizes and rng.random() < 0.67 else 0})
+    state = {}
+    win = frac_t_max(M, Q, -(-len(h) // Q)) if Q > 1 else t_max(M, len(h))
+
+    def before_call(z, i, device, piece, epoch, m0, n_out):
+        st = steps[i]
+        if st["points"] is not None:
+            if st["clear_first"]:
+                z.set_survey(phase_inc=[])
+            state["inc"], state["shift"] = pts[st["points"]]
+            z.set_survey(phase_inc=state["inc"], gain_shift=state["shift"])
+        if not st["block_out"]:
+            return None
+        bo = st["block_out"]
+        want = svm.survey(epoch, h, M, Q, state["inc"], state["shift"], ctx.P, bo, m0, n_out, win, ctx.oracle)
+        if device:
+            d_in, d_mag = ctx.eng.dev_alloc(piece.nbytes), ctx.eng.dev_alloc(want.nbytes)
+            ctx.eng.dev_upload(d_in, piece)
+            z.survey_device(d_in, piece.shape[1], 2 * bo, d_mag)
+            ctx.eng.synchronize()
+            got = ctx.eng.dev_download(d_mag, want.nbytes, np.uint32).reshape(want.shape)
+            ctx.eng.dev_free(d_in)
+            ctx.eng.dev_free(d_mag)
+        else:
+            got = z.survey(piece, 2 * bo)
+        ctx.count("surveys")
+        ctx.count("survey blocks", want.shape[1])
+        if np.array_equal(got, want):
+            return None
+        d = np.argwhere(got != want)
+        return ("survey before call %d (%s form, %d outputs from output %d of the epoch, blocks of %d outputs, %d points): %d "
+                "entries differ, first (source, block, point) %s: got %d, model %d; inc %r shift %r" % (
+                    i, "device" if device else "host", n_out, m0, bo, n_pts, len(d), d[0].tolist(), got[tuple(d[0])],
+                    want[tuple(d[0])], state["inc"][:16], state["shift"][:16]))
+
+    bad = (run_frac if frac else run_plain)(cfg, ctx, before_call)
+    return None if bad is None else "survey case (decimation %d/%d; survey steps %r): %s\n  %s" % (M, Q, steps, describe(cfg), bad)
 
 
 # ------------------------------------------------------------------------------------------------------ scan cases
@@ -589,13 +666,15 @@ def main():
     rng = np.random.default_rng(seed)
     from oracle import bindings
     ctx = Context(bindings.Oracle())
-    mode, fmode = os.environ.get("FUZZ_SCAN"), os.environ.get("FUZZ_FRAC")
+    mode, fmode, smode = os.environ.get("FUZZ_SCAN"), os.environ.get("FUZZ_FRAC"), os.environ.get("FUZZ_SURVEY")
 
     def one():
         r = rng.random() if mode is None else 1.0
         scan = mode == "1" or (mode is None and r < 0.125)
         if scan:
             return scan, scan_case(rng, ctx)
+        if smode == "1" or (smode is None and mode is None and r >= 0.9):
+            return scan, survey_case(rng, ctx)
         frac = fmode == "1" or (fmode is None and r < 0.27)     # (FUZZ_SCAN=0 alone: plain cases only, as ever)
         return scan, (frac_case(rng, ctx) if frac else plain_case(rng, ctx))
 
