@@ -296,7 +296,7 @@ size_t iqd_resampler_out_count(const iqd_resampler_t *r, size_t n_in);
 int iqd_resampler_run(iqd_resampler_t *r, const void *in, size_t n_in, void *out);                 /* host pointers */
 int iqd_resampler_run_device(iqd_resampler_t *r, const void *in_dev, size_t n_in, void *out_dev);  /* queued on the engine's stream */
 
-/* Wideband channelizer: many engine channels cut out of one uint8 capture at M x 256 kS/s (an RTL-SDR at 2.048 MS/s is
+/* Wideband channelizer: many engine channels cut out of one capture (uint8 here; int8 and int16: "Signed captures" below) at M x 256 kS/s (an RTL-SDR at 2.048 MS/s is
  * M = 8).  The reference gets its one channel from the RTL2832U's own down-converter (Radio tunes the dongle, the chip
  * delivers 256 kS/s around that frequency); this is the same front for any number of channels of one receiver.  Every
  * step after the phasor table is integer and fixed here, so results are exact, not within a tolerance:
@@ -336,7 +336,8 @@ typedef struct iqd_channelizer_config {
     uint32_t n_taps;        /* K, 1..1024 (1..1024 Q); ignored when taps == NULL */
     const int16_t *taps;    /* h[0..K), Q15; NULL -> iqd_channelizer_default_taps(M) */
     uint32_t decimation_den; /* Q: 0 or 1 (integer decimation), 2, 4, 8 (fractional, below) */
-    uint32_t reserved[3];   /* 0 */
+    uint32_t sample_format; /* IQD_WIDE_U8 (0, the above), IQD_WIDE_S8, IQD_WIDE_S16 ("Signed captures" below) */
+    uint32_t reserved[2];   /* 0 */
 } iqd_channelizer_config;
 typedef struct iqd_channelizer iqd_channelizer_t;
 int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_channelizer_t **out);
@@ -379,6 +380,35 @@ int iqd_channelizer_default_taps(uint32_t decimation, int16_t *out, uint32_t cap
  *   scanner   channels of a fractional channelizer cannot follow a scanner: iqd_channelizer_follow_scanner(z, ..., 1)
  *             returns IQD_EINVAL.  iqd_channelizer_tuning is for integer M only. */
 int iqd_channelizer_default_taps_q(uint32_t decimation, uint32_t den, int16_t *out, uint32_t capacity);
+
+/* Signed captures: iqd_channelizer_config.sample_format says what a source's bytes are.  IQD_WIDE_U8 (0) is the RTL-SDR's
+ * offset binary, everything above bit for bit.  IQD_WIDE_S8 is signed int8 (HackRF), IQD_WIDE_S16 little-endian signed
+ * int16 (SDRplay, Airspy, USRP, the baseband recordings of SDR++, SDR# and SDRangel); any other value is IQD_EINVAL.  B is
+ * the bytes per rail, 1 or 2.  Everything not named here is the integer channelizer's spec above:
+ *
+ *   sources   a source's bytes are interleaved I, Q of the format (int16: little-endian); x[n] = I + j Q with the values
+ *             as they are: S8 I, Q in [-128, 127] (the capture u8 ^ 0x80 is the same signal as u8), S16 in [-32768, 32767].
+ *             x[n < 0] = 0.  wide / wide_dev point at these bytes whatever the parameter's C type; wide_dev is 16-byte
+ *             aligned as before.
+ *   output m  taps g[k], n = m M + M - 1 and A = sum_k g[k] x[n - k] as above, A exact in unbounded integers (the S16 sum
+ *             passes int32).  Stage a by format:
+ *               S8   a = sat16((A + 128) >> 8), as U8
+ *               S16  a = sat16((A + 2^15) >> 16) on each rail
+ *             then the rotation, y and the byte as above.  So an S16 capture x16 = 256 x8 gives exactly the bytes of the
+ *             8-bit capture x8: (256 A + 2^15) >> 16 = (A + 128) >> 8.  The tap conditions are unchanged.
+ *   length    bytes_per_source: a multiple of 64 M B (32 M samples, 32 outputs).  out and the rows of
+ *             iqd_accept_wideband* are [n_channels][bytes_per_source / (M B)]; the engine's block_bytes rule applies to
+ *             that row length.
+ *   works     fixed channels at integer M: iqd_channelizer_run / _run_device, iqd_accept_wideband / _device,
+ *             set_channels between calls (retuning, moving), reset.
+ *   not yet   each IQD_EINVAL before anything is queued, the message naming the format: decimation_den > 1 together with
+ *             sample_format != 0 (at create); iqd_channelizer_follow_scanner(z, ..., 1); iqd_channelizer_set_survey with
+ *             n_points > 0.
+ * iqd_channelizer_window_outputs (host only, no GPU): the most outputs of one channel the kernel stages per workgroup
+ * window, t with 2 B' (t M + Kp) <= 32768 bytes of LDS - Kp = K rounded up to 32, B' the byte planes of a sample rail
+ * (U8, S8: 1; S16: 2) - cut to a multiple of 64 and to 1024 at most; 0 for arguments out of range. */
+enum { IQD_WIDE_U8 = 0, IQD_WIDE_S8 = 1, IQD_WIDE_S16 = 2 };
+uint32_t iqd_channelizer_window_outputs(uint32_t decimation, uint32_t n_taps, uint32_t sample_format);
 
 /* Scanner-driven channels: a channelizer channel c may FOLLOW THE SCANNER of the engine channel it feeds in
  * iqd_accept_wideband*(e, z, first_ch, ...), e_c = first_ch + c.  A following channel's row of one call is split into the

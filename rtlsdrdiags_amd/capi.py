@@ -44,7 +44,7 @@ class AgcState(C.Structure):
 class ChannelizerConfig(C.Structure):
     _fields_ = [("n_sources", C.c_uint32), ("n_channels", C.c_uint32), ("decimation", C.c_uint32),
                 ("n_taps", C.c_uint32), ("taps", C.c_void_p), ("decimation_den", C.c_uint32),
-                ("reserved", C.c_uint32 * 3)]
+                ("sample_format", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class IqdError(RuntimeError):
@@ -71,6 +71,7 @@ EXPORTS = [
     "iqd_channelizer_default_taps", "iqd_channelizer_set_source_frequency", "iqd_channelizer_follow_scanner",
     "iqd_channelizer_tuning", "iqd_accept_wideband_device", "iqd_channelizer_default_taps_q",
     "iqd_channelizer_set_survey", "iqd_channelizer_survey_device", "iqd_channelizer_survey", "iqd_magnitude_dbfs",
+    "iqd_channelizer_window_outputs",
 ]
 
 _LIB = None
@@ -162,6 +163,8 @@ def _lib():
     L.iqd_channelizer_set_survey.argtypes = [vp, u32, vp, vp]
     L.iqd_channelizer_survey_device.argtypes = [vp, vp, sz, u32, vp]
     L.iqd_channelizer_survey.argtypes = [vp, vp, sz, u32, vp]
+    L.iqd_channelizer_window_outputs.argtypes = [u32, u32, u32]
+    L.iqd_channelizer_window_outputs.restype = u32
     L.iqd_magnitude_dbfs.argtypes = [u32]
     L.iqd_magnitude_dbfs.restype = C.c_int32
     _LIB = L
@@ -337,10 +340,11 @@ class Engine:
 
     def accept_wideband(self, chz, wide_u8, first=0):
         """iqd_accept_wideband: one call's [n_sources, bytes_per_source] uint8 capture through the channelizer `chz` into
-        engine channels [first, first + chz.n_channels).  Returns (pcm rows, counts, magnitude, allowed) like accept()."""
-        wide = np.ascontiguousarray(wide_u8, dtype=np.uint8).reshape(chz.n_sources, -1)
+        engine channels [first, first + chz.n_channels).  Returns (pcm rows, counts, magnitude, allowed) like accept().
+        A channelizer of sample_format "s8" / "s16" takes [n_sources, 2 samples] int8 / int16 (else TypeError)."""
+        wide = chz._capture(wide_u8)
         bps = wide.shape[1]
-        row, n = bps // chz.decimation * chz.decimation_den, chz.n_channels
+        row, n = bps // (chz.decimation * chz.rail_bytes) * chz.decimation_den, chz.n_channels
         nblk = row // self.block_bytes if row % self.block_bytes == 0 else 1
         pcm = np.zeros((n, row // 64), dtype=np.int16)
         cnt = np.zeros(n, dtype=np.uint32)
@@ -591,21 +595,36 @@ def phase_inc(offset_hz, fs):
 
 _phase_inc = phase_inc      # (methods below take a `phase_inc` argument of their own)
 
+# iqd_channelizer_config.sample_format: name -> (IQD_WIDE_*, the dtype of one rail; int16 is little-endian)
+SAMPLE_FORMAT = {"u8": (0, np.dtype(np.uint8)), "s8": (1, np.dtype(np.int8)), "s16": (2, np.dtype("<i2"))}
+
+
+def channelizer_window_outputs(decimation, n_taps, sample_format="u8"):
+    """iqd_channelizer_window_outputs (host only): the most outputs per channel of one workgroup window, 0 if out of range."""
+    return int(_lib().iqd_channelizer_window_outputs(int(decimation), int(n_taps), SAMPLE_FORMAT[sample_format][0]))
+
 
 class Channelizer:
     """iqd_channelizer_*: n_channels channels cut out of n_sources wideband captures at decimation / decimation_den x
-    256 kS/s (decimation_den 1, 2, 4 or 8; 2.4 MS/s is 75 / 8)."""
+    256 kS/s (decimation_den 1, 2, 4 or 8; 2.4 MS/s is 75 / 8).  sample_format: what the captures hold - "u8" (offset
+    binary, the RTL-SDR's), "s8" (int8) or "s16" (little-endian int16); run and accept_wideband then take
+    [n_sources, 2 samples] arrays of that dtype."""
 
-    def __init__(self, engine, decimation, n_channels, n_sources=1, taps=None, decimation_den=1):
+    def __init__(self, engine, decimation, n_channels, n_sources=1, taps=None, decimation_den=1, sample_format="u8"):
         self._e, self._L = engine, engine._L
         self._h = None
+        if sample_format not in SAMPLE_FORMAT:
+            raise ValueError("sample_format must be one of %s" % ", ".join(SAMPLE_FORMAT))
+        self.sample_format = sample_format
+        self._code, self._dtype = SAMPLE_FORMAT[sample_format]
+        self.rail_bytes = self._dtype.itemsize
         self.decimation, self.n_channels, self.n_sources = int(decimation), int(n_channels), int(n_sources)
         self.decimation_den = int(decimation_den) or 1
         self.n_points = 0                                        # survey points (set_survey)
         self._taps = None if taps is None else np.ascontiguousarray(taps, np.int16)
         cfg = ChannelizerConfig(self.n_sources, self.n_channels, self.decimation,
                                 0 if self._taps is None else len(self._taps),
-                                None if self._taps is None else self._taps.ctypes.data, int(decimation_den))
+                                None if self._taps is None else self._taps.ctypes.data, int(decimation_den), self._code)
         h = C.c_void_p()
         engine._check(self._L.iqd_channelizer_create(engine._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -627,11 +646,20 @@ class Channelizer:
         self._e._check(self._L.iqd_channelizer_set_channels(self._h, int(first), int(n), _np_ptr(src), _np_ptr(inc),
                                                             _np_ptr(sh)))
 
+    def _capture(self, wide):
+        """One call's capture as [n_sources, bytes_per_source] bytes.  An array of another sample format's dtype is a
+        TypeError: a "u8" channelizer refuses int8 / int16 arrays, "s8" and "s16" anything but their own dtype."""
+        dt = getattr(wide, "dtype", None)
+        if dt is not None and dt != self._dtype and (self._code != 0 or dt in (np.dtype(np.int8), np.dtype(np.int16))):
+            raise TypeError("a channelizer of sample_format %r takes %s arrays, not %s" % (self.sample_format, self._dtype, dt))
+        wide = np.ascontiguousarray(wide, dtype=self._dtype).reshape(self.n_sources, -1)
+        return wide.view(np.uint8)
+
     def run(self, wide_u8):
         """[n_sources, bytes_per_source] uint8 -> [n_channels, bytes_per_source decimation_den / decimation] uint8 (host
-        arrays)."""
-        wide = np.ascontiguousarray(wide_u8, dtype=np.uint8).reshape(self.n_sources, -1)
-        out = np.zeros((self.n_channels, wide.shape[1] // self.decimation * self.decimation_den), np.uint8)
+        arrays).  sample_format "s8" / "s16": [n_sources, 2 samples] int8 / int16 -> [n_channels, 2 samples / decimation]."""
+        wide = self._capture(wide_u8)
+        out = np.zeros((self.n_channels, wide.shape[1] // (self.decimation * self.rail_bytes) * self.decimation_den), np.uint8)
         self._e._check(self._L.iqd_channelizer_run(self._h, _np_ptr(wide), wide.shape[1], _np_ptr(out)))
         return out
 

@@ -3,7 +3,8 @@
 // Keeps the prototype, every channel's (source, increment, gain shift) and complex taps, groups the channels by source
 // into tiles of 8 (padding slots have zero taps and store nothing), packs the tiles' taps as MFMA A operands
 // (iqd_chan.h) and queues the kernel of iqd_chan.hip on the engine's stream.  Only the channels a set_channels call
-// names get new taps; the packing is redone at the next run.
+// names get new taps; the packing is redone at the next run.  Captures of a signed sample format (IQD_WIDE_S8, IQD_WIDE_S16)
+// go to chz_fmt_kernel (iqd_chan_fmt.hip) with the same tiles and A operands; S16 adds the rows' coefficient sums.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -63,6 +64,7 @@ struct iqd_channelizer {
     hipStream_t stream = nullptr;
     uint32_t n_src = 0, n_ch = 0, m = 0, k = 0, kp = 0, nq = 0;
     uint32_t q = 1, kb = 0;                       // decimation m / q; kb = ceil(k / q), the longest branch
+    uint32_t fmt = IQD_WIDE_U8, rail = 1;         // sample format of the captures; bytes per rail B (2: IQD_WIDE_S16)
     std::vector<int16_t> h, phasor;               // prototype [K]; (c, s) pairs [8192]
     std::vector<uint32_t> src, inc;
     std::vector<uint8_t> shift;
@@ -84,6 +86,8 @@ struct iqd_channelizer {
     uint32_t n_fixed_tiles = 0;                   // tiles [0, n_fixed_tiles) hold fixed channels, the rest following ones
     std::vector<uint32_t> slot_of;                // [n_ch]: tile * 8 + slot
     std::vector<uint8_t> amat;                    // [n_tiles][q residues][nq][2][64][16]
+    std::vector<ChzFmtTile> gsum;                 // [n_tiles]: the rows' coefficient sums (IQD_WIDE_S16 only)
+    DevBufExact d_gsum;
     DevBufExact d_amat, d_tiles, d_wgs, d_swgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
     DevBufExact w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
     // the band survey: points measured on every source, in tiles of 8 of their own (iqd_chan_survey.hip)
@@ -98,6 +102,8 @@ struct iqd_channelizer {
     int cur = 0;
 
     int fail(int code, const char *msg) { return engine_fail(e, code, msg); }
+    // bytes of one channel's row for bytes_per_source capture bytes
+    size_t row_bytes(size_t bytes_per_source) const { return bytes_per_source / ((size_t)m * rail) * q; }
 };
 
 #define CHZ_TRY(z, call)                                                                                  \
@@ -190,6 +196,7 @@ static void chz_group(iqd_channelizer *z)
         for (uint32_t t = 0; t < r.n_tiles; t += z->scan_waves)
             z->swgs.push_back(ChzWg{r.source, r.first_tile + t, std::min(z->scan_waves, r.n_tiles - t), 0});
     z->amat.assign(z->tiles.size() * z->q * z->nq * 2 * 64 * 16, 0);
+    if (z->fmt == IQD_WIDE_S16) z->gsum.assign(z->tiles.size(), ChzFmtTile{});
     std::fill(z->ch_dirty.begin(), z->ch_dirty.end(), 1);
 }
 
@@ -232,6 +239,15 @@ static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
     if (tile >= z->n_fixed_tiles) return;   // a following channel: the walker builds its operands itself, per block
     const size_t taps = c == CHZ_NONE ? 0 : (size_t)c * z->q * z->kb;
     chz_pack_rows(z, z->amat.data(), tile, l, c == CHZ_NONE ? nullptr : &z->gr[taps], c == CHZ_NONE ? nullptr : &z->gi[taps]);
+    if (z->fmt == IQD_WIDE_S16) {   // the sums of rows 2 l (gr on I, -gi on Q) and 2 l + 1 (gi on I, gr on Q); |sum| < 2^25
+        int32_t sr = 0, si = 0;
+        for (uint32_t k = 0; c != CHZ_NONE && k < z->kb; k++) {
+            sr += z->gr[taps + k];
+            si += z->gi[taps + k];
+        }
+        z->gsum[tile].g[l][0] = sr - si;
+        z->gsum[tile].g[l][1] = sr + si;
+    }
 }
 
 // Packs the tiles that hold a channel with new parameters and queues their upload on the engine's stream (runs of
@@ -255,6 +271,7 @@ static int chz_upload(iqd_channelizer *z)
     if (regroup) {
         CHZ_TRY(z, z->d_amat.ensure(z->amat.size()));
         CHZ_TRY(z, z->d_tiles.ensure(n_tiles * sizeof(ChzTile)));
+        if (z->fmt == IQD_WIDE_S16) CHZ_TRY(z, z->d_gsum.ensure(std::max<size_t>(1, n_tiles) * sizeof(ChzFmtTile)));
         CHZ_TRY(z, z->d_wgs.ensure(std::max<size_t>(1, z->wgs.size()) * sizeof(ChzWg)));
         CHZ_TRY(z, z->d_swgs.ensure(std::max<size_t>(1, z->swgs.size()) * sizeof(ChzWg)));
     }
@@ -265,7 +282,7 @@ static int chz_upload(iqd_channelizer *z)
         if (!tile_dirty[t]) continue;
         if (!runs.empty() && runs.back().first + runs.back().n == t) runs.back().n++;
         else runs.push_back(Run{t, 1});
-        bytes += tile_bytes + sizeof(ChzTile);
+        bytes += tile_bytes + sizeof(ChzTile) + (z->fmt == IQD_WIDE_S16 ? sizeof(ChzFmtTile) : 0);
     }
     Staging &st = z->stg[z->stg_cur];
     CHZ_TRY(z, st.ensure(bytes ? bytes : 16));
@@ -281,6 +298,8 @@ static int chz_upload(iqd_channelizer *z)
         const size_t na = r.first < z->n_fixed_tiles ? std::min<size_t>(r.n, z->n_fixed_tiles - r.first) : 0;
         if (na) CHZ_TRY(z, copy(z->d_amat.as<uint8_t>() + r.first * tile_bytes, &z->amat[r.first * tile_bytes], na * tile_bytes));
         CHZ_TRY(z, copy(z->d_tiles.as<ChzTile>() + r.first, &z->tiles[r.first], r.n * sizeof(ChzTile)));
+        if (z->fmt == IQD_WIDE_S16)
+            CHZ_TRY(z, copy(z->d_gsum.as<ChzFmtTile>() + r.first, &z->gsum[r.first], r.n * sizeof(ChzFmtTile)));
     }
     if (regroup && !z->wgs.empty()) CHZ_TRY(z, copy(z->d_wgs.p, z->wgs.data(), z->wgs.size() * sizeof(ChzWg)));
     if (regroup && !z->swgs.empty()) CHZ_TRY(z, copy(z->d_swgs.p, z->swgs.data(), z->swgs.size() * sizeof(ChzWg)));
@@ -292,9 +311,9 @@ static int chz_upload(iqd_channelizer *z)
     return IQD_OK;
 }
 
-static int chz_fill_history(iqd_channelizer *z)   // zero history: offset-binary 0x80
+static int chz_fill_history(iqd_channelizer *z)   // zero history: offset-binary 0x80; a signed format's raw bytes: 0
 {
-    CHZ_TRY(z, hipMemsetAsync(z->d_hist[z->cur].p, 0x80, (size_t)z->n_src * 2 * z->kp, z->stream));
+    CHZ_TRY(z, hipMemsetAsync(z->d_hist[z->cur].p, z->fmt == IQD_WIDE_U8 ? 0x80 : 0, (size_t)z->n_src * 2 * z->kp * z->rail, z->stream));
     z->m_abs = 0;
     return IQD_OK;
 }
@@ -373,6 +392,12 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
                                           "decimation / decimation_den <= 64");
     for (uint32_t r : cfg->reserved)
         if (r) return engine_fail(e, IQD_EINVAL, "channelizer: reserved fields must be 0");
+    if (cfg->sample_format > IQD_WIDE_S16)
+        return engine_fail(e, IQD_EINVAL, "channelizer: sample_format must be IQD_WIDE_U8, IQD_WIDE_S8 or IQD_WIDE_S16");
+    if (cfg->sample_format != IQD_WIDE_U8 && den > 1)
+        return engine_fail(e, IQD_EINVAL, cfg->sample_format == IQD_WIDE_S16
+                               ? "channelizer: IQD_WIDE_S16 captures at a fractional rate (decimation_den > 1) are not built yet"
+                               : "channelizer: IQD_WIDE_S8 captures at a fractional rate (decimation_den > 1) are not built yet");
     std::vector<int16_t> h;
     if (cfg->taps) {
         if (cfg->n_taps < 1 || cfg->n_taps > 1024 * den)
@@ -404,6 +429,8 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
     z->m = cfg->decimation;
     z->h = h;
     z->q = den;
+    z->fmt = cfg->sample_format;
+    z->rail = cfg->sample_format == IQD_WIDE_S16 ? 2 : 1;
     z->k = (uint32_t)h.size();
     z->kb = (z->k + den - 1) / den;
     z->kp = (z->kb + 31) / 32 * 32;
@@ -427,7 +454,7 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
     std::vector<uint32_t> packed(CHZ_PHASOR);
     for (uint32_t i = 0; i < CHZ_PHASOR; i++)
         packed[i] = (uint16_t)z->phasor[2 * i] | ((uint32_t)(uint16_t)z->phasor[2 * i + 1] << 16);
-    const size_t hb = (size_t)z->n_src * 2 * z->kp;
+    const size_t hb = (size_t)z->n_src * 2 * z->kp * z->rail;
     bool ok = z->d_phasor.ensure(CHZ_PHASOR * 4) == hipSuccess && z->d_hist[0].ensure(hb) == hipSuccess &&
               z->d_hist[1].ensure(hb) == hipSuccess;
     ok = ok && hipMemcpy(z->d_phasor.p, packed.data(), CHZ_PHASOR * 4, hipMemcpyHostToDevice) == hipSuccess;
@@ -485,6 +512,8 @@ int iqd_channelizer_set_channels(iqd_channelizer_t *z, uint32_t first, uint32_t 
 
 static int chz_check_len(iqd_channelizer *z, size_t bytes_per_source)
 {
+    if (z->fmt == IQD_WIDE_S16 && (bytes_per_source == 0 || bytes_per_source % (128 * (size_t)z->m) != 0))
+        return z->fail(IQD_EINVAL, "channelizer: bytes_per_source of IQD_WIDE_S16 captures must be a positive multiple of 128 * decimation");
     if (bytes_per_source == 0 || bytes_per_source % (64 * (size_t)z->m) != 0)
         return z->fail(IQD_EINVAL, "channelizer: bytes_per_source must be a positive multiple of 64 * decimation");
     if (bytes_per_source / z->m * z->q > 0x7fffffffull) return z->fail(IQD_EINVAL, "channelizer: bytes_per_source too large");
@@ -498,6 +527,7 @@ static uint32_t chz_t_max(const iqd_channelizer *z)
     if (z->q > 1)   // windows of whole store groups: 2 (t_max m / q + kp) <= CHZ_FRAC_WIN_MAX
         return std::min<uint32_t>(1024, (uint32_t)((uint64_t)(CHZ_FRAC_WIN_MAX / 2 - z->kp) * z->q / z->m)) /
                chz_frac_group(z->q) * chz_frac_group(z->q);
+    if (z->fmt != IQD_WIDE_U8) return chz_window_outputs(z->m, z->kp, z->rail);
     return std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - z->kp) / z->m) / CHZ_GROUP * CHZ_GROUP;
 }
 
@@ -509,7 +539,7 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
         int rc = chz_upload(z);
         if (rc != IQD_OK) return rc;
     }
-    const uint32_t n_out = (uint32_t)(bytes_per_source / (2 * z->m) * z->q);   // a multiple of 32 q
+    const uint32_t n_out = (uint32_t)(z->row_bytes(bytes_per_source) / 2);   // a multiple of 32 q
     const uint32_t t_max = chz_t_max(z);
     ChzLaunch a{};
     a.wide = (const uint8_t *)wide_dev;
@@ -542,7 +572,16 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
         scan->wpt = z->scan_wpt;
         scan->t_blk = scan->block_out <= t_max ? scan->block_out : t_max;   // the walker's windows stay inside one block
     }
-    CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->d_swgs.as<ChzWg>(), scan ? (uint32_t)z->swgs.size() : 0u, scan, z->stream));
+    if (z->fmt != IQD_WIDE_U8) {   // (no following channels, no fractional rate: refused where they are asked for)
+        ChzFmtLaunch f{};
+        f.a = a;
+        f.gsum = z->d_gsum.as<ChzFmtTile>();
+        f.rail_bytes = z->rail;
+        f.pstride = 2 * (a.t_blk * a.m + a.kp) + 16;
+        CHZ_TRY(z, launch_channelizer_fmt(f, (uint32_t)z->wgs.size(), z->stream));
+    } else {
+        CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->d_swgs.as<ChzWg>(), scan ? (uint32_t)z->swgs.size() : 0u, scan, z->stream));
+    }
     z->cur ^= 1;
     z->m_abs += n_out;
     return IQD_OK;
@@ -567,7 +606,7 @@ int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_
     int rc = chz_check_len(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(z->device);
-    const size_t ib = (size_t)z->n_src * bytes_per_source, ob = (size_t)z->n_ch * (bytes_per_source / z->m * z->q);
+    const size_t ib = (size_t)z->n_src * bytes_per_source, ob = (size_t)z->n_ch * z->row_bytes(bytes_per_source);
     CHZ_TRY(z, z->st_wide.ensure(ib));
     CHZ_TRY(z, z->st_out.ensure(ob));
     CHZ_TRY(z, hipMemcpyAsync(z->st_wide.p, wide, ib, hipMemcpyHostToDevice, z->stream));
@@ -582,6 +621,9 @@ int iqd_channelizer_set_survey(iqd_channelizer_t *z, uint32_t n_points, const ui
 {
     if (!z) return IQD_EINVAL;
     if (n_points > 4096) return z->fail(IQD_EINVAL, "channelizer: a survey has at most 4096 points");
+    if (n_points && z->fmt != IQD_WIDE_U8)
+        return z->fail(IQD_EINVAL, z->fmt == IQD_WIDE_S16 ? "channelizer: the band survey of IQD_WIDE_S16 captures is not built yet"
+                                                          : "channelizer: the band survey of IQD_WIDE_S8 captures is not built yet");
     if (n_points && !phase_inc) return z->fail(IQD_EINVAL, "channelizer: NULL survey increments");
     for (uint32_t i = 0; gain_shift && i < n_points; i++)
         if (gain_shift[i] > 8) return z->fail(IQD_EINVAL, "channelizer: gain shift must be 0..8");
@@ -735,7 +777,7 @@ static int wideband_queue(iqd_t *e, iqd_channelizer *z, uint32_t first_ch, const
     uint32_t e_nch = 0, bb = 0, flags = 0;
     engine_geometry(e, &e_nch, &bb, &flags);
     if (first_ch >= e_nch || z->n_ch > e_nch - first_ch) return z->fail(IQD_EINVAL, "accept_wideband: bad engine channel range");
-    const size_t row = bytes_per_source / z->m * z->q;
+    const size_t row = z->row_bytes(bytes_per_source);
     if (row % bb != 0 && (row >= bb || row % 64 != 0))
         return z->fail(IQD_EINVAL, "accept_wideband: bytes_per_source / decimation must be a multiple of block_bytes, or one short block");
     const size_t nblk = row % bb == 0 ? row / bb : 1;
@@ -759,7 +801,7 @@ static int wideband_queue(iqd_t *e, iqd_channelizer *z, uint32_t first_ch, const
         // still, the channelizer steps back as well: the call's history went to the other buffer, so the stream stands
         // where it stood before the call, like the engine's.
         z->cur ^= 1;
-        z->m_abs -= bytes_per_source / (2 * z->m) * z->q;
+        z->m_abs -= z->row_bytes(bytes_per_source) / 2;
         return rc;
     }
     return IQD_OK;
@@ -775,7 +817,7 @@ int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const
     if (rc != IQD_OK) return rc;
     uint32_t e_nch = 0, bb = 0, flags = 0;
     engine_geometry(e, &e_nch, &bb, &flags);
-    const size_t row = bytes_per_source / z->m * z->q;
+    const size_t row = z->row_bytes(bytes_per_source);
     const size_t nblk = row % bb == 0 ? row / bb : 1;
     (void)hipSetDevice(z->device);
     const size_t n = z->n_ch, ib = (size_t)z->n_src * bytes_per_source;
@@ -819,6 +861,9 @@ int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_
 {
     if (!z) return IQD_EINVAL;
     if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
+    if (follow && z->fmt != IQD_WIDE_U8)
+        return z->fail(IQD_EINVAL, z->fmt == IQD_WIDE_S16 ? "channelizer: channels on IQD_WIDE_S16 captures cannot follow a scanner yet"
+                                                          : "channelizer: channels on IQD_WIDE_S8 captures cannot follow a scanner yet");
     if (follow && z->q > 1)
         return z->fail(IQD_EINVAL, "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow a scanner");
     for (uint32_t i = 0; i < n; i++) {
@@ -829,6 +874,15 @@ int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_
         z->layout_dirty = true;
     }
     return IQD_OK;
+}
+
+// chz_t_max as a host-only function (the window's fit in LDS is checked on it for every M)
+uint32_t iqd_channelizer_window_outputs(uint32_t decimation, uint32_t n_taps, uint32_t sample_format)
+{
+    if (decimation < 2 || decimation > 64 || n_taps < 1 || n_taps > 1024 || sample_format > IQD_WIDE_S16) return 0;
+    const uint32_t kp = (n_taps + 31) / 32 * 32;
+    if (sample_format == IQD_WIDE_U8) return std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - kp) / decimation) / CHZ_GROUP * CHZ_GROUP;
+    return chz_window_outputs(decimation, kp, sample_format == IQD_WIDE_S16 ? 2 : 1);
 }
 
 int iqd_channelizer_tuning(uint32_t decimation, uint64_t source_centre_hz, uint64_t station_hz, int rotation, uint32_t *inc)

@@ -90,6 +90,28 @@ struct ChzSurveyLaunch {
     uint32_t n_win, rows;                  // windows of a.t_blk outputs per source; ceil(n_tiles / CHZ_WAVES)
 };
 
+// Signed captures (chz_fmt_kernel, iqd_chan_fmt.hip; IQD_WIDE_S8 / IQD_WIDE_S16) beside ChzLaunch, whose fields mean what
+// they mean to chz_kernel except: a.wide / a.hist / a.hist_next are raw capture bytes of the format (2 B bytes per sample,
+// B = rail_bytes; the history is 2 kp B bytes per source, zero history is zero bytes) and a.bytes_per_source counts them.
+// The window is staged as B signed-byte planes of 2 (t_blk m + kp) bytes each, pstride apart.
+struct ChzFmtTile {
+    int32_t g[CHZ_TILE_CH][2];             // per slot: the coefficient sums of its rows, sum gr - sum gi and sum gr + sum gi
+};
+struct ChzFmtLaunch {
+    ChzLaunch a;
+    const ChzFmtTile *gsum;                // [n_tiles], beside a.tiles (S16 only)
+    uint32_t rail_bytes;                   // B: 1 (S8, one plane) or 2 (S16, planes hi and lo')
+    uint32_t pstride;                      // LDS bytes from one plane to the next: >= 2 (t_blk m + kp) + 16, a multiple of 16
+};
+
+// The most outputs of one window with `planes` byte planes of the samples in LDS (1: U8 and S8, 2: S16):
+// 2 planes (t m + kp) <= CHZ_WIN_MAX, whole store groups, at most 1024.  (iqd_channelizer_window_outputs exports it.)
+constexpr uint32_t chz_window_outputs(uint32_t m, uint32_t kp, uint32_t planes)
+{
+    const uint32_t t = (CHZ_WIN_MAX / (2 * planes) - kp) / m;
+    return (t < 1024 ? t : 1024) / CHZ_GROUP * CHZ_GROUP;
+}
+
 // iqd_channelizer_tuning: the increment of a channel whose station is `station` Hz (centre station + 64000 r) cut from a
 // source centred on `centre` Hz at Fs = 256000 M; false when out of band.  Host and device share this one statement.
 __host__ __device__ inline bool chz_tuning(uint32_t m, unsigned long long centre, unsigned long long station, int32_t r,
@@ -112,6 +134,9 @@ hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_fixed_wgs, const Ch
 hipError_t launch_channelizer_frac(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s);
 // chz_survey_kernel for a.den = 1, 2, 4, 8 and the kernel that divides the sums (iqd_chan_survey.hip)
 hipError_t launch_channelizer_survey(const ChzLaunch &a, const ChzSurveyLaunch &s, hipStream_t st);
+
+// chz_fmt_kernel for f.rail_bytes = 1, 2 and its history kernel (iqd_chan_fmt.hip)
+hipError_t launch_channelizer_fmt(const ChzFmtLaunch &f, uint32_t n_wgs, hipStream_t st);
 
 // host-only spec pieces (iqd_chan.cpp)
 void chz_phasor_table(int16_t *out /* [8192] (c, s) pairs */);

@@ -72,4 +72,28 @@ __device__ __forceinline__ void chz_stage_window(const ChzLaunch &a, uint32_t so
     }
 }
 
+// Signed 16-bit captures (chz_fmt_kernel, iqd_chan_fmt.hip).  Two little-endian samples' dwords w0, w1 = (I lo, I hi, Q lo,
+// Q hi) each -> one dword of the high plane (I hi, Q hi of both) and of the low plane (the low bytes - 128, i.e. ^ 0x80).
+// Plain shifts and masks: the compiler makes each one v_perm_b32.
+__host__ __device__ __forceinline__ uint32_t chz_fmt_hi(uint32_t w0, uint32_t w1)
+{
+    return ((w0 >> 8) & 0xffu) | ((w0 >> 16) & 0xff00u) | ((w1 << 8) & 0xff0000u) | (w1 & 0xff000000u);
+}
+__host__ __device__ __forceinline__ uint32_t chz_fmt_lo(uint32_t w0, uint32_t w1)
+{
+    return ((w0 & 0xffu) | ((w0 >> 8) & 0xff00u) | ((w1 << 16) & 0xff0000u) | ((w1 << 8) & 0xff000000u)) ^ 0x80808080u;
+}
+
+// One rail of an S16 output before sat16: (A + 2^15) >> 16 for A = 256 H + Lo' + 128 G, from the accumulators of the high
+// sample plane (H: tap planes hlo, hhi), of the low one (Lo': llo, lhi) and the row's coefficient sum G.  H and Lo' fit int32
+// like chz_epilogue's A (their 256 hi alone need not: combined modulo 2^32); Lo = Lo' + 128 G need not and is an int64;
+// |(Lo + 2^15) >> 8| < 2^25 and its sum with H fit int32 again.  |result| < 2^23.
+__host__ __device__ __forceinline__ int32_t chz_fmt_stage_a(int32_t hlo, int32_t hhi, int32_t llo, int32_t lhi, int32_t G)
+{
+    const int32_t H = (int32_t)((uint32_t)hlo + ((uint32_t)hhi << 8));
+    const int32_t Lp = (int32_t)((uint32_t)llo + ((uint32_t)lhi << 8));
+    const int64_t Lo = (int64_t)Lp + 128 * (int64_t)G;
+    return (H + (int32_t)((Lo + 32768) >> 8)) >> 8;
+}
+
 }  // namespace iqd

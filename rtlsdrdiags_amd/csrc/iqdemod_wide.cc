@@ -1,5 +1,5 @@
 // iqdemod_wide — many channels out of ONE wideband capture, straight over the C ABI (include/iqdemod.h): the one-receiver
-// counterpart of iqdemod_multi.  The capture is uint8 interleaved I/Q at decimation x 256 kS/s (an RTL-SDR at 2.048 MS/s
+// counterpart of iqdemod_multi.  The capture is interleaved I/Q (uint8, or format=s8 / s16) at decimation x 256 kS/s (an RTL-SDR at 2.048 MS/s
 // is decimation=8, one at 2.4 MS/s decimation=75/8); every channel is cut out by the channelizer (iqd_channelizer_*) at its offset from the capture's
 // centre and demodulated by one engine channel - one reference IqDataProcessor with its demodulators (Radio.cc:150-181).
 // PCM goes out as S16_LE at 8 kS/s (radioApp.cc:103-111), one file per channel.
@@ -7,8 +7,11 @@
 //   iqdemod_wide in=cap.iq [decimation=8] rate=2048000 offsets=<Hz>[,<Hz>...] modes=<m>[,<m>...] [gains=<L>[,<L>...]]
 //                out=pcm_%d.s16 [blocks=K] [rotation=<r>] [centre=<Hz>] [scan=<start>,<end>,<step>[,...]]
 //                [squelch=<dBFS>[,<dBFS>...]] [freqlog=<file>]
-//                [survey=<first_offset_Hz>,<step_Hz>,<count> [surveyshift=<L>] surveylog=<file>]
+//                [survey=<first_offset_Hz>,<step_Hz>,<count> [surveyshift=<L>] surveylog=<file>] [format=u8|s8|s16]
 //
+//   format     what the capture holds: u8 offset binary (an RTL-SDR; the default), s8 signed int8 (hackrf_transfer), s16
+//              little-endian signed int16 (SDRplay, Airspy, USRP, SDR++ / SDR# / SDRangel basebands).  s8 and s16 are for
+//              fixed channels at an integer decimation: not together with survey=, scan= or a fractional rate.
 //   decimation M, or P/Q with Q = 2, 4 or 8 (rate = 256000 P / Q); left out, it is rate / 256000 in lowest terms
 //   offsets    the channel's frequency minus the capture's centre, Hz (|offset| < rate / 2)
 //   modes      per channel, the list repeating (0 none 1 am 2 fm 3 wbfm 4 lsb 5 usb)
@@ -84,6 +87,7 @@ int main(int argc, char **argv)
   std::vector<uint64_t> scan;
   std::vector<double> survey;
   uint32_t surveyshift = 0;
+  std::string format = "u8";
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
     if (!strncmp(a, "in=", 3)) in = a + 3;
@@ -107,6 +111,7 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "survey=", 7)) survey = numList(a + 7);
     else if (!strncmp(a, "surveyshift=", 12)) surveyshift = (uint32_t)atoi(a + 12);
     else if (!strncmp(a, "surveylog=", 10)) surveylog = a + 10;
+    else if (!strncmp(a, "format=", 7)) format = a + 7;
     else {
       fprintf(stderr, "iqdemod_wide: unknown argument %s\n", a);
       return 1;
@@ -125,6 +130,17 @@ int main(int argc, char **argv)
       den /= 2;
     }
   }
+  if (format != "u8" && format != "s8" && format != "s16") {
+    fprintf(stderr, "iqdemod_wide: format must be u8, s8 or s16\n");
+    return 1;
+  }
+  const uint32_t sample_format = format == "s16" ? IQD_WIDE_S16 : format == "s8" ? IQD_WIDE_S8 : IQD_WIDE_U8;
+  const size_t rail = format == "s16" ? 2 : 1;   // bytes per rail
+  if (sample_format != IQD_WIDE_U8 && (!survey.empty() || !scan.empty() || den > 1)) {
+    fprintf(stderr, "iqdemod_wide: format=%s cannot be combined with %s: not built for signed captures yet\n", format.c_str(),
+            !survey.empty() ? "survey=" : !scan.empty() ? "scan=" : "a fractional rate");
+    return 1;
+  }
   const bool surveying = !survey.empty();
   const bool survey_ok = !surveying || (survey.size() == 3 && survey[2] >= 1 && survey[2] <= 4096 && surveyshift <= 8 && !surveylog.empty());
   const bool demod_ok = !offsets.empty() ? !out.empty() && !modes.empty() : surveying;
@@ -135,7 +151,7 @@ int main(int argc, char **argv)
   if (in.empty() || !demod_ok || !survey_ok || m < 2 || den < 1 || rate <= 0 || gains.empty() || !blocks || scan.size() % 3 != 0) {
     fprintf(stderr, "usage: iqdemod_wide in=cap.iq [decimation=8|75/8] rate=2048000 offsets=<Hz,...> modes=<m,...> "
                     "[gains=<L,...>] out=pcm_%%d.s16 [blocks=K] [rotation=r] [centre=Hz] [scan=start,end,step,...] "
-                    "[squelch=dBFS,...] [freqlog=file] [survey=first_Hz,step_Hz,count [surveyshift=L] surveylog=file]\n");
+                    "[squelch=dBFS,...] [freqlog=file] [survey=first_Hz,step_Hz,count [surveyshift=L] surveylog=file] [format=u8|s8|s16]\n");
     return 1;
   }
   const uint32_t n = (uint32_t)offsets.size();   // 0: survey only
@@ -204,6 +220,7 @@ int main(int argc, char **argv)
   zc.n_channels = n ? n : 1;   // (survey only: one channel at offset 0 carries the stream's history along)
   zc.decimation = m;
   zc.decimation_den = den;
+  zc.sample_format = sample_format;
   iqd_channelizer_t *z = nullptr;
   rc = iqd_channelizer_create(e, &zc, &z);
   if (rc == IQD_OK && n) rc = iqd_channelizer_set_channels(z, 0, n, source.data(), inc.data(), shift.data());
@@ -236,9 +253,10 @@ int main(int argc, char **argv)
   }
 
   // (wide bytes per engine block: 32768 m / den = 64 m (512 / den), whole calls of the channelizer)
-  const size_t block = 32768 / den * (size_t)m, call = blocks * block, unit = 64 * (size_t)m;
+  // (rail bytes per rail: a signed 16-bit capture has twice the bytes per block; den is 1 there)
+  const size_t block = 32768 / den * (size_t)m * rail, call = blocks * block, unit = 64 * (size_t)m * rail;
   std::vector<uint8_t> wide(call);
-  std::vector<int16_t> pcm((size_t)n * call / m * den / 64);
+  std::vector<int16_t> pcm((size_t)n * call / m / rail * den / 64);
   std::vector<uint32_t> sv_mag((size_t)blocks * n_pts);
   std::vector<uint8_t> sv_rows(n ? 0 : call / m * den);
   std::vector<uint32_t> count(n);
@@ -285,7 +303,7 @@ int main(int argc, char **argv)
       status = 3;
       return false;
     }
-    const size_t row = bytes / m * den / 64;
+    const size_t row = bytes / m / rail * den / 64;
     for (uint32_t c = 0; c < n; c++)
       if (fwrite(&pcm[(size_t)c * row], 2, count[c], sinks[c]) != count[c]) {
         fprintf(stderr, "iqdemod_wide: write failed\n");

@@ -4,6 +4,7 @@ per channel and call, M = 8, default taps.  Prints one JSON line:
 
     python tools/chan_bench.py [--steps K] [--settle-ms 100]
     python tools/chan_bench.py --decimation 75 --den 8   (a fractional channelizer: a 2.4 MS/s capture, same outputs)
+    python tools/chan_bench.py --format s16            (a signed 16-bit capture, or s8: chz_fmt_kernel; same outputs)
     python tools/chan_bench.py --scan [--steps K]      (scanner-driven channels, written to profiles/ as well)
     python tools/chan_bench.py --survey [--decimation 75 --den 8]   (the band survey against rows of real channels)
 
@@ -62,6 +63,7 @@ def main():
     ap.add_argument("--grid-only", action="store_true", help="with --survey: only grid_run_ms (a build without the survey)")
     ap.add_argument("--decimation", type=int, default=8, help="M, or P of a fractional decimation P / Q")
     ap.add_argument("--den", type=int, default=1, help="Q of a fractional decimation (1, 2, 4, 8)")
+    ap.add_argument("--format", choices=["u8", "s8", "s16"], default="u8", help="the captures' sample format")
     args = ap.parse_args()
     from rtlsdrdiags_amd import capi
     if args.scan:
@@ -70,12 +72,13 @@ def main():
         return survey_bench(capi, args)
 
     M, Q, n_src, n_ch, n_out = args.decimation, args.den, 16, 4096, 1 << 16
-    bps = n_out * 2 * M // Q
+    B = 2 if args.format == "s16" else 1               # bytes per rail (white bytes are full-scale in every format)
+    bps = n_out * 2 * M * B // Q
     row = 2 * n_out
     rng = np.random.default_rng(1)
     eng = capi.Engine(n_ch)
     eng.set_mode("fm")
-    z = capi.Channelizer(eng, M, n_ch, n_src, decimation_den=Q)
+    z = capi.Channelizer(eng, M, n_ch, n_src, decimation_den=Q, sample_format=args.format)
     z.set_channels(0, source=np.arange(n_ch) % n_src, phase_inc=rng.integers(0, 2 ** 32, n_ch, dtype=np.uint64),
                    gain_shift=np.full(n_ch, 3))
     d_in, d_out = eng.dev_alloc(n_src * bps), eng.dev_alloc(n_ch * row)
@@ -86,7 +89,7 @@ def main():
     chan = lambda: z.run_device(d_in, bps, d_out)
     chan_ms, chan_mean = timed(chan, eng.synchronize, args.steps, args.settle_ms)
     line = {"workload": "channelizer 4096 ch / 16 sources / 2^16 outputs / M=%s / default taps" % (M if Q == 1 else "%d/%d" % (M, Q)),
-            "chan_ms": round(chan_ms, 4),
+            "format": args.format, "chan_ms": round(chan_ms, 4),
             "chan_mean_ms": round(chan_mean, 4)}
     if not args.chan_only:
         fm = lambda: eng.accept_device(d_out, row, d_pcm, d_cnt)
@@ -97,7 +100,7 @@ def main():
     K = -(-len(capi.channelizer_default_taps(M, Q)) // Q)     # taps per branch
     nq = (K + 31) // 32
     tiles = n_src * ((n_ch // n_src + 7) // 8)
-    mfma = tiles * (n_out // 16) * nq * 2              # v_mfma_i32_16x16x64_i8, two tap planes
+    mfma = tiles * (n_out // 16) * nq * 2 * B          # v_mfma_i32_16x16x64_i8, two tap planes x B sample planes
     ops = mfma * 16 * 16 * 64 * 2
     hbm = n_src * bps + n_ch * row                     # input once, output rows; taps and phasor stay in cache
     line.update(bytes=hbm, out_bytes=n_ch * row, mfma_instructions=mfma, mfma_ops=ops,
