@@ -126,7 +126,8 @@ int iqd_get_rx_gain_db(iqd_t *e, uint32_t ch, uint32_t *gain_db);
  * reference's signalMagnitudeCallback, IqDataProcessor.cc:781-790 -> AutomaticGainControl.cc:47-64 - and moves
  * the channel's IF gain (Radio::setReceiveIfGainInDb, Radio.cc:817-868), which the squelch of the NEXT block
  * compares with (IqDataProcessor.cc:765).  The recorded samples themselves do not change with the gain: there
- * is no tuner behind a channel here.  Each setter mirrors the reference method of the same name and returns
+ * is no tuner behind a channel here - except a channelizer channel that follows its gain ("Gain-following channels"
+ * below: the channelizer applies the IF gain per block).  Each setter mirrors the reference method of the same name and returns
  * IQD_EINVAL where that method returns false (setType :287-320, setDeadband :351-369, setBlankingLimit :399-420,
  * setOperatingPoint :440-448, setAgcFilterCoefficient :475-493, enable/disable :516-595). */
 enum iqd_agc_type { IQD_AGC_LOWPASS = 0, IQD_AGC_HARRIS = 1 };
@@ -448,6 +449,47 @@ int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_
 int iqd_channelizer_tuning(uint32_t decimation, uint64_t source_centre_hz, uint64_t station_hz, int rotation, uint32_t *inc);
 int iqd_accept_wideband_device(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const void *wide_dev, size_t bytes_per_source,
                                void *rows_dev, void *pcm_dev, void *pcm_count_dev, void *magnitude_dev, void *signal_present_dev);
+
+/* Gain-following channels: a channelizer channel c may FOLLOW THE IF GAIN of the engine channel it feeds in
+ * iqd_accept_wideband*(e, z, first_ch, ...), e_c = first_ch + c.  The channelizer stands where the reference's tuner
+ * stands, so this closes the AGC's loop: the samples get louder or quieter, the next block's magnitude answers.  A
+ * following channel's row of one call is split into the engine's blocks (block_bytes, or the one short block), as for
+ * scanner-driven channels; block b is cut by exactly the integer spec above - taps, emit point, A, stage a, rotation,
+ * history, absolute n - except that the last step uses a gain in dB instead of the shift L:
+ *
+ *   G_b       e_c's IF gain in force when block b begins: for b = 0 after the call's pending settings are applied
+ *             (iqd_set_rx_gain_db, AGC one-shots); for b > 0 after block b-1's AGC step.  Exactly the value the engine's
+ *             gain trace records for block b, the gain block b's squelch compares with.  With the AGC disabled it is the
+ *             operator's manual gain: iqd_set_rx_gain_db is then a gain in dB for the channel (default 24).
+ *   g_b       min(G_b, IQD_GAIN_FOLLOW_MAX = 48).  The squelch still subtracts the unclamped G_b: with the samples
+ *             scaled, dBFS - gain is the antenna-referred level, as in the reference (IqDataProcessor.cc:765).
+ *   split     e = g_b div 6, j = g_b mod 6, m_j = lrint(4096 2^(j/6)) = IQD_GAIN_M0 .. IQD_GAIN_M5.
+ *   output    with r = rr or ri of the spec above (|r| < 2^31): t = floor(r m_j / 2^14),
+ *             y = sat8((t + 2^(19-e)) >> (20-e)), byte = y + 128.
+ *   identity  g = 6 L gives, byte for byte, the channel with gain shift L: floor(r / 4) + 2^(19-e) =
+ *             floor((r + 2^(21-e)) / 4).  "6 dB" is therefore a factor of exactly 2 (6.0206 dB): a step of 6 in g is
+ *             0.02 dB more than 6 dB, and the steps within are within 0.006 dB of 1 dB (m_j is rounded to 1 in 4096).
+ *   floor     there is no gain below 0 dB: a channel whose carrier is near full scale at g = 0 stays there.
+ *
+ * The AGC's meaning is unchanged: the accept behind the channelizer re-derives the same decisions from the rows and moves
+ * the real state; the channelizer steps a shadow of agc_run per block on the device, with no host synchronisation per block
+ * and one launch per call whatever the block count.
+ *
+ * iqd_channelizer_follow_gain(z, first, n, 1 / 0): while a channel follows, its set_channels gain shift is kept but ignored
+ *             (source and increment still apply); it is back in force at the next call after follow = 0.
+ *             iqd_channelizer_reset keeps the flags.  follow = 0 on channels that do not follow is accepted.
+ * IQD_EINVAL, before anything is queued: follow = 1 on a channelizer with decimation_den > 1 or sample_format != 0; follow = 1
+ *             on a channel that follows its scanner, and iqd_channelizer_follow_scanner(..., 1) on a channel that follows
+ *             its gain; iqd_channelizer_run / run_device while any channel follows its gain (no engine channel to
+ *             follow); iqd_channelizer_survey* while any channel follows its gain. */
+#define IQD_GAIN_FOLLOW_MAX 48
+#define IQD_GAIN_M0 4096
+#define IQD_GAIN_M1 4598
+#define IQD_GAIN_M2 5161
+#define IQD_GAIN_M3 5793
+#define IQD_GAIN_M4 6502
+#define IQD_GAIN_M5 7298
+int iqd_channelizer_follow_gain(iqd_channelizer_t *z, uint32_t first, uint32_t n, int follow);
 
 /* Band survey: where in the capture are the signals?  Per block and per point of a grid, the magnitude the squelch would
  * see - without placing channels, writing rows or running an accept.

@@ -71,7 +71,7 @@ EXPORTS = [
     "iqd_channelizer_default_taps", "iqd_channelizer_set_source_frequency", "iqd_channelizer_follow_scanner",
     "iqd_channelizer_tuning", "iqd_accept_wideband_device", "iqd_channelizer_default_taps_q",
     "iqd_channelizer_set_survey", "iqd_channelizer_survey_device", "iqd_channelizer_survey", "iqd_magnitude_dbfs",
-    "iqd_channelizer_window_outputs",
+    "iqd_channelizer_window_outputs", "iqd_channelizer_follow_gain",
 ]
 
 _LIB = None
@@ -158,6 +158,7 @@ def _lib():
     L.iqd_channelizer_default_taps_q.argtypes = [u32, u32, vp, u32]
     L.iqd_channelizer_set_source_frequency.argtypes = [vp, u32, u32, vp]
     L.iqd_channelizer_follow_scanner.argtypes = [vp, u32, u32, C.c_int]
+    L.iqd_channelizer_follow_gain.argtypes = [vp, u32, u32, C.c_int]
     L.iqd_channelizer_tuning.argtypes = [u32, u64, u64, C.c_int, C.POINTER(u32)]
     L.iqd_accept_wideband_device.argtypes = [vp, vp, u32, vp, sz, vp, vp, vp, vp, vp]
     L.iqd_channelizer_set_survey.argtypes = [vp, u32, vp, vp]
@@ -707,6 +708,12 @@ class Channelizer:
         """Channels [first, first + n) follow (or stop following) their engine channel's scanner."""
         n = self.n_channels - int(first) if n is None else int(n)
         self._e._check(self._L.iqd_channelizer_follow_scanner(self._h, int(first), n, 1 if follow else 0))
+
+    def follow_gain(self, follow=True, first=0, n=None):
+        """Channels [first, first + n) follow (or stop following) their engine channel's IF gain: the channelizer applies it,
+        in dB and per engine block, in place of the channel's gain shift."""
+        n = self.n_channels - int(first) if n is None else int(n)
+        self._e._check(self._L.iqd_channelizer_follow_gain(self._h, int(first), n, 1 if follow else 0))
 
     def close(self):
         """iqd_channelizer_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""

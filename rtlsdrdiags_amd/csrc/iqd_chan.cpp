@@ -3,7 +3,8 @@
 // Keeps the prototype, every channel's (source, increment, gain shift) and complex taps, groups the channels by source
 // into tiles of 8 (padding slots have zero taps and store nothing), packs the tiles' taps as MFMA A operands
 // (iqd_chan.h) and queues the kernel of iqd_chan.hip on the engine's stream.  Only the channels a set_channels call
-// names get new taps; the packing is redone at the next run.  Captures of a signed sample format (IQD_WIDE_S8, IQD_WIDE_S16)
+// names get new taps; the packing is redone at the next run.  Channels that follow their engine channel's IF gain
+// (iqd_channelizer_follow_gain) get tiles and workgroups of their own and go to chz_gain_kernel (iqd_chan_gain.hip).  Captures of a signed sample format (IQD_WIDE_S8, IQD_WIDE_S16)
 // go to chz_fmt_kernel (iqd_chan_fmt.hip) with the same tiles and A operands; S16 adds the rows' coefficient sums.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -69,8 +70,9 @@ struct iqd_channelizer {
     std::vector<uint32_t> src, inc;
     std::vector<uint8_t> shift;
     std::vector<uint8_t> follow;                  // [n_ch]: the channel follows its engine channel's scanner
+    std::vector<uint8_t> follow_gain;             // [n_ch]: the channel follows its engine channel's IF gain
     std::vector<unsigned long long> centre;       // [n_src]: source centre frequencies
-    uint32_t n_follow = 0;
+    uint32_t n_follow = 0, n_gain = 0;
     bool centre_dirty = true;
     uint32_t n_cus = 256;
     std::vector<int16_t> gr, gi;                  // [n_ch][q branches][kb], zero from a branch's length on
@@ -81,14 +83,17 @@ struct iqd_channelizer {
     std::vector<ChzTile> tiles;
     std::vector<ChzWg> wgs;                       // chz_kernel's workgroups (fixed channels)
     std::vector<ChzWg> swgs;                      // the walker's (following channels)
+    std::vector<ChzWg> gwgs;                      // the gain walker's (gain-following channels)
     uint32_t scan_waves = 1;                      // tiles per walker workgroup
     uint32_t scan_wpt = 1;                        // waves per tile
-    uint32_t n_fixed_tiles = 0;                   // tiles [0, n_fixed_tiles) hold fixed channels, the rest following ones
+    uint32_t gain_waves = 1, gain_wpt = 1;        // the same of the gain walker
+    uint32_t n_fixed_tiles = 0;                   // tiles [0, n_fixed_tiles) hold fixed channels,
+    uint32_t n_packed_tiles = 0;                  // [n_fixed_tiles, n_packed_tiles) gain-following ones, the rest scanner-following
     std::vector<uint32_t> slot_of;                // [n_ch]: tile * 8 + slot
     std::vector<uint8_t> amat;                    // [n_tiles][q residues][nq][2][64][16]
     std::vector<ChzFmtTile> gsum;                 // [n_tiles]: the rows' coefficient sums (IQD_WIDE_S16 only)
     DevBufExact d_gsum;
-    DevBufExact d_amat, d_tiles, d_wgs, d_swgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
+    DevBufExact d_amat, d_tiles, d_wgs, d_swgs, d_gwgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
     DevBufExact w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
     // the band survey: points measured on every source, in tiles of 8 of their own (iqd_chan_survey.hip)
     std::vector<uint32_t> sv_inc;
@@ -154,20 +159,34 @@ static void chz_new_taps(iqd_channelizer *z, uint32_t c)
     z->any_dirty = true;
 }
 
-// channels sorted by source, 8 per tile, up to CHZ_WAVES tiles of one source per workgroup row; fixed and following
-// channels never share a tile.  The walker's workgroups take scan_waves tiles each: as few as keep every CU busy.
+// channels sorted by source, 8 per tile, up to CHZ_WAVES tiles of one source per workgroup row; fixed, gain-following and
+// scanner-following channels never share a tile.  A walker's workgroups take `waves` tiles each: as few as keep every CU
+// busy; the rest of the workgroup's 8 waves share the tiles' outputs (wpt waves per tile).
+static void chz_walker_wgs(const iqd_channelizer *z, const std::vector<ChzWg> &runs, std::vector<ChzWg> &wgs, uint32_t &waves,
+                           uint32_t &wpt)
+{
+    uint32_t n_tiles = 0;
+    for (const ChzWg &r : runs) n_tiles += r.n_tiles;
+    waves = std::max(1u, std::min(CHZ_WAVES, n_tiles / std::max(1u, z->n_cus)));
+    wpt = 1;
+    while (2 * wpt * waves <= CHZ_WAVES) wpt *= 2;
+    for (const ChzWg &r : runs)
+        for (uint32_t t = 0; t < r.n_tiles; t += waves)
+            wgs.push_back(ChzWg{r.source, r.first_tile + t, std::min(waves, r.n_tiles - t), 0});
+}
+
 static void chz_group(iqd_channelizer *z)
 {
     z->tiles.clear();
     z->wgs.clear();
     z->swgs.clear();
+    z->gwgs.clear();
     z->slot_of.assign(z->n_ch, 0);
-    std::vector<std::vector<uint32_t>> by_src[2];
-    by_src[0].resize(z->n_src);
-    by_src[1].resize(z->n_src);
-    for (uint32_t c = 0; c < z->n_ch; c++) by_src[z->follow[c] ? 1 : 0][z->src[c]].push_back(c);
-    std::vector<ChzWg> runs;                      // following tiles per source
-    for (int f = 0; f < 2; f++)
+    std::vector<std::vector<uint32_t>> by_src[3];   // 0 fixed, 1 gain-following, 2 scanner-following
+    for (auto &b : by_src) b.resize(z->n_src);
+    for (uint32_t c = 0; c < z->n_ch; c++) by_src[z->follow[c] ? 2 : z->follow_gain[c] ? 1 : 0][z->src[c]].push_back(c);
+    std::vector<ChzWg> runs[3];                   // following tiles per source
+    for (int f = 0; f < 3; f++) {
         for (uint32_t s = 0; s < z->n_src; s++) {
             const auto &list = by_src[f][s];
             const uint32_t first_tile = (uint32_t)z->tiles.size();
@@ -180,21 +199,17 @@ static void chz_group(iqd_channelizer *z)
                 z->tiles.push_back(t);
             }
             const uint32_t n_tiles = (uint32_t)z->tiles.size() - first_tile;
-            z->n_fixed_tiles = f == 0 ? (uint32_t)z->tiles.size() : z->n_fixed_tiles;
             if (f == 0)
                 for (uint32_t t = 0; t < n_tiles; t += CHZ_WAVES)
                     z->wgs.push_back(ChzWg{s, first_tile + t, std::min(CHZ_WAVES, n_tiles - t), 0});
             else if (n_tiles)
-                runs.push_back(ChzWg{s, first_tile, n_tiles, 0});
+                runs[f].push_back(ChzWg{s, first_tile, n_tiles, 0});
         }
-    uint32_t n_follow_tiles = 0;
-    for (const ChzWg &r : runs) n_follow_tiles += r.n_tiles;
-    z->scan_waves = std::max(1u, std::min(CHZ_WAVES, n_follow_tiles / std::max(1u, z->n_cus)));
-    z->scan_wpt = 1;   // the rest of the workgroup's 8 waves share the tiles' outputs
-    while (2 * z->scan_wpt * z->scan_waves <= CHZ_WAVES) z->scan_wpt *= 2;
-    for (const ChzWg &r : runs)
-        for (uint32_t t = 0; t < r.n_tiles; t += z->scan_waves)
-            z->swgs.push_back(ChzWg{r.source, r.first_tile + t, std::min(z->scan_waves, r.n_tiles - t), 0});
+        if (f == 0) z->n_fixed_tiles = (uint32_t)z->tiles.size();
+        if (f == 1) z->n_packed_tiles = (uint32_t)z->tiles.size();
+    }
+    chz_walker_wgs(z, runs[1], z->gwgs, z->gain_waves, z->gain_wpt);
+    chz_walker_wgs(z, runs[2], z->swgs, z->scan_waves, z->scan_wpt);
     z->amat.assign(z->tiles.size() * z->q * z->nq * 2 * 64 * 16, 0);
     if (z->fmt == IQD_WIDE_S16) z->gsum.assign(z->tiles.size(), ChzFmtTile{});
     std::fill(z->ch_dirty.begin(), z->ch_dirty.end(), 1);
@@ -236,7 +251,7 @@ static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
     const uint32_t c = t.ch[l];
     t.inc[l] = c == CHZ_NONE ? 0 : z->inc[c];
     t.shift[l] = c == CHZ_NONE ? 0 : z->shift[c];
-    if (tile >= z->n_fixed_tiles) return;   // a following channel: the walker builds its operands itself, per block
+    if (tile >= z->n_packed_tiles) return;   // a scanner-following channel: the walker builds its operands itself, per block
     const size_t taps = c == CHZ_NONE ? 0 : (size_t)c * z->q * z->kb;
     chz_pack_rows(z, z->amat.data(), tile, l, c == CHZ_NONE ? nullptr : &z->gr[taps], c == CHZ_NONE ? nullptr : &z->gi[taps]);
     if (z->fmt == IQD_WIDE_S16) {   // the sums of rows 2 l (gr on I, -gi on Q) and 2 l + 1 (gi on I, gr on Q); |sum| < 2^25
@@ -274,10 +289,11 @@ static int chz_upload(iqd_channelizer *z)
         if (z->fmt == IQD_WIDE_S16) CHZ_TRY(z, z->d_gsum.ensure(std::max<size_t>(1, n_tiles) * sizeof(ChzFmtTile)));
         CHZ_TRY(z, z->d_wgs.ensure(std::max<size_t>(1, z->wgs.size()) * sizeof(ChzWg)));
         CHZ_TRY(z, z->d_swgs.ensure(std::max<size_t>(1, z->swgs.size()) * sizeof(ChzWg)));
+        CHZ_TRY(z, z->d_gwgs.ensure(std::max<size_t>(1, z->gwgs.size()) * sizeof(ChzWg)));
     }
     struct Run { size_t first, n; };
     std::vector<Run> runs;
-    size_t bytes = regroup ? (z->wgs.size() + z->swgs.size()) * sizeof(ChzWg) : 0;
+    size_t bytes = regroup ? (z->wgs.size() + z->swgs.size() + z->gwgs.size()) * sizeof(ChzWg) : 0;
     for (size_t t = 0; t < n_tiles; t++) {
         if (!tile_dirty[t]) continue;
         if (!runs.empty() && runs.back().first + runs.back().n == t) runs.back().n++;
@@ -295,7 +311,7 @@ static int chz_upload(iqd_channelizer *z)
         return e;
     };
     for (const Run &r : runs) {
-        const size_t na = r.first < z->n_fixed_tiles ? std::min<size_t>(r.n, z->n_fixed_tiles - r.first) : 0;
+        const size_t na = r.first < z->n_packed_tiles ? std::min<size_t>(r.n, z->n_packed_tiles - r.first) : 0;
         if (na) CHZ_TRY(z, copy(z->d_amat.as<uint8_t>() + r.first * tile_bytes, &z->amat[r.first * tile_bytes], na * tile_bytes));
         CHZ_TRY(z, copy(z->d_tiles.as<ChzTile>() + r.first, &z->tiles[r.first], r.n * sizeof(ChzTile)));
         if (z->fmt == IQD_WIDE_S16)
@@ -303,6 +319,7 @@ static int chz_upload(iqd_channelizer *z)
     }
     if (regroup && !z->wgs.empty()) CHZ_TRY(z, copy(z->d_wgs.p, z->wgs.data(), z->wgs.size() * sizeof(ChzWg)));
     if (regroup && !z->swgs.empty()) CHZ_TRY(z, copy(z->d_swgs.p, z->swgs.data(), z->swgs.size() * sizeof(ChzWg)));
+    if (regroup && !z->gwgs.empty()) CHZ_TRY(z, copy(z->d_gwgs.p, z->gwgs.data(), z->gwgs.size() * sizeof(ChzWg)));
     CHZ_TRY(z, hipEventRecord(st.done, z->stream));
     st.pending = true;
     z->stg_cur ^= 1;
@@ -441,6 +458,7 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
     z->inc.assign(z->n_ch, 0);
     z->shift.assign(z->n_ch, 0);
     z->follow.assign(z->n_ch, 0);
+    z->follow_gain.assign(z->n_ch, 0);
     z->centre.assign(z->n_src, 0);
     {
         int cus = 0;
@@ -531,7 +549,8 @@ static uint32_t chz_t_max(const iqd_channelizer *z)
     return std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - z->kp) / z->m) / CHZ_GROUP * CHZ_GROUP;
 }
 
-// Queues one call: chz_kernel for the fixed channels, the walker for the following ones (scan != NULL), the history.
+// Queues one call: chz_kernel for the fixed channels, the walkers for the following ones (scan != NULL; gain: its
+// engine state and blocks are scan's), the history.
 static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_source, void *out_dev, ChzScanLaunch *scan)
 {
     (void)hipSetDevice(z->device);
@@ -561,7 +580,7 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
     a.den = z->q;
     a.t_blk = n_out <= t_max ? n_out : t_max;
     if (scan) {
-        if (z->centre_dirty) {
+        if (z->centre_dirty && z->n_follow) {   // (the scan walker's; the gain walker does not read them)
             CHZ_TRY(z, hipMemcpyAsync(z->d_centre.p, z->centre.data(), (size_t)z->n_src * 8, hipMemcpyHostToDevice, z->stream));
             CHZ_TRY(z, hipStreamSynchronize(z->stream));   // (the host vector may change once this returns)
             z->centre_dirty = false;
@@ -580,6 +599,21 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
         f.pstride = 2 * (a.t_blk * a.m + a.kp) + 16;
         CHZ_TRY(z, launch_channelizer_fmt(f, (uint32_t)z->wgs.size(), z->stream));
     } else {
+        if (scan && !z->gwgs.empty()) {   // before launch_channelizer: its history kernel comes last
+            ChzGainLaunch g{};
+            g.agc_cfg = scan->agc_cfg;
+            g.agc = scan->agc;
+            g.consts = scan->consts;
+            g.first_ch = scan->first_ch;
+            g.block_out = scan->block_out;
+            g.n_blocks = scan->n_blocks;
+            g.t_blk = scan->t_blk;
+            g.waves = z->gain_waves;
+            g.wpt = z->gain_wpt;
+            ChzLaunch b = a;
+            b.wgs = z->d_gwgs.as<ChzWg>();
+            CHZ_TRY(z, launch_channelizer_gain(b, (uint32_t)z->gwgs.size(), g, z->stream));
+        }
         CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->d_swgs.as<ChzWg>(), scan ? (uint32_t)z->swgs.size() : 0u, scan, z->stream));
     }
     z->cur ^= 1;
@@ -593,6 +627,7 @@ int iqd_channelizer_run_device(iqd_channelizer_t *z, const void *wide_dev, size_
     if (!wide_dev || !out_dev) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
     if ((((uintptr_t)wide_dev) | ((uintptr_t)out_dev)) & 15) return z->fail(IQD_EINVAL, "channelizer: buffers must be 16-byte aligned");
     if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: a channel follows its scanner; use iqd_accept_wideband*");
+    if (z->n_gain) return z->fail(IQD_EINVAL, "channelizer: a channel follows its gain; use iqd_accept_wideband*");
     int rc = chz_check_len(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     return chz_queue(z, wide_dev, bytes_per_source, out_dev, nullptr);
@@ -603,6 +638,7 @@ int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_
     if (!z) return IQD_EINVAL;
     if (!wide || !out) return z->fail(IQD_EINVAL, "channelizer: NULL buffer");
     if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: a channel follows its scanner; use iqd_accept_wideband*");
+    if (z->n_gain) return z->fail(IQD_EINVAL, "channelizer: a channel follows its gain; use iqd_accept_wideband*");
     int rc = chz_check_len(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(z->device);
@@ -676,6 +712,7 @@ static int chz_survey_check(iqd_channelizer *z, size_t bytes_per_source, uint32_
 {
     if (z->sv_inc.empty()) return z->fail(IQD_EINVAL, "channelizer: no survey points set");
     if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: no survey while a channel follows its scanner");
+    if (z->n_gain) return z->fail(IQD_EINVAL, "channelizer: no survey while a channel follows its gain");
     int rc = chz_check_len(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     const uint32_t unit = z->q > 1 ? 256 : 64;
@@ -782,7 +819,7 @@ static int wideband_queue(iqd_t *e, iqd_channelizer *z, uint32_t first_ch, const
         return z->fail(IQD_EINVAL, "accept_wideband: bytes_per_source / decimation must be a multiple of block_bytes, or one short block");
     const size_t nblk = row % bb == 0 ? row / bb : 1;
     (void)hipSetDevice(z->device);
-    if (z->n_follow) {
+    if (z->n_follow || z->n_gain) {
         ChzScanLaunch sl{};
         rc = engine_settle(e, &sl);
         if (rc != IQD_OK) return rc;
@@ -866,11 +903,36 @@ int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_
                                                           : "channelizer: channels on IQD_WIDE_S8 captures cannot follow a scanner yet");
     if (follow && z->q > 1)
         return z->fail(IQD_EINVAL, "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow a scanner");
+    for (uint32_t i = 0; follow && i < n; i++)
+        if (z->follow_gain[first + i])
+            return z->fail(IQD_EINVAL, "channelizer: a channel that follows its gain cannot follow its scanner as well (not built yet)");
     for (uint32_t i = 0; i < n; i++) {
         uint8_t &f = z->follow[first + i];
         if (f == (follow ? 1 : 0)) continue;
         f = follow ? 1 : 0;
         z->n_follow += follow ? 1 : -1;
+        z->layout_dirty = true;
+    }
+    return IQD_OK;
+}
+
+int iqd_channelizer_follow_gain(iqd_channelizer_t *z, uint32_t first, uint32_t n, int follow)
+{
+    if (!z) return IQD_EINVAL;
+    if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
+    if (follow && z->fmt != IQD_WIDE_U8)
+        return z->fail(IQD_EINVAL, z->fmt == IQD_WIDE_S16 ? "channelizer: channels on IQD_WIDE_S16 captures cannot follow their gain yet"
+                                                          : "channelizer: channels on IQD_WIDE_S8 captures cannot follow their gain yet");
+    if (follow && z->q > 1)
+        return z->fail(IQD_EINVAL, "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow their gain yet");
+    for (uint32_t i = 0; follow && i < n; i++)
+        if (z->follow[first + i])
+            return z->fail(IQD_EINVAL, "channelizer: a channel that follows its scanner cannot follow its gain as well (not built yet)");
+    for (uint32_t i = 0; i < n; i++) {
+        uint8_t &f = z->follow_gain[first + i];
+        if (f == (follow ? 1 : 0)) continue;
+        f = follow ? 1 : 0;
+        z->n_gain += follow ? 1 : -1;
         z->layout_dirty = true;
     }
     return IQD_OK;

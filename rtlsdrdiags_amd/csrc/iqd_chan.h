@@ -80,6 +80,22 @@ struct ChzScanLaunch {
     uint32_t wpt;                          // waves per tile (waves * wpt <= CHZ_WAVES)
 };
 
+// What the gain walker (chz_gain_kernel, iqd_chan_gain.hip) reads besides ChzLaunch: a.wgs are its own workgroups (tiles of
+// gain-following channels only, their A operands host-packed like the fixed ones); the engine's AGC state is read, never
+// written (the walker steps a shadow copy).
+struct ChzGainShadow { AgcConfig cfg; AgcState st; };
+constexpr uint32_t CHZ_GAIN_SHADOW = CHZ_WAVES * CHZ_TILE_CH * (uint32_t)sizeof(ChzGainShadow);   // the walker's shadows in LDS
+struct ChzGainLaunch {
+    const AgcConfig *agc_cfg;              // the engine's state, [engine ch]
+    const AgcState *agc;
+    const Consts *consts;                  // the engine's constant tables (dB table)
+    uint32_t first_ch;                     // engine channel of channelizer channel 0
+    uint32_t block_out, n_blocks;          // outputs per block, blocks in this call
+    uint32_t t_blk;                        // outputs per window (a multiple of 64, or the whole short block)
+    uint32_t waves;                        // tiles per workgroup
+    uint32_t wpt;                          // waves per tile (waves * wpt <= CHZ_WAVES)
+};
+
 // The band survey (chz_survey_kernel, iqd_chan_survey.hip) beside ChzLaunch: a.tiles / a.amat are the survey's point tiles
 // (ChzTile::ch is the point index), shared by all sources; a.wgs and a.out are unused.  Workgroup x of the grid is
 // (source, window, row of CHZ_WAVES point tiles) = (x / (n_win rows), x / rows % n_win, x % rows).
@@ -137,6 +153,9 @@ hipError_t launch_channelizer_survey(const ChzLaunch &a, const ChzSurveyLaunch &
 
 // chz_fmt_kernel for f.rail_bytes = 1, 2 and its history kernel (iqd_chan_fmt.hip)
 hipError_t launch_channelizer_fmt(const ChzFmtLaunch &f, uint32_t n_wgs, hipStream_t st);
+
+// chz_gain_kernel alone: n_wgs workgroups a.wgs of gain-following tiles, one launch whatever g.n_blocks (iqd_chan_gain.hip)
+hipError_t launch_channelizer_gain(const ChzLaunch &a, uint32_t n_wgs, const ChzGainLaunch &g, hipStream_t st);
 
 // host-only spec pieces (iqd_chan.cpp)
 void chz_phasor_table(int16_t *out /* [8192] (c, s) pairs */);

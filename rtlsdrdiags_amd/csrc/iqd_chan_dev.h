@@ -55,6 +55,40 @@ __device__ __forceinline__ uint32_t chz_epilogue(int32_t rlo, int32_t rhi, int32
     return (uint32_t)(yr + 128) | ((uint32_t)(yi + 128) << 8);
 }
 
+// chz_epilogue up to the rotation (chz_gain_kernel, iqd_chan_gain.hip): stage a and rr = ar c + ai s, ri = ai c - ar s,
+// |rr|, |ri| < 2^31
+__device__ __forceinline__ void chz_epilogue_rot(int32_t rlo, int32_t rhi, int32_t ilo, int32_t ihi, uint32_t p, int32_t &rr,
+                                                 int32_t &ri)
+{
+    const int32_t Ar = (int32_t)((uint32_t)rlo + ((uint32_t)rhi << 8) + 128u);
+    const int32_t Ai = (int32_t)((uint32_t)ilo + ((uint32_t)ihi << 8) + 128u);
+    const int32_t ar = chz_sat(Ar >> 8, -32768, 32767);
+    const int32_t ai = chz_sat(Ai >> 8, -32768, 32767);
+    const int32_t c = (int16_t)(p & 0xffffu), s = (int16_t)(p >> 16);
+    const chz_s2 va = {(short)ar, (short)ai};
+    const chz_s2 vb = {(short)ai, (short)ar};
+    const chz_s2 cs = {(short)c, (short)s};
+    const chz_s2 cns = {(short)c, (short)-s};
+    rr = __builtin_amdgcn_sdot2(va, cs, 0, false);
+    ri = __builtin_amdgcn_sdot2(vb, cns, 0, false);
+}
+
+// The gain in dB as the last step (include/iqdemod.h: "Gain-following channels"): g = 6 e + j, m_j = lrint(4096 2^(j/6)).
+// Mantissa and exponent of one gain as one word, (m_j << 4) | e; g <= 48, so e <= 8.
+__host__ __device__ __forceinline__ uint32_t chz_gain_split(uint32_t g)
+{
+    const uint32_t e = g / 6, j = g - 6 * e;
+    const uint32_t m = j == 0 ? IQD_GAIN_M0 : j == 1 ? IQD_GAIN_M1 : j == 2 ? IQD_GAIN_M2 : j == 3 ? IQD_GAIN_M3
+                     : j == 4 ? IQD_GAIN_M4 : IQD_GAIN_M5;
+    return (m << 4) | e;
+}
+// One rail: t = floor(r m_j / 2^14) as the high word of r (m_j 2^18) (m_j 2^18 < 2^31, |t| < 2^30), then
+// y = sat8((t + 2^(19 - e)) >> (20 - e)) with rnd = 2^(19 - e), sh = 20 - e
+__device__ __forceinline__ int32_t chz_gain_rail(int32_t r, int32_t m18, int32_t rnd, uint32_t sh)
+{
+    return chz_sat((__mulhi(r, m18) + rnd) >> sh, -128, 127);
+}
+
 // Every thread of the workgroup: the window of outputs [m0, m0 + nloc) of one source - bytes [2 M m0 - 2 Kp, 2 M (m0 +
 // nloc)) of [history | this call], made signed - into LDS.
 __device__ __forceinline__ void chz_stage_window(const ChzLaunch &a, uint32_t source, uint32_t m0, uint32_t nloc, uint8_t *win)

@@ -8,6 +8,7 @@
 //                out=pcm_%d.s16 [blocks=K] [rotation=<r>] [centre=<Hz>] [scan=<start>,<end>,<step>[,...]]
 //                [squelch=<dBFS>[,<dBFS>...]] [freqlog=<file>]
 //                [survey=<first_offset_Hz>,<step_Hz>,<count> [surveyshift=<L>] surveylog=<file>] [format=u8|s8|s16]
+//                [agc=off|lowpass|harris[,...]] [rxgain=<dB>[,<dB>...]] [gainlog=<file>]
 //
 //   format     what the capture holds: u8 offset binary (an RTL-SDR; the default), s8 signed int8 (hackrf_transfer), s16
 //              little-endian signed int16 (SDRplay, Airspy, USRP, SDR++ / SDR# / SDRangel basebands).  s8 and s16 are for
@@ -28,6 +29,14 @@
 //   squelch    per channel the squelch threshold, dBFS, the list repeating (default: the engine's)
 //   freqlog    one line per block and channel: block (from 0, over the whole capture), channel, the station frequency
 //              the block was cut at (a fixed channel: centre + offset - 64000 rotation), 1 if the squelch let it through
+//   agc        per channel its AutomaticGainControl, the list repeating: off (the default), lowpass or harris.  A channel
+//              with a running AGC follows its gain (iqd_channelizer_follow_gain): the channelizer applies the channel's IF
+//              gain in dB to every block in place of gains=, so the AGC levels the channel.
+//   rxgain     per channel the IF gain in dB (iqd_set_rx_gain_db), the list repeating; every channel then follows its gain
+//              (with agc=off it is the channel's manual gain).  agc= and rxgain= are for a u8 capture at an integer
+//              decimation and not together with scan=.
+//   gainlog    one line per block and channel: block (from 0, over the whole capture), channel, the gain in dB the block
+//              was cut with (a channel that does not follow its gain: 6 L)
 //   survey     a grid of count offsets first, first + step, ... (the increments as for offsets; count <= 4096): every
 //              accept is surveyed before it is run (iqd_channelizer_survey, one block per 32768-byte engine block, the
 //              short block at the capture's end as one block - left out, with a notice, where its length is no admissible
@@ -77,13 +86,14 @@ std::vector<uint64_t> u64List(const char *s)
 
 int main(int argc, char **argv)
 {
-  std::string in, out, freqlog, surveylog;
+  std::string in, out, freqlog, surveylog, gainlog;
   uint32_t m = 0, den = 1, blocks = 4;
   bool m_given = false;
   double rate = 0;
   int rotation = 1;
   uint64_t centre = 0;
-  std::vector<double> offsets, modes, gains{0}, squelch;
+  std::vector<double> offsets, modes, gains{0}, squelch, rxgain;
+  std::vector<std::string> agc;
   std::vector<uint64_t> scan;
   std::vector<double> survey;
   uint32_t surveyshift = 0;
@@ -112,6 +122,16 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "surveyshift=", 12)) surveyshift = (uint32_t)atoi(a + 12);
     else if (!strncmp(a, "surveylog=", 10)) surveylog = a + 10;
     else if (!strncmp(a, "format=", 7)) format = a + 7;
+    else if (!strncmp(a, "rxgain=", 7)) rxgain = numList(a + 7);
+    else if (!strncmp(a, "gainlog=", 8)) gainlog = a + 8;
+    else if (!strncmp(a, "agc=", 4)) {
+      for (const char *q = a + 4;;) {
+        const char *c = strchr(q, ',');
+        agc.push_back(c ? std::string(q, c) : std::string(q));
+        if (!c) break;
+        q = c + 1;
+      }
+    }
     else {
       fprintf(stderr, "iqdemod_wide: unknown argument %s\n", a);
       return 1;
@@ -141,6 +161,19 @@ int main(int argc, char **argv)
             !survey.empty() ? "survey=" : !scan.empty() ? "scan=" : "a fractional rate");
     return 1;
   }
+  bool gain_following = !rxgain.empty();
+  for (const std::string &t : agc) {
+    if (t != "off" && t != "lowpass" && t != "harris") {
+      fprintf(stderr, "iqdemod_wide: agc must be off, lowpass or harris\n");
+      return 1;
+    }
+    gain_following = gain_following || t != "off";
+  }
+  if (gain_following && (!scan.empty() || den > 1 || sample_format != IQD_WIDE_U8)) {
+    fprintf(stderr, "iqdemod_wide: agc= / rxgain= cannot be combined with %s: channels that follow their gain are not built for it yet\n",
+            !scan.empty() ? "scan=" : den > 1 ? "a fractional rate" : "format=s8|s16");
+    return 1;
+  }
   const bool surveying = !survey.empty();
   const bool survey_ok = !surveying || (survey.size() == 3 && survey[2] >= 1 && survey[2] <= 4096 && surveyshift <= 8 && !surveylog.empty());
   const bool demod_ok = !offsets.empty() ? !out.empty() && !modes.empty() : surveying;
@@ -151,7 +184,8 @@ int main(int argc, char **argv)
   if (in.empty() || !demod_ok || !survey_ok || m < 2 || den < 1 || rate <= 0 || gains.empty() || !blocks || scan.size() % 3 != 0) {
     fprintf(stderr, "usage: iqdemod_wide in=cap.iq [decimation=8|75/8] rate=2048000 offsets=<Hz,...> modes=<m,...> "
                     "[gains=<L,...>] out=pcm_%%d.s16 [blocks=K] [rotation=r] [centre=Hz] [scan=start,end,step,...] "
-                    "[squelch=dBFS,...] [freqlog=file] [survey=first_Hz,step_Hz,count [surveyshift=L] surveylog=file] [format=u8|s8|s16]\n");
+                    "[squelch=dBFS,...] [freqlog=file] [survey=first_Hz,step_Hz,count [surveyshift=L] surveylog=file] [format=u8|s8|s16] "
+                    "[agc=off|lowpass|harris,...] [rxgain=dB,...] [gainlog=file]\n");
     return 1;
   }
   const uint32_t n = (uint32_t)offsets.size();   // 0: survey only
@@ -205,6 +239,12 @@ int main(int argc, char **argv)
     return 1;
   }
 
+  FILE *glog = nullptr;
+  if (!gainlog.empty() && !(glog = fopen(gainlog.c_str(), "w"))) {
+    fprintf(stderr, "iqdemod_wide: cannot create %s\n", gainlog.c_str());
+    return 1;
+  }
+
   iqd_config cfg{};
   cfg.abi_version = IQD_ABI_VERSION;
   cfg.n_channels = n ? n : 1;
@@ -240,6 +280,18 @@ int main(int argc, char **argv)
     if (rc == IQD_OK) rc = iqd_channelizer_follow_scanner(z, c, 1, 1);
     follows[c] = 1;
   }
+  // channels that follow their gain: a running AGC, or a gain in dB of their own
+  std::vector<uint8_t> follows_gain(n, 0);
+  for (uint32_t c = 0; c < n && rc == IQD_OK; c++) {
+    const std::string t = agc.empty() ? "off" : agc[c % agc.size()];
+    if (!rxgain.empty()) rc = iqd_set_rx_gain_db(e, c, 1, (uint32_t)rxgain[c % rxgain.size()]);
+    if (rc == IQD_OK && t != "off") rc = iqd_agc_set_type(e, c, 1, t == "harris" ? IQD_AGC_HARRIS : IQD_AGC_LOWPASS);
+    if (rc == IQD_OK && t != "off") rc = iqd_agc_enable(e, c, 1, 1);
+    follows_gain[c] = t != "off" || !rxgain.empty();
+    if (rc == IQD_OK && follows_gain[c]) rc = iqd_channelizer_follow_gain(z, c, 1, 1);
+  }
+  if (rc == IQD_OK && glog) rc = iqd_set_gain_trace(e, 1);
+  std::vector<uint32_t> gtrace;
   // the frequency each channel's next block is cut at: the scanner's (its start() jump applied), or the fixed one
   std::vector<uint64_t> cut(n), trace;
   if (rc == IQD_OK && flog) rc = iqd_set_gain_trace(e, 1);
@@ -298,6 +350,10 @@ int main(int argc, char **argv)
       trace.resize((size_t)n * nblk);
       r = iqd_get_frequency_trace(e, 0, n, trace.data(), nblk);
     }
+    if (r == IQD_OK && glog) {
+      gtrace.resize((size_t)n * nblk);
+      r = iqd_get_gain_trace(e, 0, n, gtrace.data(), nblk);
+    }
     if (r != IQD_OK) {
       fprintf(stderr, "iqdemod_wide: accept: %s (%s)\n", iqd_strerror(r), iqd_last_error(e));
       status = 3;
@@ -315,6 +371,12 @@ int main(int argc, char **argv)
                 (unsigned)open[(size_t)c * nblk + b]);
         if (follows[c]) cut[c] = trace[(size_t)c * nblk + b];   // the frequency after this block's scanner step
       }
+    for (size_t b = 0; glog && b < nblk; b++)
+      for (uint32_t c = 0; c < n; c++) {
+        const uint32_t g = gtrace[(size_t)c * nblk + b];
+        fprintf(glog, "%llu %u %u\n", (unsigned long long)(block_no + b), c,
+                follows_gain[c] ? (g < IQD_GAIN_FOLLOW_MAX ? g : (uint32_t)IQD_GAIN_FOLLOW_MAX) : 6u * shift[c]);
+      }
     block_no += nblk;
     return true;
   };
@@ -331,6 +393,7 @@ int main(int argc, char **argv)
   fclose(f);
   if (flog) fclose(flog);
   if (slog) fclose(slog);
+  if (glog) fclose(glog);
   for (FILE *s : sinks) fclose(s);
   iqd_channelizer_destroy(z);
   iqd_destroy(e);

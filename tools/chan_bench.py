@@ -7,6 +7,7 @@ per channel and call, M = 8, default taps.  Prints one JSON line:
     python tools/chan_bench.py --format s16            (a signed 16-bit capture, or s8: chz_fmt_kernel; same outputs)
     python tools/chan_bench.py --scan [--steps K]      (scanner-driven channels, written to profiles/ as well)
     python tools/chan_bench.py --survey [--decimation 75 --den 8]   (the band survey against rows of real channels)
+    python tools/chan_bench.py --gain [--steps K]      (channels that follow their AGC's IF gain)
 
   chan_ms            per call, host clock around iqd_channelizer_run_device + synchronize (median of K steps, after
                      about --settle-ms of the same call untimed, like bench.py's clock settle)
@@ -21,6 +22,10 @@ rows_accept_ms, an estimate of the walker's share (the two are timed in separate
 comes from a kernel trace of this run: rocprofv3 --kernel-trace (profiles/chan_scan_kernel_trace.json).  The same for 16
 following channels (one source), and host_loop_ms: today's host-driven loop for those 16 - one-block calls of
 iqd_channelizer_run + iqd_accept_iq with iqd_scanner_get + iqd_channelizer_tuning before each block.
+
+--gain: every channel follows its gain (iqd_channelizer_follow_gain), FM with a running Harris AGC; each call is 4 blocks
+(block_bytes 32768), the same size as --scan's.  gain_call_ms: iqd_accept_wideband_device + synchronize; fixed_call_ms:
+the same call with the channels fixed (chz_kernel, AGC running open loop); rows_accept_ms and walker_ms as for --scan.
 
 --survey: 16 sources, 2^16 outputs each, a 12.5 kHz grid of 163 points per source (2608 virtual channels), block_bytes
 32768.  survey_ms: iqd_channelizer_survey_device + synchronize; grid_run_ms: iqd_channelizer_run_device for 2608 real
@@ -59,6 +64,7 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=100.0)
     ap.add_argument("--chan-only", action="store_true", help="only the channelizer calls (counter runs)")
     ap.add_argument("--scan", action="store_true", help="scanner-driven channels (see above)")
+    ap.add_argument("--gain", action="store_true", help="gain-following channels (see above)")
     ap.add_argument("--survey", action="store_true", help="the band survey against run_device on the same grid (see above)")
     ap.add_argument("--grid-only", action="store_true", help="with --survey: only grid_run_ms (a build without the survey)")
     ap.add_argument("--decimation", type=int, default=8, help="M, or P of a fractional decimation P / Q")
@@ -70,6 +76,8 @@ def main():
         return scan_bench(capi, args)
     if args.survey:
         return survey_bench(capi, args)
+    if args.gain:
+        return gain_bench(capi, args)
 
     M, Q, n_src, n_ch, n_out = args.decimation, args.den, 16, 4096, 1 << 16
     B = 2 if args.format == "s16" else 1               # bytes per rail (white bytes are full-scale in every format)
@@ -213,6 +221,45 @@ def scan_bench(capi, args):
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "chan_scan_bench.json"), "w") as f:
         f.write(json.dumps(line) + "\n")
+
+
+def _gain_setup(capi, n_ch, n_src, M, n_out, follow=True):
+    from rtlsdrdiags_amd import synth
+    bps = n_out * 2 * M
+    row = bps // M
+    eng = capi.Engine(n_ch)
+    eng.set_mode("fm")
+    eng.set_squelch(-40)
+    eng.agc_set_type(1)
+    eng.agc_enable(True)
+    rng = np.random.default_rng(1)
+    z = capi.Channelizer(eng, M, n_ch, n_src)
+    z.set_channels(0, source=np.arange(n_ch) % n_src, phase_inc=rng.integers(0, 2 ** 32, n_ch, dtype=np.uint64),
+                   gain_shift=np.full(n_ch, 3))
+    if follow:
+        z.follow_gain(True)
+    d_in, d_rows = eng.dev_alloc(n_src * bps), eng.dev_alloc(n_ch * row)
+    d_pcm, d_cnt = eng.dev_alloc(n_ch * row // 64 * 2), eng.dev_alloc(n_ch * 4)
+    eng.dev_upload(d_in, np.concatenate([synth.white_u8(bps // 2, seed=s) for s in range(n_src)]))
+    call = lambda: eng.accept_wideband_device(z, d_in, bps, d_rows, d_pcm, d_cnt)
+    rows = lambda: eng.accept_device(d_rows, row, d_pcm, d_cnt)
+    return eng, z, call, rows
+
+
+def gain_bench(capi, args):
+    M, n_out, n_ch, n_src = 8, 1 << 16, 4096, 16
+    line = {"workload": "gain-following channelizer, 4096 ch / 16 sources / M=8 / default taps / 2^16 outputs (4 blocks) per "
+                        "call / FM + Harris AGC"}
+    eng, z, call, rows = _gain_setup(capi, n_ch, n_src, M, n_out)
+    gain_ms, _ = timed(call, eng.synchronize, args.steps, args.settle_ms)
+    rows_ms, _ = timed(rows, eng.synchronize, args.steps, args.settle_ms)
+    z.close(); eng.close()
+    eng, z, call, _ = _gain_setup(capi, n_ch, n_src, M, n_out, follow=False)
+    fixed_ms, _ = timed(call, eng.synchronize, args.steps, args.settle_ms)
+    z.close(); eng.close()
+    line.update(gain_call_ms=round(gain_ms, 4), rows_accept_ms=round(rows_ms, 4), walker_ms=round(gain_ms - rows_ms, 4),
+                fixed_call_ms=round(fixed_ms, 4))
+    print(json.dumps(line))
 
 
 if __name__ == "__main__":

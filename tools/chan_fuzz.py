@@ -14,6 +14,10 @@ About one case in ten is a survey case (FUZZ_SURVEY=1: every case, FUZZ_SURVEY=0
 a band survey (iqd_channelizer_survey*, against tests/chan_survey_model.py) drawn before some of its calls, each followed by
 the call itself, so that a survey that moved the channelizer's state shows in the rows.
 
+Gain cases (channels that follow their engine channel's IF gain, iqd_channelizer_follow_gain, against
+tests/chan_gain_model.py on oracle chains) are drawn only when asked: FUZZ_GAIN=1 makes every case one, and nothing else
+draws them, so that a seed without it is the cases it always was.
+
 A plain case is drawn without a GPU (draw_plain) and then run (run_plain), so that a CPU test can hold the fixed slices
 of tests/test_gpu_chan_fuzz.py to the mutants of tests/chan_mutants.py before they go to the GPU (first_channel_kills)."""
 import json
@@ -25,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np                                     # noqa: E402
 from rtlsdrdiags_amd import capi, synth                # noqa: E402
 from tests import chan_frac_model as fm                # noqa: E402
+from tests import chan_gain_model as gm                # noqa: E402
 from tests import chan_model as cm                     # noqa: E402
 from tests import chan_mutants as mu                   # noqa: E402
 from tests import chan_scan_model as sm                # noqa: E402
@@ -34,7 +39,8 @@ K_EDGES = (1, 31, 32, 33, 255, 256, 257, 1023, 1024)
 INC_EDGES = (0, 1, 2 ** 31, 2 ** 31 - 1, 2 ** 32 - 1)
 BOUND_SUM = (2 ** 31 - 256) // 256
 SLICES = {"plain": ((9101, 150), (9102, 150)), "scan": (9103, 40),   # (seed, cases): tests/test_gpu_chan_fuzz.py's
-          "survey": (9104, 40)}                                       # tests/test_gpu_chan_survey_fuzz.py's
+          "survey": (9104, 40),                                       # tests/test_gpu_chan_survey_fuzz.py's
+          "gain": (9105, 24)}                                         # tests/test_gpu_chan_gain_fuzz.py's
 MODEL_BUDGET = 4e7        # tap x wideband-sample products the model may spend per case (chan_model convolves at the
 #                           wide rate: K M outputs per channel); fewer channels are compared when a case is past it
 
@@ -633,6 +639,126 @@ def scan_case(rng, ctx):
     return run_scan(ctx, M, taps, h, n_src, n_ch, bb, calls, rng, check=check)
 
 
+# ------------------------------------------------------------------------------------------------------ gain cases
+def gain_case(rng, ctx):
+    """Gain-following and fixed channels of one channelizer through iqd_accept_wideband_device, against
+    chan_gain_model.follow on oracle chains: engine blocks of 256 ... 32768 bytes, per channel an AGC (either type, or
+    off) with its operating point, deadband and blanking limit drawn, manual gains 0 ... 60 set between calls and the
+    following flag toggled.  None, or what differed."""
+    P = ctx.P
+    M = int(rng.integers(2, 65))
+    if rng.random() < 0.6:
+        taps, h = None, capi.channelizer_default_taps(M)
+    else:
+        K = int(rng.choice(K_EDGES)) if rng.random() < 0.5 else int(rng.integers(1, 1025))
+        hh = np.abs(np.sinc((np.arange(K) - (K - 1) / 2) / max(2.0, M)))
+        taps = h = np.clip(np.rint(hh / hh.sum() * 32768 * rng.uniform(0.3, 1.0) * rng.choice([-1, 1], K)), -32639, 32639).astype(np.int16)
+    cap = int(min(32768, max(128, 1e8 // (len(h) * M))))     # outputs per call the model can afford (it convolves at the wide rate)
+    bb = int(rng.choice([b for b in (256, 1024, 2560, 4096, 32768) if b // 2 <= cap]))
+    bo, fs = bb // 2, 256000 * M
+    n_ch = int(rng.choice([1, 3, 8, 9, 17]))
+    n_src = int(rng.integers(1, 4))
+    per = max(1, min(6, cap // bo))
+    calls = [0 if rng.random() < 0.25 else int(rng.integers(1, per + 1)) for _ in range(int(rng.integers(1, 5)))]
+    outs = [k * bo if k else 32 * int(rng.integers(1, max(2, bo // 32))) for k in calls]
+    total = sum(outs)
+    n_check = max(1, min(n_ch, int(MODEL_BUDGET // 2 // (4.0 * len(h) * M * max(32, total)))))
+    check = sorted(set([0] + rng.choice(n_ch, n_check, replace=False).tolist()))
+    src = rng.integers(0, n_src, n_ch).astype(np.uint32)
+    fracs = rng.uniform(-0.45, 0.45, 4)
+    stations = [{"offset": float(f) * fs, "kind": "fm", "amplitude": float(2.0 ** rng.uniform(0, 6.3))} for f in fracs[:3]]
+    wide = np.stack([synth.wideband(total * M, fs, stations, seed=int(rng.integers(1 << 30)), sigma=float(rng.choice([0.3, 1.0, 4.0])))
+                     if rng.random() < 0.8 else draw_input(rng, M, total * M)[1] for _ in range(n_src)])
+    inc = np.array([capi.phase_inc(float(rng.choice(fracs)) * fs, fs) if rng.random() < 0.7 else draw_inc(rng) for _ in range(n_ch)],
+                   np.uint64)
+    shift = rng.integers(0, 9, n_ch).astype(np.uint8)
+    follow = rng.random(n_ch) < 0.75
+    follow[0] = True
+    eng = capi.Engine(n_ch, block_bytes=bb)
+    eng.set_gain_trace(True)
+    chains = {c: ctx.oracle.chain() for c in check}
+    setup = []
+    for c in range(n_ch):
+        th = int(rng.choice([-200, -60, -45, -30]))
+        agc = int(rng.integers(0, 2)) if rng.random() < 0.7 else None
+        op, dead, blank = int(rng.integers(-24, -3)), int(rng.integers(0, 4)), int(rng.integers(0, 4))
+        g0 = int(rng.integers(0, 61 if agc is None else 47))   # (a running AGC holds the gain within 0 ... 46)
+        setup.append([th, agc, op, dead, blank, g0])
+        for t in [eng] + ([chains[c]] if c in chains else []):
+            a = (c, 1) if t is eng else ()
+            t.set_mode("fm", *a)
+            t.set_squelch(th, *a)
+            t.set_rx_gain_db(g0, *a)
+            t.agc_set_operating_point(op, *a)
+            t.agc_set_deadband(dead, *a)
+            t.agc_set_blanking_limit(blank, *a)
+            if agc is not None:
+                t.agc_set_type(agc, *a)
+                t.agc_enable(True, *a)
+    z = capi.Channelizer(eng, M, n_ch, n_src, taps=taps)
+    z.set_channels(0, source=src, phase_inc=inc, gain_shift=shift)
+    for c in np.flatnonzero(follow):
+        z.follow_gain(True, int(c), 1)
+    log, bad, m_at = [], None, 0
+    for i, n_out in enumerate(outs):
+        if i and rng.random() < 0.7:                       # between calls: follow toggled, or the operator's gain
+            c = int(rng.choice(check))
+            if rng.random() < 0.4:
+                follow[c] = not follow[c]
+                z.follow_gain(bool(follow[c]), c, 1)
+                log.append((i, c, "follow", bool(follow[c])))
+                ctx.count("follow toggles")
+            else:
+                g = int(rng.integers(0, 61 if setup[c][1] is None else 47))
+                eng.set_rx_gain_db(g, c, 1)
+                chains[c].set_rx_gain_db(g)
+                log.append((i, c, "gain", g))
+                ctx.count("manual gains")
+        nblk = calls[i] if calls[i] else 1
+        blk = n_out // nblk
+        piece = wide[:, 2 * M * m_at:2 * M * (m_at + n_out)]
+        rows, pcm, cnt, mag, alw = _dev_call(eng, z, piece, bb)
+        trace = eng.gain_trace(nblk)
+        for c in check:
+            s = int(src[c])
+            if follow[c]:
+                r, p, mg, al, tr = gm.follow(chains[c], wide[s], h, M, int(inc[c]), P, blk, nblk, m_first=m_at)
+                ctx.count("gain blocks", nblk)
+                ctx.count("gain changes", (np.diff(tr.astype(np.int64)) != 0).sum())
+                ctx.count("blocks above 46 dB", (tr > 46).sum())
+                ctx.count("short blocks", calls[i] == 0)
+            else:
+                tr = []
+                r = cm.channel(wide[s], h, M, int(inc[c]), int(shift[c]), P, m_range=(m_at, m_at + n_out))
+                p, mg, al = [], [], []
+                for b in range(nblk):                        # (block by block: the gain before each block is the trace's)
+                    tr.append(chains[c].rx_gain_db())
+                    pb, mb, ab = chains[c].accept_stream(r[2 * blk * b:2 * blk * (b + 1)], block_bytes=2 * blk)
+                    p.append(pb); mg.append(mb[0]); al.append(ab[0])
+                p, mg, al, tr = np.concatenate(p), np.array(mg), np.array(al), np.array(tr)
+            diff = ("rows" if not np.array_equal(rows[c], r) else
+                    "pcm" if cnt[c] != len(p) or not np.array_equal(pcm[c, :cnt[c]], p) else
+                    "magnitude" if not np.array_equal(mag[c], mg) else
+                    "allowed" if not np.array_equal(alw[c], al) else
+                    "gain trace" if not np.array_equal(trace[c], tr) else None)
+            if diff:
+                d = np.flatnonzero(rows[c] != r)
+                bad = ("gain case: M=%d K=%d (%s) sources=%d channels=%d block_bytes=%d calls(outputs)=%r: call %d, channel %d "
+                       "(source %d, following %s, threshold/agc/operating point/deadband/blanking/gain %r, inc 0x%08x, L %d) "
+                       "differs in %s%s; gains got %r model %r; ops %r" % (
+                           M, len(h), "default taps" if taps is None else "given taps", n_src, n_ch, bb, outs, i, c, s,
+                           bool(follow[c]), setup[c], inc[c], shift[c], diff,
+                           " (%d bytes, first at %d)" % (len(d), d[0]) if len(d) else "", trace[c].tolist(),
+                           np.asarray(tr).tolist(), log))
+                break
+        if bad:
+            break
+        m_at += n_out
+    z.close()
+    eng.close()
+    return bad
+
+
 def compute_units():
     """torch.cuda.get_device_properties(0).multi_processor_count, asked in a child process: torch brings its own HIP
     runtime, which finds no device in a process where the engine's has opened it first."""
@@ -667,8 +793,11 @@ def main():
     from oracle import bindings
     ctx = Context(bindings.Oracle())
     mode, fmode, smode = os.environ.get("FUZZ_SCAN"), os.environ.get("FUZZ_FRAC"), os.environ.get("FUZZ_SURVEY")
+    gmode = os.environ.get("FUZZ_GAIN") == "1"
 
     def one():
+        if gmode:                                          # (asked for: no draw decides it, the other kinds draw as ever)
+            return False, gain_case(rng, ctx)
         r = rng.random() if mode is None else 1.0
         scan = mode == "1" or (mode is None and r < 0.125)
         if scan:
