@@ -52,16 +52,21 @@ def samples(wide_row, fmt, defect=None):
     return (xi, xr) if defect == "iq_swap" else (xr, xi)
 
 
-def channelize(wide, fmt, h, M, sources, incs, shifts, P, defect=None, calls=None, stage_a=False):
+def channelize(wide, fmt, h, M, sources, incs, shifts, P, defect=None, calls=None, stage_a=False, m_range=None,
+               stale_g=None):
     """All channels: wide [n_sources, 2 samples] of the format's dtype, the whole stream from sample 0 -> [n_ch, 2 n_out]
-    uint8.  calls: the samples per call, in order (default: one call); only hist_short depends on it."""
+    uint8.  calls: the samples per call, in order (default: one call); only hist_short depends on it.  m_range = (m0, m1):
+    outputs m0 <= m < m1 of that stream only (default: all of them).  stale_g: per channel the increment whose coefficient
+    sums G enter S16's 128 G term instead of the channel's own - what a retune gives whose new sums never reach the kernel."""
     wide = np.asarray(wide)
     wide = wide.reshape(-1, wide.shape[-1])
     h = np.asarray(h, np.int64)
     K, kp = len(h), (len(h) + 31) // 32 * 32
     n_samp = wide.shape[1] // 2
     n_out = n_samp // M
-    n = np.arange(n_out, dtype=np.int64) * M + M - 1
+    m0, m1 = (0, n_out) if m_range is None else m_range
+    n = np.arange(m0, m1, dtype=np.int64) * M + M - 1
+    n_out = len(n)
     shift16, half = (16, 1 << 15) if fmt == "s16" else (8, 128)
     if defect == "round_m1":
         half -= 1
@@ -90,6 +95,10 @@ def channelize(wide, fmt, h, M, sources, incs, shifts, P, defect=None, calls=Non
         Gi = np.stack([b for _, b in g], axis=1)
         Ar = Xr @ Gr - Xi @ Gi
         Ai = Xi @ Gr + Xr @ Gi
+        if fmt == "s16" and stale_g is not None:
+            o = [cm.channel_taps(h, int(stale_g[c]), P) for c in chs]
+            Or, Oi = np.stack([a for a, _ in o], axis=1).sum(0), np.stack([b for _, b in o], axis=1).sum(0)
+            Ar, Ai = Ar + 128 * (Or - Oi - Gr.sum(0) + Gi.sum(0)), Ai + 128 * (Or + Oi - Gr.sum(0) - Gi.sum(0))
         if fmt == "s16" and defect == "no_g":
             Ar, Ai = Ar - 128 * (Gr.sum(0) - Gi.sum(0)), Ai - 128 * (Gr.sum(0) + Gi.sum(0))
         if fmt == "s16" and defect == "g_sign":

@@ -18,6 +18,14 @@ Gain cases (channels that follow their engine channel's IF gain, iqd_channelizer
 tests/chan_gain_model.py on oracle chains) are drawn only when asked: FUZZ_GAIN=1 makes every case one, and nothing else
 draws them, so that a seed without it is the cases it always was.
 
+Format cases (signed captures: sample_format "s8" / "s16", chz_fmt_kernel, against tests/chan_fmt_model.py) are drawn only
+when asked as well: FUZZ_FMT=1 makes every case one.  Such a case is drawn without a GPU (draw_fmt) and then run (run_fmt):
+M, taps, sources, channels, calls and the operator's steps as in a plain case, the long calls sized by
+iqd_channelizer_window_outputs of the format, inputs of the format's dtype (full range, small with a live low byte, on the
+rails, constant, carriers), a share with a stage-a half point planted on channel 0 and a share on the taps' limit with
+sign-matched rail input (sat16; Lo outside int32).  tests/test_chan_fmt_fuzz_host.py holds the fixed slice SLICES["fmt"]
+to the defects of tests/chan_fmt_model.py before tests/test_gpu_chan_fmt_fuzz.py runs it.
+
 A plain case is drawn without a GPU (draw_plain) and then run (run_plain), so that a CPU test can hold the fixed slices
 of tests/test_gpu_chan_fuzz.py to the mutants of tests/chan_mutants.py before they go to the GPU (first_channel_kills)."""
 import json
@@ -28,6 +36,8 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np                                     # noqa: E402
 from rtlsdrdiags_amd import capi, synth                # noqa: E402
+from tests import chan_fmt_cases as fc                 # noqa: E402
+from tests import chan_fmt_model as sfm                # noqa: E402
 from tests import chan_frac_model as fm                # noqa: E402
 from tests import chan_gain_model as gm                # noqa: E402
 from tests import chan_model as cm                     # noqa: E402
@@ -40,7 +50,8 @@ INC_EDGES = (0, 1, 2 ** 31, 2 ** 31 - 1, 2 ** 32 - 1)
 BOUND_SUM = (2 ** 31 - 256) // 256
 SLICES = {"plain": ((9101, 150), (9102, 150)), "scan": (9103, 40),   # (seed, cases): tests/test_gpu_chan_fuzz.py's
           "survey": (9104, 40),                                       # tests/test_gpu_chan_survey_fuzz.py's
-          "gain": (9105, 24)}                                         # tests/test_gpu_chan_gain_fuzz.py's
+          "gain": (9105, 24),                                         # tests/test_gpu_chan_gain_fuzz.py's
+          "fmt": (9106, 36)}                                          # tests/test_gpu_chan_fmt_fuzz.py's
 MODEL_BUDGET = 4e7        # tap x wideband-sample products the model may spend per case (chan_model convolves at the
 #                           wide rate: K M outputs per channel); fewer channels are compared when a case is past it
 
@@ -759,6 +770,221 @@ def gain_case(rng, ctx):
     return bad
 
 
+# ---------------------------------------------------------------------------------------------------- format cases
+# of the format cases: on the taps' limit with matched input; with a planted half point; draw_taps' taps at the bound
+FMT_LIMIT_SHARE, FMT_PLANT_SHARE, FMT_BOUND_SHARE = 0.12, 0.25, 0.08
+LIMIT_INCS = (0, 2 ** 29, 3 * 2 ** 29, 5 * 2 ** 29, 7 * 2 ** 29)   # 0 degrees and the diagonals (chan_fmt_cases.limit_taps)
+LIMIT_SEG = 2048                                         # samples of one (rail, extreme) segment: twice the taps' reach
+
+
+def draw_fmt_input(rng, fmt, M, n_samples):
+    """(kind, [2 n_samples] of the format's dtype, the offset-binary capture it was converted from or None)"""
+    kind = int(rng.integers(0, 5))
+    r = np.random.default_rng(int(rng.integers(1 << 30)))
+    dt = sfm.DTYPE[fmt]
+    info = np.iinfo(dt)
+    if kind == 0:
+        return "full", fc.full_random(r, n_samples, fmt), None
+    if kind == 1:                                             # (S16: the high byte is 0 or -1, the low one carries it all)
+        return "small", fc.small_random(r, n_samples, fmt), None
+    if kind == 2:
+        return "rails", r.choice([info.min, info.max], 2 * n_samples).astype(dt), None
+    if kind == 3:
+        fs = 256000.0 * M
+        st = [{"offset": float(rng.uniform(-0.45, 0.45)) * fs, "kind": ("fm", "am", "usb")[i % 3],
+               "amplitude": float(2.0 ** rng.uniform(1, 5.5)), "tone": 1000.0 + 300 * i,
+               "on": [(int(a), int(a) + int(rng.integers(1, n_samples + 1)))
+                      for a in rng.integers(0, n_samples, 2)]} for i in range(int(rng.integers(1, 4)))]
+        u8 = synth.wideband(n_samples, fs, st, seed=int(rng.integers(1 << 30)), sigma=float(rng.choice([0.0, 1.0, 4.0])))
+        return "carriers", sfm.from_u8(u8, fmt).copy(), u8
+    return "constant", np.tile(rng.integers(info.min, info.max + 1, 2).astype(dt), n_samples), None
+
+
+def limit_input(h, M, inc, P, fmt, n_samples):
+    """Rail input sign-matched to the taps of increment inc (chan_fmt_cases.limit_case's, at any M that is a multiple of
+    the taps' period 8): segments of LIMIT_SEG samples for (rail, extreme) = (re, max), (re, min), (im, max), (im, min),
+    over and over.  In the second half of a segment |A| is the largest the taps allow."""
+    assert M % 8 == 0
+    gr, gi = cm.channel_taps(h, inc, P)
+    nn = np.arange(n_samples)
+    k = (M - 1 - nn) % 8                                      # x[n] meets g[k], k = (n_m - n) mod 8, n_m = M - 1 mod 8
+    sr = np.array([np.sign(gr[kk::8].sum()) for kk in range(8)])[k]
+    si = np.array([np.sign(gi[kk::8].sum()) for kk in range(8)])[k]
+    q = nn // LIMIT_SEG % 4
+    wr, wi = np.where(q < 2, sr, si), np.where(q < 2, -si, sr)    # Ar = sum gr xr - gi xi, Ai = sum gr xi + gi xr
+    wr, wi = np.where(q % 2 == 0, wr, -wr), np.where(q % 2 == 0, wi, -wi)
+    info = np.iinfo(sfm.DTYPE[fmt])
+    w = np.empty(2 * n_samples, sfm.DTYPE[fmt])
+    w[0::2], w[1::2] = np.where(wr > 0, info.max, info.min), np.where(wi > 0, info.max, info.min)
+    return w
+
+
+def draw_fmt(rng):
+    """One format case, drawn without a GPU: draw_plain's configuration and script on a signed capture.  cfg["wide"] is
+    [n_src, 2 samples] of the format's dtype, so that walk() serves as it is (a unit is 64 M elements: 32 outputs)."""
+    fmt = ("s8", "s16")[int(rng.integers(0, 2))]
+    share = rng.random()
+    limit = share < FMT_LIMIT_SHARE
+    plant = not limit and share < FMT_LIMIT_SHARE + FMT_PLANT_SHARE
+    bound = FMT_LIMIT_SHARE + FMT_PLANT_SHARE <= share < FMT_LIMIT_SHARE + FMT_PLANT_SHARE + FMT_BOUND_SHARE
+    M = 8 * int(rng.integers(1, 9)) if limit else int(rng.choice([2, 64])) if rng.random() < 0.1 else int(rng.integers(2, 65))
+    taps, h = draw_taps(rng, M)
+    while bound and np.abs(h.astype(np.int64)).sum() != BOUND_SUM:      # draw_taps' own, until it is one of those
+        taps, h = draw_taps(rng, M)
+    if limit:
+        taps = h = fc.limit_taps()
+    elif plant and taps is not None and np.abs(h.astype(np.int64)).max() > 31:
+        # small taps: the sample that plant_half changes may take any value, and the output byte must not saturate on it
+        taps = h = (h.astype(np.int64) * 31 // np.abs(h.astype(np.int64)).max()).astype(np.int16)
+    K = len(h)
+    n_src = int(rng.integers(1, 5))
+    used = [s for s in range(n_src) if rng.random() < 0.7] or [int(rng.integers(0, n_src))]   # the rest: no channel
+    n_ch = draw_count(rng)
+    src = rng.choice(used, n_ch).astype(np.uint32)
+    inc = np.array([draw_inc(rng) for _ in range(n_ch)], np.uint64)
+    shift = rng.integers(0, 9, n_ch).astype(np.uint8)
+    src_inc = [int(rng.choice(LIMIT_INCS)) for _ in range(n_src)]       # limit cases: what a source's input is matched to
+    if limit:
+        for c in range(n_ch):
+            if c == 0 or rng.random() < 0.5:
+                inc[c] = src_inc[src[c]]
+    if plant:
+        inc[0], shift[0] = 0, 8              # real taps; L = 8: one LSB of stage a is two of the output byte
+    win = capi.channelizer_window_outputs(M, K, fmt)
+    calls, long_calls = [], 0
+    for _ in range(int(rng.integers(1, 9))):
+        r = rng.random()
+        if r < 0.3:
+            u = 1                                                       # the shortest call: 32 outputs
+        elif r < 0.55:
+            u = 2 * int(rng.integers(1, 6)) + 1                         # n_out % 64 == 32
+        elif r < 0.8 or long_calls >= 2:
+            u = 2 * int(rng.integers(1, 6))
+        else:                                                           # several windows and a tail of 32, 96 or 160 outputs
+            u = win // 32 * (2 if 2 * win <= 768 and rng.random() < 0.4 else 1) + 2 * int(rng.integers(0, 3)) + 1
+            long_calls += 1
+        ops = []
+        if calls and rng.random() < 0.5:
+            what = int(rng.integers(0, 4))
+            if what == 0:
+                first = int(rng.integers(0, n_ch))
+                n = int(rng.integers(1, min(4, n_ch - first) + 1))
+                ops.append(("retune", first, [draw_inc(rng) for _ in range(n)], [int(v) for v in rng.integers(0, 9, n)]))
+            elif what == 1:
+                ops.append(("move", int(rng.integers(0, n_ch)), int(rng.integers(0, n_src))))
+            elif what == 2:
+                ops.append(("reset",))
+            else:
+                ops.append(("form",))
+        calls.append({"units": u, "ops": ops})
+    if limit:                                # every segment once: the first call grows to what is missing
+        calls[0]["units"] += max(0, -(-4 * LIMIT_SEG // (32 * M)) - sum(c["units"] for c in calls))
+    units = sum(c["units"] for c in calls)
+    total = units * 32 * M
+    kinds, wide, u8 = [], [], {}
+    for s in range(n_src):
+        k, w, u = draw_fmt_input(rng, fmt, M, total)
+        if limit:
+            k, w, u = "limit 0x%08x" % src_inc[s], limit_input(h, M, src_inc[s], ctx_phasor(), fmt, total), None
+        elif plant and s == src[0]:
+            k, w, u = "small", fc.small_random(np.random.default_rng(int(rng.integers(1 << 30))), total, fmt), None
+        kinds.append(k)
+        wide.append(w)
+        if u is not None:
+            u8[s] = u
+    # the channels compared: the first and the last, those an operator's step touches, and random ones within the budget
+    # (the model gathers [outputs, K] per rail and call and multiplies it by the checked channels' taps)
+    touched = [c for call in calls for op in call["ops"] if op[0] in ("retune", "move")
+               for c in ([op[1], op[1] + len(op[2]) - 1] if op[0] == "retune" else [op[1]])]
+    work = 4.0 * K * units * 32
+    n_check = int(max(min(4, n_ch), min(n_ch if n_ch <= 64 else 32, MODEL_BUDGET // work)))
+    check = np.arange(n_ch) if n_check >= n_ch else np.unique(np.concatenate(
+        [[0, n_ch - 1], touched, rng.choice(n_ch, n_check, replace=False)]).astype(np.int64))
+    cfg = {"fmt": fmt, "M": M, "K": K, "taps": taps, "h": h, "n_src": n_src, "n_ch": n_ch, "src": src, "inc": inc,
+           "shift": shift, "calls": calls, "kinds": kinds, "wide": np.stack(wide), "u8": u8, "check": check,
+           "device_form": bool(rng.random() < 0.5), "limit": limit, "window": win, "planted": None}
+    if plant:                                # in a call that still finds channel 0 as it was set up, on the source it has then
+        ok = [(epoch, m0, n_out, int(s_[0])) for _, _, _, epoch, m0, n_out, s_, i_, l_ in walk(cfg) if i_[0] == 0 and l_[0] == 8]
+        epoch, m0, n_out, s0 = ok[int(rng.integers(0, len(ok)))]
+        m_star = m0 + int(rng.integers(0, n_out))
+        try:                                 # (epoch is a view of cfg["wide"]: from the last reset, which zeroed the history)
+            fc.plant_half(epoch[s0], h, M, ctx_phasor(), m_star)
+            cfg["planted"] = (s0, m_star)
+        except AssertionError:               # (taps without an odd one: no sample value need do it)
+            pass
+    return cfg
+
+
+_PHASOR = []
+
+
+def ctx_phasor():
+    if not _PHASOR:
+        _PHASOR.append(capi.channelizer_phasor_table())
+    return _PHASOR[0]
+
+
+def describe_fmt(cfg):
+    return "%s%s%s %s" % (cfg["fmt"], ", taps on the limit and matched rail input" if cfg["limit"] else "",
+                          ", half point planted at (source, output of its epoch) %r" % (cfg["planted"],) if cfg["planted"] else "",
+                          describe(cfg))
+
+
+def run_fmt(cfg, ctx):
+    """Runs a format case's script through iqd_channelizer_run / run_device of a channelizer of its sample format, every
+    checked channel of every call against chan_fmt_model.channelize over the epoch; None, or what differed."""
+    eng, P, M, fmt = ctx.eng, ctx.P, cfg["M"], cfg["fmt"]
+    B = sfm.RAIL_BYTES[fmt]
+    z = capi.Channelizer(eng, M, cfg["n_ch"], n_sources=cfg["n_src"], taps=cfg["taps"], sample_format=fmt)
+    z.set_channels(0, source=cfg["src"], phase_inc=cfg["inc"], gain_shift=cfg["shift"])
+    bad = None
+    ck = cfg["check"]
+    for i, device, ops, epoch, m0, n_out, src, inc, shift in walk(cfg):
+        for op in ops:
+            if op[0] == "retune":
+                z.set_channels(op[1], phase_inc=op[2], gain_shift=op[3])
+            elif op[0] == "move":
+                z.set_channels(op[1], source=[op[2]])
+            elif op[0] == "reset":
+                z.reset()
+        piece = np.ascontiguousarray(epoch[:, 2 * M * m0:])
+        if device:
+            d_in, d_out = eng.dev_alloc(piece.nbytes), eng.dev_alloc(cfg["n_ch"] * 2 * n_out)
+            eng.dev_upload(d_in, piece)
+            z.run_device(d_in, piece.shape[1] * B, d_out)
+            eng.synchronize()
+            got = eng.dev_download(d_out, cfg["n_ch"] * 2 * n_out).reshape(cfg["n_ch"], -1)
+            eng.dev_free(d_in)
+            eng.dev_free(d_out)
+        else:
+            got = z.run(piece)
+        ctx.count("fmt ops", len(ops))
+        ctx.count("fmt device calls" if device else "fmt host calls")
+        want = sfm.channelize(epoch, fmt, cfg["h"], M, src[ck], inc[ck], shift[ck], P, m_range=(m0, m0 + n_out))
+        for j, c in enumerate(ck):
+            if not np.array_equal(got[c], want[j]):
+                d = np.flatnonzero(got[c] != want[j])
+                bad = ("call %d (%s form, %d outputs from output %d of the epoch): channel %d (source %d inc 0x%08x L %d) "
+                       "differs in %d bytes, first at byte %d (outputs %s): got %s, model %s" % (
+                           i, "device" if device else "host", n_out, m0, c, src[c], inc[c], shift[c], len(d), d[0],
+                           np.unique(d // 2)[:12].tolist(), got[c][d[:8]].tolist(), want[j][d[:8]].tolist()))
+                break
+        if bad:
+            break
+    z.close()
+    ctx.count("fmt cases")
+    return bad
+
+
+def fmt_case(rng, ctx, only=None):
+    """only = "s8" / "s16": the case is drawn as ever and run if it is of that format (None otherwise, as if identical)."""
+    cfg = draw_fmt(rng)
+    if only is not None and cfg["fmt"] != only:
+        return None
+    bad = run_fmt(cfg, ctx)
+    return None if bad is None else "format case: %s\n  %s" % (describe_fmt(cfg), bad)
+
+
 def compute_units():
     """torch.cuda.get_device_properties(0).multi_processor_count, asked in a child process: torch brings its own HIP
     runtime, which finds no device in a process where the engine's has opened it first."""
@@ -794,10 +1020,13 @@ def main():
     ctx = Context(bindings.Oracle())
     mode, fmode, smode = os.environ.get("FUZZ_SCAN"), os.environ.get("FUZZ_FRAC"), os.environ.get("FUZZ_SURVEY")
     gmode = os.environ.get("FUZZ_GAIN") == "1"
+    tmode = os.environ.get("FUZZ_FMT") == "1"
 
     def one():
         if gmode:                                          # (asked for: no draw decides it, the other kinds draw as ever)
             return False, gain_case(rng, ctx)
+        if tmode:                                          # (asked for as well)
+            return False, fmt_case(rng, ctx)
         r = rng.random() if mode is None else 1.0
         scan = mode == "1" or (mode is None and r < 0.125)
         if scan:
