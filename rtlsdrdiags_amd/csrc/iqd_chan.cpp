@@ -43,6 +43,31 @@ struct Staging {
         }
         return bytes <= h.n ? hipSuccess : h.alloc(bytes);
     }
+    // the pieces through this slot to the device, queued on stream, and the event behind them
+    struct Piece { void *dst; const void *src; size_t n; };
+    hipError_t upload(const std::vector<Piece> &pieces, hipStream_t stream)
+    {
+        size_t bytes = 0, at = 0;
+        for (const Piece &p : pieces) bytes += p.n;
+        hipError_t e = ensure(bytes ? bytes : 16);
+        for (const Piece &p : pieces) {
+            if (e != hipSuccess) return e;
+            memcpy(h + at, p.src, p.n);
+            e = hipMemcpyAsync(p.dst, h + at, p.n, hipMemcpyHostToDevice, stream);
+            at += p.n;
+        }
+        if (e == hipSuccess) e = hipEventRecord(done, stream);
+        pending = e == hipSuccess;
+        return e;
+    }
+};
+
+// the three kinds of channel: each has tiles and workgroups of its own and its kernel
+enum { CHZ_FIXED, CHZ_GAIN, CHZ_SCAN, CHZ_KINDS };
+struct WgSet {
+    std::vector<ChzWg> wgs;
+    DevBufExact dev;
+    uint32_t waves = 1, wpt = 1;                  // a walker's: tiles per workgroup, waves per tile
 };
 
 double bessel_i0(double x)
@@ -81,19 +106,14 @@ struct iqd_channelizer {
     bool any_dirty = true;
     uint64_t m_abs = 0;                           // outputs per channel since create / reset
     std::vector<ChzTile> tiles;
-    std::vector<ChzWg> wgs;                       // chz_kernel's workgroups (fixed channels)
-    std::vector<ChzWg> swgs;                      // the walker's (following channels)
-    std::vector<ChzWg> gwgs;                      // the gain walker's (gain-following channels)
-    uint32_t scan_waves = 1;                      // tiles per walker workgroup
-    uint32_t scan_wpt = 1;                        // waves per tile
-    uint32_t gain_waves = 1, gain_wpt = 1;        // the same of the gain walker
+    WgSet wg[CHZ_KINDS];                          // chz_kernel's workgroups (fixed channels), the gain walker's, the scan walker's
     uint32_t n_fixed_tiles = 0;                   // tiles [0, n_fixed_tiles) hold fixed channels,
     uint32_t n_packed_tiles = 0;                  // [n_fixed_tiles, n_packed_tiles) gain-following ones, the rest scanner-following
     std::vector<uint32_t> slot_of;                // [n_ch]: tile * 8 + slot
     std::vector<uint8_t> amat;                    // [n_tiles][q residues][nq][2][64][16]
     std::vector<ChzFmtTile> gsum;                 // [n_tiles]: the rows' coefficient sums (IQD_WIDE_S16 only)
     DevBufExact d_gsum;
-    DevBufExact d_amat, d_tiles, d_wgs, d_swgs, d_gwgs, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
+    DevBufExact d_amat, d_tiles, d_phasor, d_proto, d_centre, d_hist[2], st_wide, st_out;
     DevBufExact w_rows, w_pcm, w_cnt, w_mag, w_sp;        // iqd_accept_wideband's device staging
     // the band survey: points measured on every source, in tiles of 8 of their own (iqd_chan_survey.hip)
     std::vector<uint32_t> sv_inc;
@@ -162,31 +182,29 @@ static void chz_new_taps(iqd_channelizer *z, uint32_t c)
 // channels sorted by source, 8 per tile, up to CHZ_WAVES tiles of one source per workgroup row; fixed, gain-following and
 // scanner-following channels never share a tile.  A walker's workgroups take `waves` tiles each: as few as keep every CU
 // busy; the rest of the workgroup's 8 waves share the tiles' outputs (wpt waves per tile).
-static void chz_walker_wgs(const iqd_channelizer *z, const std::vector<ChzWg> &runs, std::vector<ChzWg> &wgs, uint32_t &waves,
-                           uint32_t &wpt)
+static void chz_walker_wgs(const iqd_channelizer *z, const std::vector<ChzWg> &runs, WgSet &w)
 {
     uint32_t n_tiles = 0;
     for (const ChzWg &r : runs) n_tiles += r.n_tiles;
-    waves = std::max(1u, std::min(CHZ_WAVES, n_tiles / std::max(1u, z->n_cus)));
-    wpt = 1;
-    while (2 * wpt * waves <= CHZ_WAVES) wpt *= 2;
+    w.waves = std::max(1u, std::min(CHZ_WAVES, n_tiles / std::max(1u, z->n_cus)));
+    w.wpt = 1;
+    while (2 * w.wpt * w.waves <= CHZ_WAVES) w.wpt *= 2;
     for (const ChzWg &r : runs)
-        for (uint32_t t = 0; t < r.n_tiles; t += waves)
-            wgs.push_back(ChzWg{r.source, r.first_tile + t, std::min(waves, r.n_tiles - t), 0});
+        for (uint32_t t = 0; t < r.n_tiles; t += w.waves)
+            w.wgs.push_back(ChzWg{r.source, r.first_tile + t, std::min(w.waves, r.n_tiles - t), 0});
 }
 
 static void chz_group(iqd_channelizer *z)
 {
     z->tiles.clear();
-    z->wgs.clear();
-    z->swgs.clear();
-    z->gwgs.clear();
+    for (WgSet &w : z->wg) w.wgs.clear();
     z->slot_of.assign(z->n_ch, 0);
-    std::vector<std::vector<uint32_t>> by_src[3];   // 0 fixed, 1 gain-following, 2 scanner-following
+    std::vector<std::vector<uint32_t>> by_src[CHZ_KINDS];
     for (auto &b : by_src) b.resize(z->n_src);
-    for (uint32_t c = 0; c < z->n_ch; c++) by_src[z->follow[c] ? 2 : z->follow_gain[c] ? 1 : 0][z->src[c]].push_back(c);
-    std::vector<ChzWg> runs[3];                   // following tiles per source
-    for (int f = 0; f < 3; f++) {
+    for (uint32_t c = 0; c < z->n_ch; c++)
+        by_src[z->follow[c] ? CHZ_SCAN : z->follow_gain[c] ? CHZ_GAIN : CHZ_FIXED][z->src[c]].push_back(c);
+    std::vector<ChzWg> runs[CHZ_KINDS];           // following tiles per source
+    for (int f = 0; f < CHZ_KINDS; f++) {
         for (uint32_t s = 0; s < z->n_src; s++) {
             const auto &list = by_src[f][s];
             const uint32_t first_tile = (uint32_t)z->tiles.size();
@@ -199,17 +217,17 @@ static void chz_group(iqd_channelizer *z)
                 z->tiles.push_back(t);
             }
             const uint32_t n_tiles = (uint32_t)z->tiles.size() - first_tile;
-            if (f == 0)
+            if (f == CHZ_FIXED)
                 for (uint32_t t = 0; t < n_tiles; t += CHZ_WAVES)
-                    z->wgs.push_back(ChzWg{s, first_tile + t, std::min(CHZ_WAVES, n_tiles - t), 0});
+                    z->wg[f].wgs.push_back(ChzWg{s, first_tile + t, std::min(CHZ_WAVES, n_tiles - t), 0});
             else if (n_tiles)
                 runs[f].push_back(ChzWg{s, first_tile, n_tiles, 0});
         }
-        if (f == 0) z->n_fixed_tiles = (uint32_t)z->tiles.size();
-        if (f == 1) z->n_packed_tiles = (uint32_t)z->tiles.size();
+        if (f == CHZ_FIXED) z->n_fixed_tiles = (uint32_t)z->tiles.size();
+        if (f == CHZ_GAIN) z->n_packed_tiles = (uint32_t)z->tiles.size();
     }
-    chz_walker_wgs(z, runs[1], z->gwgs, z->gain_waves, z->gain_wpt);
-    chz_walker_wgs(z, runs[2], z->swgs, z->scan_waves, z->scan_wpt);
+    chz_walker_wgs(z, runs[CHZ_GAIN], z->wg[CHZ_GAIN]);
+    chz_walker_wgs(z, runs[CHZ_SCAN], z->wg[CHZ_SCAN]);
     z->amat.assign(z->tiles.size() * z->q * z->nq * 2 * 64 * 16, 0);
     if (z->fmt == IQD_WIDE_S16) z->gsum.assign(z->tiles.size(), ChzFmtTile{});
     std::fill(z->ch_dirty.begin(), z->ch_dirty.end(), 1);
@@ -287,41 +305,22 @@ static int chz_upload(iqd_channelizer *z)
         CHZ_TRY(z, z->d_amat.ensure(z->amat.size()));
         CHZ_TRY(z, z->d_tiles.ensure(n_tiles * sizeof(ChzTile)));
         if (z->fmt == IQD_WIDE_S16) CHZ_TRY(z, z->d_gsum.ensure(std::max<size_t>(1, n_tiles) * sizeof(ChzFmtTile)));
-        CHZ_TRY(z, z->d_wgs.ensure(std::max<size_t>(1, z->wgs.size()) * sizeof(ChzWg)));
-        CHZ_TRY(z, z->d_swgs.ensure(std::max<size_t>(1, z->swgs.size()) * sizeof(ChzWg)));
-        CHZ_TRY(z, z->d_gwgs.ensure(std::max<size_t>(1, z->gwgs.size()) * sizeof(ChzWg)));
+        for (WgSet &w : z->wg) CHZ_TRY(z, w.dev.ensure(std::max<size_t>(1, w.wgs.size()) * sizeof(ChzWg)));
     }
-    struct Run { size_t first, n; };
-    std::vector<Run> runs;
-    size_t bytes = regroup ? (z->wgs.size() + z->swgs.size() + z->gwgs.size()) * sizeof(ChzWg) : 0;
+    std::vector<Staging::Piece> pieces;
     for (size_t t = 0; t < n_tiles; t++) {
         if (!tile_dirty[t]) continue;
-        if (!runs.empty() && runs.back().first + runs.back().n == t) runs.back().n++;
-        else runs.push_back(Run{t, 1});
-        bytes += tile_bytes + sizeof(ChzTile) + (z->fmt == IQD_WIDE_S16 ? sizeof(ChzFmtTile) : 0);
+        size_t n = 1;                             // a run of consecutive dirty tiles
+        while (t + n < n_tiles && tile_dirty[t + n]) n++;
+        const size_t na = t < z->n_packed_tiles ? std::min<size_t>(n, z->n_packed_tiles - t) : 0;
+        if (na) pieces.push_back({z->d_amat.as<uint8_t>() + t * tile_bytes, &z->amat[t * tile_bytes], na * tile_bytes});
+        pieces.push_back({z->d_tiles.as<ChzTile>() + t, &z->tiles[t], n * sizeof(ChzTile)});
+        if (z->fmt == IQD_WIDE_S16) pieces.push_back({z->d_gsum.as<ChzFmtTile>() + t, &z->gsum[t], n * sizeof(ChzFmtTile)});
+        t += n;                                   // (tile t + n is clean, or the end)
     }
-    Staging &st = z->stg[z->stg_cur];
-    CHZ_TRY(z, st.ensure(bytes ? bytes : 16));
-    uint8_t *h = st.h;
-    size_t at = 0;
-    auto copy = [&](void *dst, const void *src, size_t n) {
-        memcpy(h + at, src, n);
-        const hipError_t e = hipMemcpyAsync(dst, h + at, n, hipMemcpyHostToDevice, z->stream);
-        at += n;
-        return e;
-    };
-    for (const Run &r : runs) {
-        const size_t na = r.first < z->n_packed_tiles ? std::min<size_t>(r.n, z->n_packed_tiles - r.first) : 0;
-        if (na) CHZ_TRY(z, copy(z->d_amat.as<uint8_t>() + r.first * tile_bytes, &z->amat[r.first * tile_bytes], na * tile_bytes));
-        CHZ_TRY(z, copy(z->d_tiles.as<ChzTile>() + r.first, &z->tiles[r.first], r.n * sizeof(ChzTile)));
-        if (z->fmt == IQD_WIDE_S16)
-            CHZ_TRY(z, copy(z->d_gsum.as<ChzFmtTile>() + r.first, &z->gsum[r.first], r.n * sizeof(ChzFmtTile)));
-    }
-    if (regroup && !z->wgs.empty()) CHZ_TRY(z, copy(z->d_wgs.p, z->wgs.data(), z->wgs.size() * sizeof(ChzWg)));
-    if (regroup && !z->swgs.empty()) CHZ_TRY(z, copy(z->d_swgs.p, z->swgs.data(), z->swgs.size() * sizeof(ChzWg)));
-    if (regroup && !z->gwgs.empty()) CHZ_TRY(z, copy(z->d_gwgs.p, z->gwgs.data(), z->gwgs.size() * sizeof(ChzWg)));
-    CHZ_TRY(z, hipEventRecord(st.done, z->stream));
-    st.pending = true;
+    for (WgSet &w : z->wg)
+        if (regroup && !w.wgs.empty()) pieces.push_back({w.dev.p, w.wgs.data(), w.wgs.size() * sizeof(ChzWg)});
+    CHZ_TRY(z, z->stg[z->stg_cur].upload(pieces, z->stream));
     z->stg_cur ^= 1;
     z->layout_dirty = false;
     z->any_dirty = false;
@@ -540,13 +539,27 @@ static int chz_check_len(iqd_channelizer *z, size_t bytes_per_source)
 }
 
 // the most outputs of one window
-static uint32_t chz_t_max(const iqd_channelizer *z)
+static uint32_t chz_t_max(const iqd_channelizer *z) { return chz_window_outputs(z->m, z->kp, z->q, z->rail); }
+
+// What every launch of one call shares: the capture, the history it starts from, the tables, the geometry.  The tiles and
+// what goes out are the caller's (a.amat, a.tiles, a.wgs, a.out, a.out_row, a.hist_next).
+static ChzLaunch chz_launch(const iqd_channelizer *z, const void *wide_dev, size_t bytes_per_source)
 {
-    if (z->q > 1)   // windows of whole store groups: 2 (t_max m / q + kp) <= CHZ_FRAC_WIN_MAX
-        return std::min<uint32_t>(1024, (uint32_t)((uint64_t)(CHZ_FRAC_WIN_MAX / 2 - z->kp) * z->q / z->m)) /
-               chz_frac_group(z->q) * chz_frac_group(z->q);
-    if (z->fmt != IQD_WIDE_U8) return chz_window_outputs(z->m, z->kp, z->rail);
-    return std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - z->kp) / z->m) / CHZ_GROUP * CHZ_GROUP;
+    ChzLaunch a{};
+    a.wide = (const uint8_t *)wide_dev;
+    a.hist = z->d_hist[z->cur].as<uint8_t>();
+    a.phasor = z->d_phasor.as<uint32_t>();
+    a.bytes_per_source = bytes_per_source;
+    a.n_sources = z->n_src;
+    a.n_out = (uint32_t)(z->row_bytes(bytes_per_source) / 2);   // a multiple of 32 q
+    a.m = z->m;
+    a.kp = z->kp;
+    a.nq = z->nq;
+    a.nbase = (uint32_t)(z->m_abs / z->q * z->m);   // m_abs is a multiple of 32 q
+    a.den = z->q;
+    a.rail_bytes = z->rail;
+    a.t_blk = std::min(a.n_out, chz_t_max(z));
+    return a;
 }
 
 // Queues one call: chz_kernel for the fixed channels, the walkers for the following ones (scan != NULL; gain: its
@@ -558,27 +571,15 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
         int rc = chz_upload(z);
         if (rc != IQD_OK) return rc;
     }
-    const uint32_t n_out = (uint32_t)(z->row_bytes(bytes_per_source) / 2);   // a multiple of 32 q
     const uint32_t t_max = chz_t_max(z);
-    ChzLaunch a{};
-    a.wide = (const uint8_t *)wide_dev;
-    a.hist = z->d_hist[z->cur].as<uint8_t>();
+    ChzLaunch a = chz_launch(z, wide_dev, bytes_per_source);
     a.hist_next = z->d_hist[z->cur ^ 1].as<uint8_t>();
-    a.phasor = z->d_phasor.as<uint32_t>();
     a.amat = z->d_amat.as<uint4>();
     a.tiles = z->d_tiles.as<ChzTile>();
-    a.wgs = z->d_wgs.as<ChzWg>();
+    a.wgs = z->wg[CHZ_FIXED].dev.as<ChzWg>();
     a.out = (uint8_t *)out_dev;
-    a.bytes_per_source = bytes_per_source;
-    a.n_sources = z->n_src;
-    a.out_row = 2 * n_out;
-    a.n_out = n_out;
-    a.m = z->m;
-    a.kp = z->kp;
-    a.nq = z->nq;
-    a.nbase = (uint32_t)(z->m_abs / z->q * z->m);   // m_abs is a multiple of 32 q
-    a.den = z->q;
-    a.t_blk = n_out <= t_max ? n_out : t_max;
+    a.out_row = 2 * a.n_out;
+    const uint32_t n_fixed = (uint32_t)z->wg[CHZ_FIXED].wgs.size();
     if (scan) {
         if (z->centre_dirty && z->n_follow) {   // (the scan walker's; the gain walker does not read them)
             CHZ_TRY(z, hipMemcpyAsync(z->d_centre.p, z->centre.data(), (size_t)z->n_src * 8, hipMemcpyHostToDevice, z->stream));
@@ -587,37 +588,33 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
         }
         scan->proto = z->d_proto.as<int16_t>();
         scan->centre = z->d_centre.as<unsigned long long>();
-        scan->waves = z->scan_waves;
-        scan->wpt = z->scan_wpt;
-        scan->t_blk = scan->block_out <= t_max ? scan->block_out : t_max;   // the walker's windows stay inside one block
+        scan->t_blk = scan->block_out <= t_max ? scan->block_out : t_max;   // the walkers' windows stay inside one block
     }
     if (z->fmt != IQD_WIDE_U8) {   // (no following channels, no fractional rate: refused where they are asked for)
         ChzFmtLaunch f{};
         f.a = a;
         f.gsum = z->d_gsum.as<ChzFmtTile>();
-        f.rail_bytes = z->rail;
         f.pstride = 2 * (a.t_blk * a.m + a.kp) + 16;
-        CHZ_TRY(z, launch_channelizer_fmt(f, (uint32_t)z->wgs.size(), z->stream));
+        CHZ_TRY(z, launch_channelizer_fmt(f, n_fixed, z->stream));
     } else {
-        if (scan && !z->gwgs.empty()) {   // before launch_channelizer: its history kernel comes last
+        const WgSet &gw = z->wg[CHZ_GAIN], &sw = z->wg[CHZ_SCAN];
+        if (scan && !gw.wgs.empty()) {   // before launch_channelizer: its history kernel comes last
             ChzGainLaunch g{};
-            g.agc_cfg = scan->agc_cfg;
-            g.agc = scan->agc;
-            g.consts = scan->consts;
-            g.first_ch = scan->first_ch;
-            g.block_out = scan->block_out;
-            g.n_blocks = scan->n_blocks;
-            g.t_blk = scan->t_blk;
-            g.waves = z->gain_waves;
-            g.wpt = z->gain_wpt;
+            static_cast<ChzWalkLaunch &>(g) = *scan;   // the engine's state and the blocks are the same
+            g.waves = gw.waves;
+            g.wpt = gw.wpt;
             ChzLaunch b = a;
-            b.wgs = z->d_gwgs.as<ChzWg>();
-            CHZ_TRY(z, launch_channelizer_gain(b, (uint32_t)z->gwgs.size(), g, z->stream));
+            b.wgs = gw.dev.as<ChzWg>();
+            CHZ_TRY(z, launch_channelizer_gain(b, (uint32_t)gw.wgs.size(), g, z->stream));
         }
-        CHZ_TRY(z, launch_channelizer(a, (uint32_t)z->wgs.size(), z->d_swgs.as<ChzWg>(), scan ? (uint32_t)z->swgs.size() : 0u, scan, z->stream));
+        if (scan) {
+            scan->waves = sw.waves;
+            scan->wpt = sw.wpt;
+        }
+        CHZ_TRY(z, launch_channelizer(a, n_fixed, sw.dev.as<ChzWg>(), scan ? (uint32_t)sw.wgs.size() : 0u, scan, z->stream));
     }
     z->cur ^= 1;
-    z->m_abs += n_out;
+    z->m_abs += a.n_out;
     return IQD_OK;
 }
 
@@ -693,15 +690,7 @@ static int chz_survey_upload(iqd_channelizer *z)
     const size_t ab = z->sv_amat.size(), tb = z->sv_tiles.size() * sizeof(ChzTile);
     CHZ_TRY(z, z->d_sv_amat.ensure(ab));
     CHZ_TRY(z, z->d_sv_tiles.ensure(tb));
-    Staging &st = z->stg[z->stg_cur];
-    CHZ_TRY(z, st.ensure(ab + tb));
-    uint8_t *h = st.h;
-    memcpy(h, z->sv_amat.data(), ab);
-    memcpy(h + ab, z->sv_tiles.data(), tb);
-    CHZ_TRY(z, hipMemcpyAsync(z->d_sv_amat.p, h, ab, hipMemcpyHostToDevice, z->stream));
-    CHZ_TRY(z, hipMemcpyAsync(z->d_sv_tiles.p, h + ab, tb, hipMemcpyHostToDevice, z->stream));
-    CHZ_TRY(z, hipEventRecord(st.done, z->stream));
-    st.pending = true;
+    CHZ_TRY(z, z->stg[z->stg_cur].upload({{z->d_sv_amat.p, z->sv_amat.data(), ab}, {z->d_sv_tiles.p, z->sv_tiles.data(), tb}}, z->stream));
     z->stg_cur ^= 1;
     z->sv_dirty = false;
     return IQD_OK;
@@ -741,22 +730,10 @@ int iqd_channelizer_survey_device(iqd_channelizer_t *z, const void *wide_dev, si
         rc = chz_survey_upload(z);
         if (rc != IQD_OK) return rc;
     }
-    const uint32_t n_out = (uint32_t)(bytes_per_source / (2 * z->m) * z->q);
-    ChzLaunch a{};
-    a.wide = (const uint8_t *)wide_dev;
-    a.hist = z->d_hist[z->cur].as<uint8_t>();     // read only: a survey looks and does not touch
-    a.phasor = z->d_phasor.as<uint32_t>();
+    ChzLaunch a = chz_launch(z, wide_dev, bytes_per_source);   // (the history read only: a survey looks and does not touch)
     a.amat = z->d_sv_amat.as<uint4>();
     a.tiles = z->d_sv_tiles.as<ChzTile>();
-    a.bytes_per_source = bytes_per_source;
-    a.n_sources = z->n_src;
-    a.n_out = n_out;
-    a.m = z->m;
-    a.kp = z->kp;
-    a.nq = z->nq;
-    a.nbase = (uint32_t)(z->m_abs / z->q * z->m);
-    a.den = z->q;
-    a.t_blk = std::min(n_out, chz_t_max(z));
+    const uint32_t n_out = a.n_out;
     ChzSurveyLaunch s{};
     s.sums = (uint32_t *)magnitude_dev;
     s.n_points = (uint32_t)z->sv_inc.size();
@@ -894,57 +871,51 @@ int iqd_channelizer_set_source_frequency(iqd_channelizer_t *z, uint32_t first_so
     return IQD_OK;
 }
 
-int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_t n, int follow)
+// One kind of following for channels [first, first + n): flags / count are that kind's, other the other kind's flags;
+// msg: S16 captures, S8 captures, a fractional channelizer, a channel of the other kind
+static int chz_follow(iqd_channelizer *z, uint32_t first, uint32_t n, int follow, std::vector<uint8_t> &flags,
+                      const std::vector<uint8_t> &other, uint32_t &count, const char *const (&msg)[4])
 {
-    if (!z) return IQD_EINVAL;
     if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
-    if (follow && z->fmt != IQD_WIDE_U8)
-        return z->fail(IQD_EINVAL, z->fmt == IQD_WIDE_S16 ? "channelizer: channels on IQD_WIDE_S16 captures cannot follow a scanner yet"
-                                                          : "channelizer: channels on IQD_WIDE_S8 captures cannot follow a scanner yet");
-    if (follow && z->q > 1)
-        return z->fail(IQD_EINVAL, "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow a scanner");
+    if (follow && z->fmt != IQD_WIDE_U8) return z->fail(IQD_EINVAL, msg[z->fmt == IQD_WIDE_S16 ? 0 : 1]);
+    if (follow && z->q > 1) return z->fail(IQD_EINVAL, msg[2]);
     for (uint32_t i = 0; follow && i < n; i++)
-        if (z->follow_gain[first + i])
-            return z->fail(IQD_EINVAL, "channelizer: a channel that follows its gain cannot follow its scanner as well (not built yet)");
+        if (other[first + i]) return z->fail(IQD_EINVAL, msg[3]);
     for (uint32_t i = 0; i < n; i++) {
-        uint8_t &f = z->follow[first + i];
+        uint8_t &f = flags[first + i];
         if (f == (follow ? 1 : 0)) continue;
         f = follow ? 1 : 0;
-        z->n_follow += follow ? 1 : -1;
+        count += follow ? 1 : -1;
         z->layout_dirty = true;
     }
     return IQD_OK;
 }
 
+int iqd_channelizer_follow_scanner(iqd_channelizer_t *z, uint32_t first, uint32_t n, int follow)
+{
+    static const char *const msg[4] = {
+        "channelizer: channels on IQD_WIDE_S16 captures cannot follow a scanner yet",
+        "channelizer: channels on IQD_WIDE_S8 captures cannot follow a scanner yet",
+        "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow a scanner",
+        "channelizer: a channel that follows its gain cannot follow its scanner as well (not built yet)"};
+    return z ? chz_follow(z, first, n, follow, z->follow, z->follow_gain, z->n_follow, msg) : IQD_EINVAL;
+}
+
 int iqd_channelizer_follow_gain(iqd_channelizer_t *z, uint32_t first, uint32_t n, int follow)
 {
-    if (!z) return IQD_EINVAL;
-    if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
-    if (follow && z->fmt != IQD_WIDE_U8)
-        return z->fail(IQD_EINVAL, z->fmt == IQD_WIDE_S16 ? "channelizer: channels on IQD_WIDE_S16 captures cannot follow their gain yet"
-                                                          : "channelizer: channels on IQD_WIDE_S8 captures cannot follow their gain yet");
-    if (follow && z->q > 1)
-        return z->fail(IQD_EINVAL, "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow their gain yet");
-    for (uint32_t i = 0; follow && i < n; i++)
-        if (z->follow[first + i])
-            return z->fail(IQD_EINVAL, "channelizer: a channel that follows its scanner cannot follow its gain as well (not built yet)");
-    for (uint32_t i = 0; i < n; i++) {
-        uint8_t &f = z->follow_gain[first + i];
-        if (f == (follow ? 1 : 0)) continue;
-        f = follow ? 1 : 0;
-        z->n_gain += follow ? 1 : -1;
-        z->layout_dirty = true;
-    }
-    return IQD_OK;
+    static const char *const msg[4] = {
+        "channelizer: channels on IQD_WIDE_S16 captures cannot follow their gain yet",
+        "channelizer: channels on IQD_WIDE_S8 captures cannot follow their gain yet",
+        "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow their gain yet",
+        "channelizer: a channel that follows its scanner cannot follow its gain as well (not built yet)"};
+    return z ? chz_follow(z, first, n, follow, z->follow_gain, z->follow, z->n_gain, msg) : IQD_EINVAL;
 }
 
 // chz_t_max as a host-only function (the window's fit in LDS is checked on it for every M)
 uint32_t iqd_channelizer_window_outputs(uint32_t decimation, uint32_t n_taps, uint32_t sample_format)
 {
     if (decimation < 2 || decimation > 64 || n_taps < 1 || n_taps > 1024 || sample_format > IQD_WIDE_S16) return 0;
-    const uint32_t kp = (n_taps + 31) / 32 * 32;
-    if (sample_format == IQD_WIDE_U8) return std::min<uint32_t>(1024, (CHZ_WIN_MAX / 2 - kp) / decimation) / CHZ_GROUP * CHZ_GROUP;
-    return chz_window_outputs(decimation, kp, sample_format == IQD_WIDE_S16 ? 2 : 1);
+    return chz_window_outputs(decimation, (n_taps + 31) / 32 * 32, 1, sample_format == IQD_WIDE_S16 ? 2 : 1);
 }
 
 int iqd_channelizer_tuning(uint32_t decimation, uint64_t source_centre_hz, uint64_t station_hz, int rotation, uint32_t *inc)

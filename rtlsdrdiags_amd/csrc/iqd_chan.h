@@ -59,33 +59,12 @@ struct ChzLaunch {
     uint32_t n_sources, out_row, n_out, m, kp, nq, t_blk;   // m: M, or P of a fractional decimation; kp, nq: per branch
     uint32_t nbase;                  // (outputs before this call * M) mod 2^32; fractional: (outputs / Q) P mod 2^32
     uint32_t den;                    // Q of a fractional channelizer (decimation m / den), 1 otherwise
+    uint32_t rail_bytes;             // B, bytes per rail of wide / hist: 1 (U8, S8) or 2 (S16); the history is 2 kp B bytes
 };
 
-// What the scan walker (chz_scan_kernel) reads besides ChzLaunch: a.wgs are its own workgroups (tiles of following
-// channels only); the engine's per-channel state is read, never written (the walker steps a shadow copy).
-struct ChzScanLaunch {
-    const int16_t *proto;                  // [kp] prototype, zero from K on
-    const unsigned long long *centre;      // [n_sources] source centre frequencies F_s
-    const ChanParams *params;              // the engine's state, [engine ch]
-    const AgcConfig *agc_cfg;
-    const AgcState *agc;
-    const ScanConfig *scan_cfg;
-    const ScanState *scan;
-    const uint32_t *tracker;
-    const Consts *consts;                  // the engine's constant tables (dB table)
-    uint32_t first_ch;                     // engine channel of channelizer channel 0
-    uint32_t block_out, n_blocks;          // outputs per block, blocks in this call
-    uint32_t t_blk;                        // outputs per window (a multiple of 64, or the whole short block)
-    uint32_t waves;                        // tiles per workgroup
-    uint32_t wpt;                          // waves per tile (waves * wpt <= CHZ_WAVES)
-};
-
-// What the gain walker (chz_gain_kernel, iqd_chan_gain.hip) reads besides ChzLaunch: a.wgs are its own workgroups (tiles of
-// gain-following channels only, their A operands host-packed like the fixed ones); the engine's AGC state is read, never
-// written (the walker steps a shadow copy).
-struct ChzGainShadow { AgcConfig cfg; AgcState st; };
-constexpr uint32_t CHZ_GAIN_SHADOW = CHZ_WAVES * CHZ_TILE_CH * (uint32_t)sizeof(ChzGainShadow);   // the walker's shadows in LDS
-struct ChzGainLaunch {
+// What a walker (chz_scan_kernel, chz_gain_kernel) reads besides ChzLaunch: a.wgs are its own workgroups (tiles of its
+// kind of following channels only); the engine's per-channel state is read, never written (the walker steps a shadow copy).
+struct ChzWalkLaunch {
     const AgcConfig *agc_cfg;              // the engine's state, [engine ch]
     const AgcState *agc;
     const Consts *consts;                  // the engine's constant tables (dB table)
@@ -95,6 +74,21 @@ struct ChzGainLaunch {
     uint32_t waves;                        // tiles per workgroup
     uint32_t wpt;                          // waves per tile (waves * wpt <= CHZ_WAVES)
 };
+// the scan walker's (chz_scan_kernel) besides
+struct ChzScanLaunch : ChzWalkLaunch {
+    const int16_t *proto;                  // [kp] prototype, zero from K on
+    const unsigned long long *centre;      // [n_sources] source centre frequencies F_s
+    const ChanParams *params;              // the engine's state, [engine ch]
+    const ScanConfig *scan_cfg;
+    const ScanState *scan;
+    const uint32_t *tracker;
+};
+
+// The gain walker (chz_gain_kernel, iqd_chan_gain.hip) reads nothing besides: its tiles' A operands are host-packed like
+// the fixed ones.
+struct ChzGainShadow { AgcConfig cfg; AgcState st; };
+constexpr uint32_t CHZ_GAIN_SHADOW = CHZ_WAVES * CHZ_TILE_CH * (uint32_t)sizeof(ChzGainShadow);   // the walker's shadows in LDS
+struct ChzGainLaunch : ChzWalkLaunch {};
 
 // The band survey (chz_survey_kernel, iqd_chan_survey.hip) beside ChzLaunch: a.tiles / a.amat are the survey's point tiles
 // (ChzTile::ch is the point index), shared by all sources; a.wgs and a.out are unused.  Workgroup x of the grid is
@@ -108,24 +102,25 @@ struct ChzSurveyLaunch {
 
 // Signed captures (chz_fmt_kernel, iqd_chan_fmt.hip; IQD_WIDE_S8 / IQD_WIDE_S16) beside ChzLaunch, whose fields mean what
 // they mean to chz_kernel except: a.wide / a.hist / a.hist_next are raw capture bytes of the format (2 B bytes per sample,
-// B = rail_bytes; the history is 2 kp B bytes per source, zero history is zero bytes) and a.bytes_per_source counts them.
-// The window is staged as B signed-byte planes of 2 (t_blk m + kp) bytes each, pstride apart.
+// B = a.rail_bytes: 1 is S8, one plane; 2 is S16, planes hi and lo'; zero history is zero bytes) and a.bytes_per_source
+// counts them.  The window is staged as B signed-byte planes of 2 (t_blk m + kp) bytes each, pstride apart.
 struct ChzFmtTile {
     int32_t g[CHZ_TILE_CH][2];             // per slot: the coefficient sums of its rows, sum gr - sum gi and sum gr + sum gi
 };
 struct ChzFmtLaunch {
     ChzLaunch a;
     const ChzFmtTile *gsum;                // [n_tiles], beside a.tiles (S16 only)
-    uint32_t rail_bytes;                   // B: 1 (S8, one plane) or 2 (S16, planes hi and lo')
     uint32_t pstride;                      // LDS bytes from one plane to the next: >= 2 (t_blk m + kp) + 16, a multiple of 16
 };
 
-// The most outputs of one window with `planes` byte planes of the samples in LDS (1: U8 and S8, 2: S16):
-// 2 planes (t m + kp) <= CHZ_WIN_MAX, whole store groups, at most 1024.  (iqd_channelizer_window_outputs exports it.)
-constexpr uint32_t chz_window_outputs(uint32_t m, uint32_t kp, uint32_t planes)
+// The most outputs of one window at decimation m / q with `rail` byte planes of the samples in LDS (1: U8 and S8, 2: S16):
+// 2 rail (t m / q + kp) <= CHZ_WIN_MAX (q > 1: CHZ_FRAC_WIN_MAX), whole store groups, at most 1024.
+// (iqd_channelizer_window_outputs exports it.)
+constexpr uint32_t chz_window_outputs(uint32_t m, uint32_t kp, uint32_t q, uint32_t rail)
 {
-    const uint32_t t = (CHZ_WIN_MAX / (2 * planes) - kp) / m;
-    return (t < 1024 ? t : 1024) / CHZ_GROUP * CHZ_GROUP;
+    const uint32_t group = q > 1 ? chz_frac_group(q) : CHZ_GROUP;
+    const uint64_t t = (uint64_t)((q > 1 ? CHZ_FRAC_WIN_MAX : CHZ_WIN_MAX) / (2 * rail) - kp) * q / m;
+    return (uint32_t)(t < 1024 ? t : 1024) / group * group;
 }
 
 // iqd_channelizer_tuning: the increment of a channel whose station is `station` Hz (centre station + 64000 r) cut from a
@@ -146,12 +141,14 @@ __host__ __device__ inline bool chz_tuning(uint32_t m, unsigned long long centre
 // n_scan_wgs of the walker (scan_wgs, with scan; none: 0 and NULL), then the history kernel
 hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
                               const ChzScanLaunch *scan, hipStream_t st);
+// chz_history_kernel alone: the last 2 a.kp a.rail_bytes bytes of [history | this call] per source into a.hist_next
+hipError_t launch_channelizer_history(const ChzLaunch &a, hipStream_t st);
 // chz_frac_kernel alone, for a.den = 2, 4, 8 (iqd_chan_frac.hip); launch_channelizer adds the history kernel
 hipError_t launch_channelizer_frac(const ChzLaunch &a, uint32_t n_wgs, hipStream_t s);
 // chz_survey_kernel for a.den = 1, 2, 4, 8 and the kernel that divides the sums (iqd_chan_survey.hip)
 hipError_t launch_channelizer_survey(const ChzLaunch &a, const ChzSurveyLaunch &s, hipStream_t st);
 
-// chz_fmt_kernel for f.rail_bytes = 1, 2 and its history kernel (iqd_chan_fmt.hip)
+// chz_fmt_kernel for f.a.rail_bytes = 1, 2 (iqd_chan_fmt.hip) and the history kernel
 hipError_t launch_channelizer_fmt(const ChzFmtLaunch &f, uint32_t n_wgs, hipStream_t st);
 
 // chz_gain_kernel alone: n_wgs workgroups a.wgs of gain-following tiles, one launch whatever g.n_blocks (iqd_chan_gain.hip)

@@ -10,7 +10,8 @@
 //          byte pack into a per-wave LDS staging row of 8 channels x 128 bytes
 //   store  one 16-byte store per lane: 8 lanes write one channel's 128 contiguous bytes (whole sectors)
 // A second, tiny kernel writes each source's last Kp samples (the next call's history) with vector stores.
-// The device pieces shared with the fractional-rate kernel (iqd_chan_frac.hip) are in iqd_chan_dev.h.
+// The kernels of this file and of iqd_chan_{frac,survey,fmt,gain}.hip are put together from the pieces of iqd_chan_dev.h:
+// here chz_walk<1, NQR, 1, CHZ_CONSECUTIVE> with ChzFinish and ChzRowSink<1, MAG> (MAG: the scan walker's squelch magnitude).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,75 +21,6 @@
 
 namespace iqd {
 
-// One wave: its tile's outputs [m0, m0 + nloc) (nloc a multiple of 32) from the staged window, through the MFMA, the
-// epilogue and the 16-byte stores.  A: the tile's operands in registers (NQR > 0) or amat, read per group (NQR = 0).
-// MAG: also sums SignalDetector's magnitude of the bytes this lane stores (the scan walker's squelch).
-template <int NQR, bool MAG>
-__device__ __forceinline__ void chz_tile_outputs(const ChzLaunch &a, const uint8_t *win, const uint32_t *sp, uint8_t *stage,
-                                                 const chz_v4i (&A)[NQR > 0 ? NQR : 1][2], const uint4 *amat,
-                                                 const uint32_t (&inc)[2], const uint32_t (&shv)[2], const int32_t (&rnd)[2],
-                                                 uint32_t st_ch, uint32_t m0, uint32_t nloc, uint32_t &mag,
-                                                 uint32_t grp0 = 0, uint32_t gstride = 1)
-{
-    const uint32_t lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
-    const uint32_t st_cl = lane >> 3, st_piece = lane & 7;
-    const uint32_t M = a.m, nq = a.nq;
-    const chz_v4i zero = {0, 0, 0, 0};
-    for (uint32_t grp = grp0; grp * CHZ_GROUP < nloc; grp += gstride) {
-        const uint32_t ntl = min(4u, (nloc - grp * CHZ_GROUP) / 16);   // 2 or 4
-        // two 16-output tiles at a time: four independent accumulator chains (tile x plane)
-        for (uint32_t tp = 0; tp < ntl; tp += 2) {
-            chz_v4i acc[2][2] = {{zero, zero}, {zero, zero}};
-            const uint32_t obase = 2 * M * (grp * CHZ_GROUP + 16 * tp + col + 1) + 16 * g;
-            if (NQR > 0) {
-#pragma unroll
-                for (int q = 0; q < NQR; q++)
-                    if (q < (int)nq) {
-#pragma unroll
-                        for (int t = 0; t < 2; t++) {
-                            const chz_v4i b = chz_b_operand(win, obase + 2 * M * 16 * t + 64 * q);
-                            acc[t][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[q][0], b, acc[t][0], 0, 0, 0);
-                            acc[t][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[q][1], b, acc[t][1], 0, 0, 0);
-                        }
-                    }
-            } else {
-                for (uint32_t q = 0; q < nq; q++) {
-                    const chz_v4i alo = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 0) * 64]);
-                    const chz_v4i ahi = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 1) * 64]);
-#pragma unroll
-                    for (int t = 0; t < 2; t++) {
-                        const chz_v4i b = chz_b_operand(win, obase + 2 * M * 16 * t + 64 * q);
-                        acc[t][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(alo, b, acc[t][0], 0, 0, 0);
-                        acc[t][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ahi, b, acc[t][1], 0, 0, 0);
-                    }
-                }
-            }
-            // epilogue: lane (col, g) holds rows 4 g .. 4 g + 3 = channels 2 g, 2 g + 1 (re, im) of output col of each tile
-#pragma unroll
-            for (int t = 0; t < 2; t++) {
-                const uint32_t jt = 16 * (tp + t) + col;                       // output within the group
-                const uint32_t n32 = a.nbase + (m0 + grp * CHZ_GROUP + jt) * M + M - 1;   // mod 2^32
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    const uint32_t p = sp[(n32 * inc[i]) >> 20];
-                    const uint32_t v = chz_epilogue(acc[t][0][2 * i], acc[t][1][2 * i], acc[t][0][2 * i + 1],
-                                                    acc[t][1][2 * i + 1], p, rnd[i], shv[i]);
-                    *(uint16_t *)(stage + (2 * g + i) * (2 * CHZ_GROUP) + 2 * jt) = (uint16_t)v;
-                }
-            }
-        }
-        chz_wave_fence();
-        if (st_ch != CHZ_NONE && st_piece * 8 < ntl * 16) {
-            const uint4 v = *(const uint4 *)(stage + st_cl * (2 * CHZ_GROUP) + 16 * st_piece);
-            *(uint4 *)(a.out + (size_t)st_ch * a.out_row + 2 * (size_t)(m0 + grp * CHZ_GROUP) + 16 * st_piece) = v;
-            if (MAG)
-                mag += magnitude2(v.x ^ 0x80808080u) + magnitude2(v.y ^ 0x80808080u) + magnitude2(v.z ^ 0x80808080u) +
-                       magnitude2(v.w ^ 0x80808080u);
-        }
-        chz_wave_fence();
-    }
-}
-
 template <int NQR>   // NQR > 0: nq <= NQR, the A operands stay in registers; 0: they are read per group
 __global__ __launch_bounds__(512) void chz_kernel(const ChzLaunch a)
 {
@@ -96,44 +28,21 @@ __global__ __launch_bounds__(512) void chz_kernel(const ChzLaunch a)
     uint32_t *sp = (uint32_t *)chz_lds;
     uint8_t *stage_all = chz_lds + CHZ_PHASOR * 4;
     uint8_t *win = chz_lds + CHZ_LDS_FIXED;
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const uint32_t wave = threadIdx.x >> 6;
     const ChzWg w = a.wgs[blockIdx.y];
     const uint32_t m0 = blockIdx.x * a.t_blk;
     const uint32_t nloc = min(a.t_blk, a.n_out - m0);           // a multiple of 32
-    const uint32_t nq = a.nq;
 
-    for (uint32_t i = tid; i < CHZ_PHASOR / 4; i += blockDim.x) ((uint4 *)sp)[i] = ((const uint4 *)a.phasor)[i];
-    chz_stage_window(a, w.source, m0, nloc, win);
+    chz_phasor_to_lds(a, sp);
+    chz_stage_window<CHZ_U8>(a, w.source, m0, nloc, win);
     __syncthreads();
     if (wave >= w.n_tiles) return;
 
-    const uint32_t tile = w.first_tile + wave;
-    const ChzTile *T = a.tiles + tile;
-    const uint32_t g = lane >> 4;
-    uint32_t inc[2], shv[2];
-    int32_t rnd[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        inc[i] = T->inc[2 * g + i];
-        const uint32_t L = T->shift[2 * g + i];
-        shv[i] = 22 - L;
-        rnd[i] = 1 << (21 - L);
-    }
-    const uint32_t st_ch = T->ch[lane >> 3];
-    uint8_t *stage = stage_all + wave * (CHZ_TILE_CH * 2 * CHZ_GROUP);
-    const uint4 *amat = a.amat + (size_t)tile * nq * 2 * 64 + lane;
-
-    chz_v4i A[NQR > 0 ? NQR : 1][2];
-    if (NQR > 0) {
-#pragma unroll
-        for (int q = 0; q < NQR; q++)
-            if (q < (int)nq) {
-                A[q][0] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 0) * 64]);
-                A[q][1] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 1) * 64]);
-            }
-    }
-    uint32_t mag = 0;
-    chz_tile_outputs<NQR, false>(a, win, sp, stage, A, amat, inc, shv, rnd, st_ch, m0, nloc, mag);
+    ChzLaneTile<NQR> T;
+    T.params(a, w.first_tile + wave, 1, true);
+    T.load_a(a.nq);
+    ChzRowSink<1, false> sink{stage_all + wave * (CHZ_TILE_CH * 2 * CHZ_GROUP), T.st_ch, 0};
+    chz_walk<1, NQR, 1, CHZ_CONSECUTIVE>(a, win, 0, sp, T.A, T.amat, T.inc, m0, nloc, 0, 1, T.fin, sink);
 }
 
 // The scan walker (include/iqdemod.h: iqd_channelizer_follow_scanner).  One workgroup owns up to s.waves tiles of
@@ -143,7 +52,7 @@ __global__ __launch_bounds__(512) void chz_kernel(const ChzLaunch a)
 //      into the block's increment d_b, or into silence (out of band: zero taps, every output byte 0x80);
 //   2. every lane builds its own part of the tile's A operands for d_b - exactly chz_pack_slot's bytes - from the
 //      prototype and the phasor table in LDS (in registers for nq <= CHZ_NQ_REG, else in the tile's slice of a.amat);
-//   3. the block's outputs go through chz_tile_outputs, window by window, summing the squelch magnitude;
+//   3. the block's outputs go through chz_walk, window by window, summing the squelch magnitude;
 //   4. the owner lanes step the shadow copy of their engine channel's per-block recurrence in squelch_track_kernel's
 //      order: dBFS against the threshold with the IF gain in force, the tracker, scanner_step on a rejected block while
 //      scanning, agc_run.
@@ -162,26 +71,18 @@ __global__ __launch_bounds__(512) void chz_scan_kernel(const ChzLaunch a, const 
     const ChzWg w = a.wgs[blockIdx.x];
     const uint32_t kp = a.kp, nq = a.nq;
 
-    for (uint32_t i = tid; i < CHZ_PHASOR / 4; i += blockDim.x) ((uint4 *)sp)[i] = ((const uint4 *)a.phasor)[i];
+    chz_phasor_to_lds(a, sp);
     for (uint32_t i = tid; i < kp / 8; i += blockDim.x) ((uint4 *)proto)[i] = ((const uint4 *)s.proto)[i];
 
     const bool active = tl < w.n_tiles;
     const uint32_t tile = w.first_tile + (active ? tl : 0);
-    const ChzTile *T = a.tiles + tile;
-    const uint32_t col = lane & 15, g = lane >> 4;
-    uint32_t shv[2];
-    int32_t rnd[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const uint32_t L = T->shift[2 * g + i];
-        shv[i] = 22 - L;
-        rnd[i] = 1 << (21 - L);
-    }
-    const uint32_t st_ch = active ? T->ch[lane >> 3] : CHZ_NONE;
+    ChzLaneTile<NQR> T;                                           // (its increments and A operands are built here, per block)
+    T.params(a, tile, 1, active);
+    const uint32_t col = lane & 15, g = lane >> 4, st_ch = T.st_ch;
     uint8_t *stage = stage_all + (tid >> 6) * (CHZ_TILE_CH * 2 * CHZ_GROUP);
-    uint4 *amat = const_cast<uint4 *>(a.amat) + (size_t)tile * nq * 2 * 64 + lane;
+    uint4 *amat = const_cast<uint4 *>(T.amat);
     const uint32_t a_slot = col >> 1, a_row = col & 1;           // the A rows this lane builds: slot a_slot, Ar / Ai
-    const bool a_real = active && T->ch[a_slot] != CHZ_NONE;
+    const bool a_real = active && a.tiles[tile].ch[a_slot] != CHZ_NONE;
 
     // the shadow state, in the owner lane of each channel
     const bool owner = (lane & 7) == 0 && st_ch != CHZ_NONE;
@@ -195,18 +96,16 @@ __global__ __launch_bounds__(512) void chz_scan_kernel(const ChzLaunch a, const 
     const unsigned long long centre = s.centre[w.source];
     const Consts &cst = *s.consts;
 
-    chz_v4i A[NQR > 0 ? NQR : 1][2];
     for (uint32_t b = 0; b < s.n_blocks; b++) {
         // 1. this block's increment, or silence
         uint32_t d = 0;
         const uint32_t on = owner && chz_tuning(a.m, centre, ss.current_hz, rot, &d) ? 1u : 0u;
-        uint32_t inc[2];
 #pragma unroll
-        for (int i = 0; i < 2; i++) inc[i] = (uint32_t)__shfl((int)d, (int)(8 * (2 * g + i)));
+        for (int i = 0; i < 2; i++) T.inc[i] = (uint32_t)__shfl((int)d, (int)(8 * (2 * g + i)));
         const uint32_t d_a = (uint32_t)__shfl((int)d, (int)(8 * a_slot));
         const uint32_t on_a = (uint32_t)__shfl((int)on, (int)(8 * a_slot));   // (every lane: the owner must be active)
         const bool live = a_real && on_a != 0;
-        if (tid < CHZ_WAVES * 8) magsum[(b & 1) * CHZ_WAVES * 8 + tid] = 0;
+        chz_block_open(magsum, b);
         // 2. A operands: K-index kappa = 64 q + 16 g + j is sample kp - 1 - kappa / 2, rail kappa & 1 (iqd_chan.h)
         __syncthreads();   // (the prototype; and the previous block's last window has been read)
         auto build = [&](uint32_t q, uint4 &vlo, uint4 &vhi) {
@@ -236,8 +135,8 @@ __global__ __launch_bounds__(512) void chz_scan_kernel(const ChzLaunch a, const 
                 if (q < (int)nq) {
                     uint4 vlo, vhi;
                     build((uint32_t)q, vlo, vhi);
-                    A[q][0] = __builtin_bit_cast(chz_v4i, vlo);
-                    A[q][1] = __builtin_bit_cast(chz_v4i, vhi);
+                    T.A[q][0] = __builtin_bit_cast(chz_v4i, vlo);
+                    T.A[q][1] = __builtin_bit_cast(chz_v4i, vhi);
                 }
         } else if (active && part == 0) {   // one wave per tile writes them; the window's barrier comes before any read
             for (uint32_t q = 0; q < nq; q++) {
@@ -248,25 +147,19 @@ __global__ __launch_bounds__(512) void chz_scan_kernel(const ChzLaunch a, const 
             }
         }
         // 3. the block's outputs, window by window
-        uint32_t mag = 0;
+        ChzRowSink<1, true> sink{stage, st_ch, 0};
         const uint32_t mb = b * s.block_out, me = mb + s.block_out;
         for (uint32_t m0 = mb; m0 < me; m0 += s.t_blk) {
             const uint32_t nloc = min(s.t_blk, me - m0);
             if (m0 != mb) __syncthreads();
-            chz_stage_window(a, w.source, m0, nloc, win);
+            chz_stage_window<CHZ_U8>(a, w.source, m0, nloc, win);
             __syncthreads();
-            if (active) chz_tile_outputs<NQR, true>(a, win, sp, stage, A, amat, inc, shv, rnd, st_ch, m0, nloc, mag, part, s.wpt);
+            if (active) chz_walk<1, NQR, 1, CHZ_CONSECUTIVE>(a, win, 0, sp, T.A, amat, T.inc, m0, nloc, part, s.wpt, T.fin, sink);
         }
-        // 4. the squelch's magnitude per channel (its 8 storing lanes), then the shadow step
-        mag += (uint32_t)__shfl_xor((int)mag, 1);
-        mag += (uint32_t)__shfl_xor((int)mag, 2);
-        mag += (uint32_t)__shfl_xor((int)mag, 4);
-        uint32_t *ms = magsum + (b & 1) * CHZ_WAVES * 8 + tl * 8 + (lane >> 3);
-        if (owner) atomicAdd(ms, mag);
-        __syncthreads();
+        // 4. the squelch's magnitude per channel, then the shadow step
+        const uint32_t *ms = chz_block_close(magsum, b, tl, sink.mag, owner);
         if (owner) {
-            mag = *ms;
-            const uint32_t avg = mag / s.block_out;
+            const uint32_t avg = *ms / s.block_out;
             const int32_t dbfs = (int32_t)((uint32_t)magnitude_dbfs(cst, avg) - gain);
             const uint32_t present = dbfs >= threshold ? 1u : 0u;
             const uint32_t allowed = present | tracking;
@@ -277,15 +170,22 @@ __global__ __launch_bounds__(512) void chz_scan_kernel(const ChzLaunch a, const 
     }
 }
 
-// the next call's history: the last 2 kp bytes of [history | this call] per source
+// the next call's history: the last 2 kp B raw bytes of [history | this call] per source
 __global__ void chz_history_kernel(const ChzLaunch a)
 {
-    const uint32_t hb = 2 * a.kp;
+    const uint32_t hb = 2 * a.kp * a.rail_bytes;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= a.n_sources * hb) return;
     const uint32_t s = t / hb, i = t - s * hb;
     const int64_t b = (int64_t)a.bytes_per_source - hb + i;
     a.hist_next[t] = b < 0 ? a.hist[(size_t)s * hb + hb + b] : a.wide[(size_t)s * a.bytes_per_source + b];
+}
+
+hipError_t launch_channelizer_history(const ChzLaunch &a, hipStream_t st)
+{
+    const uint32_t nh = a.n_sources * 2 * a.kp * a.rail_bytes;
+    hipLaunchKernelGGL(chz_history_kernel, dim3((nh + 255) / 256), dim3(256), 0, st, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_fixed_wgs, const ChzWg *scan_wgs, uint32_t n_scan_wgs,
@@ -313,9 +213,7 @@ hipError_t launch_channelizer(const ChzLaunch &a, uint32_t n_fixed_wgs, const Ch
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    const uint32_t nh = a.n_sources * 2 * a.kp;
-    hipLaunchKernelGGL(chz_history_kernel, dim3((nh + 255) / 256), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return launch_channelizer_history(a, st);
 }
 
 }  // namespace iqd

@@ -6,9 +6,9 @@
 //
 // Grid: one workgroup per (source, window of t_blk outputs, row of up to 8 point tiles); the point tiles (8 points, one
 // wave) are shared by all sources.  One body for every rate: an MFMA tile is 16 outputs of one residue rho of a store
-// group (integer decimation: Q = 1, rho = 0, 16 consecutive outputs), exactly chz_frac_tile_outputs' schedule, which at
-// Q = 1 is chz_tile_outputs'.  The A operands stay in registers at Q = 1 up to CHZ_NQ_REG chunks, else they are read
-// per pair of tiles (L2).
+// group (integer decimation: Q = 1, rho = 0, 16 consecutive outputs): chz_walk<Q, NQR, 1, CHZ_PER_RESIDUE> with ChzFinish
+// (iqd_chan_dev.h) and the sink below.  The A operands stay in registers at Q = 1 up to CHZ_NQ_REG chunks, else they are
+// read per pair of tiles (L2).
 //
 // A lane sums the magnitudes of its two points over the outputs it meets; a pair of tiles never crosses a block boundary
 // (Q = 1: 32 consecutive outputs and blocks are multiples of 32 outputs; Q > 1: blocks are whole store groups), so the
@@ -24,53 +24,16 @@
 
 namespace iqd {
 
-template <int Q, int NQR>   // NQR > 0 (Q = 1 only): nq <= NQR, the A operands stay in registers
-__global__ __launch_bounds__(512) void chz_survey_kernel(const ChzLaunch a, const ChzSurveyLaunch s)
-{
-    static_assert(NQR == 0 || Q == 1, "register-resident A operands are for the integer decimator");
-    extern __shared__ __attribute__((aligned(16))) uint8_t chz_lds[];
-    constexpr uint32_t G = Q == 1 ? CHZ_GROUP : chz_frac_group(Q), NT = G / 16, TG = G / Q;
-    uint32_t *sp = (uint32_t *)chz_lds;
-    uint8_t *win = chz_lds + CHZ_PHASOR * 4;
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, g = lane >> 4;
-    uint32_t x = blockIdx.x;
-    const uint32_t row = x % s.rows;
-    x /= s.rows;
-    const uint32_t m0 = (x % s.n_win) * a.t_blk, source = x / s.n_win;
-    const uint32_t nloc = min(a.t_blk, a.n_out - m0);           // Q = 1: a multiple of 32; else whole groups
-    const uint32_t P = a.m, nq = a.nq, t0 = m0 / Q;
-
-    for (uint32_t i = tid; i < CHZ_PHASOR / 4; i += blockDim.x) ((uint4 *)sp)[i] = ((const uint4 *)a.phasor)[i];
-    chz_stage_window(a, source, t0, nloc / Q, win);
-    __syncthreads();
-    const uint32_t tile = row * CHZ_WAVES + wave;
-    if (tile >= s.n_tiles) return;
-
-    const ChzTile *T = a.tiles + tile;
-    uint32_t inc[2], shv[2], pt[2], mag[2] = {0, 0};
-    int32_t rnd[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        inc[i] = T->inc[2 * g + i];
-        const uint32_t L = T->shift[2 * g + i];
-        shv[i] = 22 - L;
-        rnd[i] = 1 << (21 - L);
-        pt[i] = T->ch[2 * g + i];                               // the point, CHZ_NONE = padding
-    }
-    const uint4 *amat = a.amat + (size_t)tile * Q * nq * 2 * 64 + lane;
-    chz_v4i A[NQR > 0 ? NQR : 1][2];
-    if (NQR > 0) {
-#pragma unroll
-        for (int q = 0; q < NQR; q++)
-            if (q < (int)nq) {
-                A[q][0] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 0) * 64]);
-                A[q][1] = __builtin_bit_cast(chz_v4i, amat[(q * 2 + 1) * 64]);
-            }
-    }
-
-    uint32_t *sums = s.sums + (size_t)source * s.n_blocks * s.n_points;
-    uint32_t blk = m0 / s.block_out, blk_end = (blk + 1) * s.block_out;   // (outputs; n_out < 2^31)
-    auto flush = [&]() {
+// Sink of chz_walk: the magnitude of each byte pair, summed in the lane per point; flushed when a pair's block changes
+struct ChzSurveySink {
+    static constexpr bool UNROLL = false;
+    uint32_t *sums;                                             // [n_points] of the source's block being summed
+    uint32_t n_points, block_out;
+    uint32_t pt[2];                                             // column 0, the lane that adds: its points; else CHZ_NONE
+    uint32_t blk_end;                                           // that block's end (outputs; n_out < 2^31)
+    uint32_t mag[2];
+    __device__ __forceinline__ void flush()
+    {
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             uint32_t v = mag[i];
@@ -78,71 +41,53 @@ __global__ __launch_bounds__(512) void chz_survey_kernel(const ChzLaunch a, cons
             v += (uint32_t)__shfl_xor((int)v, 2);
             v += (uint32_t)__shfl_xor((int)v, 4);
             v += (uint32_t)__shfl_xor((int)v, 8);
-            if (col == 0 && pt[i] != CHZ_NONE) atomicAdd(sums + (size_t)blk * s.n_points + pt[i], v);
+            if (pt[i] != CHZ_NONE) atomicAdd(sums + pt[i], v);
             mag[i] = 0;
         }
-    };
-
-    const chz_v4i zero = {0, 0, 0, 0};
-    for (uint32_t grp = 0; grp * G < nloc; grp++) {
-        const uint32_t ntl = Q == 1 ? min(NT, (nloc - grp * G) / 16) : NT;   // Q = 1: 2 or 4
-        for (uint32_t tp = 0; tp < ntl; tp += 2) {
-            // the block of this pair's outputs: they begin at mpos and lie in one block
-            const uint32_t mpos = m0 + grp * G + (Q == 1 ? 16 * tp : 0);
-            if (mpos >= blk_end) {                               // (a pair advances by no more than a block)
-                flush();
-                blk++;
-                blk_end += s.block_out;
-            }
-            chz_v4i acc[2][2] = {{zero, zero}, {zero, zero}};
-            uint32_t e[2], tt[2], ob[2];
-            const uint4 *am[2];
-#pragma unroll
-            for (int t = 0; t < 2; t++) {
-                const uint32_t rho = (tp + t) % Q;
-                e[t] = ((rho + 1) * P - 1) / Q;
-                tt[t] = grp * TG + 16 * ((tp + t) / Q) + col;    // wide step within the window
-                ob[t] = 2 * (P * tt[t] + e[t] + 1) + 16 * g;
-                am[t] = amat + (size_t)rho * nq * 2 * 64;
-            }
-            if (NQR > 0) {
-#pragma unroll
-                for (int q = 0; q < NQR; q++)
-                    if (q < (int)nq) {
-#pragma unroll
-                        for (int t = 0; t < 2; t++) {
-                            const chz_v4i b = chz_b_operand(win, ob[t] + 64 * q);
-                            acc[t][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[q][0], b, acc[t][0], 0, 0, 0);
-                            acc[t][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[q][1], b, acc[t][1], 0, 0, 0);
-                        }
-                    }
-            } else {
-                for (uint32_t q = 0; q < nq; q++) {
-#pragma unroll
-                    for (int t = 0; t < 2; t++) {
-                        const chz_v4i alo = __builtin_bit_cast(chz_v4i, am[t][(q * 2 + 0) * 64]);
-                        const chz_v4i ahi = __builtin_bit_cast(chz_v4i, am[t][(q * 2 + 1) * 64]);
-                        const chz_v4i b = chz_b_operand(win, ob[t] + 64 * q);
-                        acc[t][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(alo, b, acc[t][0], 0, 0, 0);
-                        acc[t][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ahi, b, acc[t][1], 0, 0, 0);
-                    }
-                }
-            }
-            // epilogue: lane (col, g) holds points 2 g, 2 g + 1 of one output of each tile; its magnitude, not its bytes
-#pragma unroll
-            for (int t = 0; t < 2; t++) {
-                const uint32_t n32 = a.nbase + (t0 + tt[t]) * P + e[t];      // mod 2^32
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    const uint32_t p = sp[(n32 * inc[i]) >> 20];
-                    const uint32_t v = chz_epilogue(acc[t][0][2 * i], acc[t][1][2 * i], acc[t][0][2 * i + 1],
-                                                    acc[t][1][2 * i + 1], p, rnd[i], shv[i]);
-                    mag[i] += magnitude2(v ^ 0x8080u);           // (the upper pair: signed 0, 0 - magnitude 0)
-                }
-            }
+    }
+    // the block of this pair's outputs: they begin at mpos and lie in one block
+    __device__ __forceinline__ void begin(uint32_t mpos)
+    {
+        if (mpos >= blk_end) {                                   // (a pair advances by no more than a block)
+            flush();
+            sums += n_points;
+            blk_end += block_out;
         }
     }
-    flush();
+    // lane (col, g) holds points 2 g, 2 g + 1 of one output of each tile; its magnitude, not its bytes
+    // (the upper pair: signed 0, 0 - magnitude 0)
+    __device__ __forceinline__ void put(int i, uint32_t, uint32_t v) { mag[i] += magnitude2(v ^ 0x8080u); }
+    __device__ __forceinline__ void end(const ChzLaunch &, uint32_t, uint32_t) {}
+};
+
+template <int Q, int NQR>   // NQR > 0 (Q = 1 only): nq <= NQR, the A operands stay in registers
+__global__ __launch_bounds__(512) void chz_survey_kernel(const ChzLaunch a, const ChzSurveyLaunch s)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t chz_lds[];
+    uint32_t *sp = (uint32_t *)chz_lds;
+    uint8_t *win = chz_lds + CHZ_PHASOR * 4;
+    const uint32_t wave = threadIdx.x >> 6;
+    uint32_t x = blockIdx.x;
+    const uint32_t row = x % s.rows;
+    x /= s.rows;
+    const uint32_t m0 = (x % s.n_win) * a.t_blk, source = x / s.n_win;
+    const uint32_t nloc = min(a.t_blk, a.n_out - m0);           // Q = 1: a multiple of 32; else whole groups
+
+    chz_phasor_to_lds(a, sp);
+    chz_stage_window<CHZ_U8>(a, source, m0 / Q, nloc / Q, win);
+    __syncthreads();
+    const uint32_t tile = row * CHZ_WAVES + wave;
+    if (tile >= s.n_tiles) return;
+
+    ChzLaneTile<NQR> T;
+    T.params(a, tile, Q, true);
+    T.load_a(a.nq);
+    const uint32_t blk = m0 / s.block_out;
+    const bool adds = (threadIdx.x & 15) == 0;
+    ChzSurveySink sink{s.sums + ((size_t)source * s.n_blocks + blk) * s.n_points, s.n_points, s.block_out,
+                       {adds ? T.ch[0] : CHZ_NONE, adds ? T.ch[1] : CHZ_NONE}, (blk + 1) * s.block_out, {0, 0}};
+    chz_walk<Q, NQR, 1, CHZ_PER_RESIDUE>(a, win, 0, sp, T.A, T.amat, T.inc, m0, nloc, 0, 1, T.fin, sink);
+    sink.flush();
 }
 
 // sums -> magnitudes: floor(sum / outputs of a block)
