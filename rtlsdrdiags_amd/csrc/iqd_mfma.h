@@ -282,12 +282,12 @@ __device__ __forceinline__ uint32_t lds_load_relaxed(const uint32_t *p)
     return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// lane 0 adds 1 to an LDS word (exec is all ones wherever this is used); the plain HIP form costs a dozen
-// instructions of "which lane is first" bookkeeping per call
-__device__ __forceinline__ void lds_signal(const uint32_t *p)
+// lane 0 adds `n` (1 unless said otherwise) to an LDS word (exec is all ones wherever this is used); the plain HIP form costs
+// a dozen instructions of "which lane is first" bookkeeping per call
+__device__ __forceinline__ void lds_signal(const uint32_t *p, uint32_t n = 1u)
 {
-    const uint32_t addr = (uint32_t)(uintptr_t)p, one = 1u;
-    asm volatile("s_mov_b64 exec, 1\n\tds_add_u32 %0, %1\n\ts_mov_b64 exec, -1" :: "v"(addr), "v"(one) : "memory");
+    const uint32_t addr = (uint32_t)(uintptr_t)p;
+    asm volatile("s_mov_b64 exec, 1\n\tds_add_u32 %0, %1\n\ts_mov_b64 exec, -1" :: "v"(addr), "v"(n) : "memory");
 }
 
 // byte offset of granule q (4 samples) of ring row j inside a slot: XOR swizzle, conflict-free for the

@@ -1,6 +1,6 @@
 // WBFM chain as a streaming pipeline (gfx950): launch descriptor and host helpers.
 //
-// One persistent workgroup of 15 waves per CU.  The exact atan2 half table (129 rows, the reference's
+// One persistent workgroup of 16 waves per CU.  The exact atan2 half table (129 rows, the reference's
 // table is odd in y bit for bit: WbFmDemodulator.cc:159-170) lives in LDS for the lifetime of the
 // workgroup.  A *segment* is what the tile kernels call a tile: a run of consecutive samples of one
 // channel with its lead-in, cold-started and verified against its predecessor (wbfm_verify_kernel).
@@ -11,7 +11,11 @@
 //       high byte plane, rotation's rail selection folded into the tap matrices) -> table index ->
 //       ds_read_b32 gather -> delta theta, branch cut, K, b0 -> u[n] into an LDS ring slot
 //   3 IIR waves, 64 segments each (one per lane): u[n] from the ring -> de-emphasis recurrence,
-//       (int16), /4 /4 /2 Q15 decimators with their histories in registers -> PCM
+//       (int16), /4 /4 Q15 decimators with their histories in registers -> a pair of stage-2 outputs per piece
+//       into the ring's y2 ring (LDS, ST_Y2_DEPTH pieces deep)
+//   1 audio wave, the same 64 segments of EVERY ring in turn: the pair from the y2 ring -> /2 with 40 taps
+//       (20 + 4 pairs of history per ring in registers) -> PCM, and the y2 parts of the boundary records.
+//       It is hardware wave 15, which lands on the one SIMD that carries no IIR wave.
 //
 // Reference: WbFmDemodulator.cc:383-562 behind IqDataProcessor.cc:735-749.
 #pragma once
@@ -21,9 +25,12 @@
 
 namespace iqd {
 
-constexpr int ST_WAVES = 15;
+constexpr int ST_WAVES = 16;
 constexpr int ST_THREADS = 64 * ST_WAVES;
 constexpr int ST_RINGS = 3;                 // = IIR waves
+constexpr int ST_AUDIO_WAVE = ST_WAVES - 1; // the wave that runs every ring's last decimator (st_audio_wave)
+constexpr int D4_WAVES = 15;                // the FM / AM / SSB pipelines (iqd_stream2.hip): 3 consumer + 12 P waves
+constexpr int D4_THREADS = 64 * D4_WAVES;
 constexpr int ST_P_PER_RING = 4;            // P waves feeding one ring (16 segments each)
 constexpr int ST_SEGS = 64 * ST_RINGS;      // segments per workgroup and round when all its rings run (StreamArgs::rings)
 constexpr int ST_HALO = FORCED_BACK;         // lead-in of every segment, 768 samples.  A warm segment (a call's first) runs
@@ -55,8 +62,43 @@ constexpr int ST_SLOT_BYTES = 64 * 16 * 4;  // one window of one ring: 64 segmen
 #endif
 constexpr int ST_DEPTH = IQD_ST_DEPTH;      // pieces a ring holds (a power of two)
 constexpr int ST_RING_SLOTS = 2 * ST_DEPTH;
-constexpr int ST_SYNC_WORDS = 24;            // per ring: [0..3] `full` of its slots, [4] `consumed`
-constexpr int ST_LDS_BYTES = ST_TABLE_BYTES + ST_RINGS * ST_RING_SLOTS * ST_SLOT_BYTES + ST_SYNC_WORDS * 4;
+constexpr int ST_SYNC_WORDS = 24;            // per ring: [0..3] `full` of its slots, [4] `consumed`, [5] y2 ring `full`, [6] y2 ring `consumed`
+constexpr int ST_SYNC_Y2_FULL = 5, ST_SYNC_Y2_CONSUMED = 6;
+
+// The y2 ring of an IIR ring: the IIR wave hands each piece's pair of stage-2 outputs (one dword per lane) to the audio wave.
+#ifndef IQD_ST_Y2_DEPTH
+#define IQD_ST_Y2_DEPTH 4
+#endif
+#ifndef IQD_ST_Y2_EVERY
+#define IQD_ST_Y2_EVERY 1
+#endif
+constexpr int ST_Y2_DEPTH = IQD_ST_Y2_DEPTH;   // pieces it holds (a power of two)
+constexpr int ST_Y2_EVERY = IQD_ST_Y2_EVERY;   // the IIR wave signals once per this many pieces (1 or 4; a ring hands over whole quads of pieces)
+constexpr int ST_Y2_SLOT_BYTES = 64 * 4;
+constexpr int ST_Y2_RING_BYTES = ST_Y2_DEPTH * ST_Y2_SLOT_BYTES;
+// Piece `piece` (counted over the wave's whole life, all rounds) of a y2 ring - the one place that says where it lives and who
+// may touch it when; both sides of the hand-over use it, and so does the CPU tier's step model (tests/test_emu_y2_ring_model.py).
+// Both counters count PIECES: `full` = pieces written and signalled, `consumed` = pieces read.  Compare as (int32_t)(counter - need) >= 0.
+struct StY2Piece {
+    uint32_t slot;            // which of the ring's `depth` slots
+    uint32_t need_consumed;   // the IIR wave may write once `consumed` has reached this: piece - depth has been read
+    uint32_t need_full;       // the audio wave may read once `full` has reached this
+    uint32_t add_full;        // what the IIR wave adds to `full` after writing: `every` behind the last piece of a group, else 0
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr StY2Piece st_y2_piece(uint32_t piece, uint32_t depth, uint32_t every)
+{
+    return StY2Piece{piece & (depth - 1u), piece + 1u - depth, piece + 1u, (piece + 1u) % every == 0u ? every : 0u};
+}
+constexpr bool st_y2_ring_ok(uint32_t depth, uint32_t every) { return depth >= 1u && (depth & (depth - 1u)) == 0u && every >= 1u && depth >= every; }
+static_assert(st_y2_ring_ok(ST_Y2_DEPTH, ST_Y2_EVERY), "a group of pieces is signalled only when complete: the ring must hold one");
+static_assert(ST_Y2_EVERY == 1 || ST_Y2_EVERY == 4, "a ring hands over multiples of four pieces per round");
+
+constexpr int ST_Y2_OFF = ST_TABLE_BYTES + ST_RINGS * ST_RING_SLOTS * ST_SLOT_BYTES;   // the y2 rings sit behind the u[n] rings
+constexpr int ST_SYNC_OFF = ST_Y2_OFF + ST_RINGS * ST_Y2_RING_BYTES;
+constexpr int ST_LDS_BYTES = ST_SYNC_OFF + ST_SYNC_WORDS * 4;
 static_assert(ST_LDS_BYTES <= 160 * 1024, "table + rings must fit the CU's LDS");
 static_assert(ST_HALO % 128 == 0 && ST_HALO + 32 <= TAIL, "the lead-in is whole 128-sample units inside the kept tail");
 

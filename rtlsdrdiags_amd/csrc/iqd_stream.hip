@@ -1,4 +1,4 @@
-// WBFM chain as a streaming pipeline: one persistent 15-wave workgroup per CU (see iqd_stream.h).
+// WBFM chain as a streaming pipeline: one persistent 16-wave workgroup per CU (see iqd_stream.h).
 // hipcc --offload-arch=gfx950 -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
@@ -48,6 +48,9 @@ __device__ __forceinline__ uint32_t st_table_read(uint32_t byte_offset) { return
 #endif
 #ifndef IQD_ST_SLEEP_I
 #define IQD_ST_SLEEP_I 10
+#endif
+#ifndef IQD_ST_SLEEP_A    // the audio wave waiting for a piece of a y2 ring
+#define IQD_ST_SLEEP_A 10
 #endif
 #ifndef IQD_ST_RUNPTR     // 1: the P waves' input addresses as a running pointer (0: piece_address() per piece, A/B builds)
 #define IQD_ST_RUNPTR 1
@@ -413,15 +416,13 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
     }
 }
 
-// ---- IIR wave: 64 segments, u[n] -> PCM ------------------------------------------------------------
+// ---- IIR wave: 64 segments, u[n] -> pairs of stage-2 outputs for the audio wave -----------------------
 struct StIir {
     float y, up;
     uint32_t wlast[2];     // the last 4 (int16)y
     uint32_t wq0[2];       // the first 4 (int16)y of the window just processed
     uint32_t y1h[4];       // the last 8 stage-1 outputs
-    uint32_t y2p[24];      // stage-2 outputs as pairs; variant V of a piece uses [V+1 .. V+20]
     uint32_t y2lo;         // first stage-2 output of the current piece
-    int loud;              // pieces for which a |y2| > AUDIO40_SAFE stays in reach of the 40-tap window
     uint32_t n_sleeps;     // (IQD_ST_WAITSTAT)
     int ring;              // (IQD_ST_TRACE)
     unsigned long long *stamps;
@@ -488,41 +489,33 @@ __device__ __forceinline__ int st_iir_window(const StreamArgs &sa, StIir &s, con
     return acc >> 15;
 }
 
-// /2, 40 taps over the pairs p[1..20] (p[20] newest): without clamps when no loud value is in reach, else in
-// the reference's order with the clamp after every MAC (Decimator_int16.cc:176-238)
-template <int V>
-__device__ __forceinline__ int st_audio(const StreamArgs &sa, const StIir &s, bool quiet, int c14)
-{
-    int acc = c14;
-    if (quiet) {
-#if IQD_ST_DOT2_FROM
-        acc = dot2_from(s.y2p[V + 20], sa.a40p[0], c14);
-#pragma unroll
-        for (int q = 1; q < 20; q++) acc = dot2(s.y2p[V + 20 - q], ST_TAP(a40p, q), acc);
-#else
-#pragma unroll
-        for (int q = 0; q < 20; q++) acc = dot2(s.y2p[V + 20 - q], ST_TAP(a40p, q), acc);
-#endif
-    } else {
-#pragma unroll
-        for (int q = 0; q < 20; q++) {
-            acc = clamp_q30(dot2(s.y2p[V + 20 - q], ST_TAP(a40p, q) & 0xffff0000u, acc));   // newer sample of the pair: h[2q]
-            acc = clamp_q30(dot2(s.y2p[V + 20 - q], ST_TAP(a40p, q) & 0x0000ffffu, acc));   // older: h[2q+1]
-        }
-    }
-    return acc >> 15;
-}
-
 struct StIirSeg {
     StSeg sg;
     int32_t back;          // tile 0: the carried exact state sits `back` samples before the tile; else -1
     float cy_y, cy_u;
     int32_t rec_pos;
     WbfmRecord rec;
-    int16_t *pcm_row;
     StHist *hist;          // this segment's boundary record
     int c14, c15;          // 1 << 14, 1 << 15 in registers (the decimators' rounding terms)
 };
+
+// Whether a ring takes the IIR wave's fast path, from what each of its 64 lanes knows about its segment (not there at all, or
+// cold, of full length and not the keeper of its channel's restart state).  The IIR wave and the audio wave both ask: a fast ring
+// hands its first pair over at position 0, any other from the lead-in's first piece on.
+__device__ __forceinline__ bool st_ring_is_fast(uint32_t valid, int32_t back, int32_t tlen, uint32_t tile_len, bool keeps_restart)
+{
+    return __all(!valid || (back < 0 && tlen == (int32_t)tile_len && !keeps_restart)) != 0;
+}
+
+// The y2 ring of one IIR ring as a lane sees it: its dword of slot 0 and the two counters (iqd_stream.h: st_y2_piece).
+struct StY2Ring {
+    uint8_t *lane_slot0;
+    const uint32_t *full, *consumed;
+};
+__device__ __forceinline__ StY2Ring st_y2_ring(uint8_t *lds, uint32_t *sync, int ring, int lane)
+{
+    return StY2Ring{lds + ST_Y2_OFF + ring * ST_Y2_RING_BYTES + lane * 4, sync + ring * 8 + ST_SYNC_Y2_FULL, sync + ring * 8 + ST_SYNC_Y2_CONSUMED};
+}
 
 // (q.sg.valid bit 1: the segment keeps the channel's restart state - WbfmRecord::pad - at q.rec_pos, and takes its own record
 //  where every full cold segment does, rec_pos_uniform)
@@ -544,14 +537,12 @@ __device__ __forceinline__ void st_iir_marks(const ChainLaunch &a, StIirSeg &q, 
         }
     }
     if ((q.sg.valid & 2u) && pos == rec_pos_uniform) { q.rec.y_out = s.y; q.rec.u_out = s.up; }
-    if (pos == q.sg.tlen) {                            // (a multiple of 128: the pair history sits in y2p[0..19] here)
+    if (pos == q.sg.tlen) {                            // (the last 40 stage-2 outputs are the audio wave's to store: st_audio_wave)
         q.rec.y_end = s.y;
         q.rec.u_end = s.up;
         if (q.sg.valid) {
             ST_STORE16(q.hist->y1_last, s.y1h[0], s.y1h[1], s.y1h[2], s.y1h[3]);
             *(u32x2 *)q.hist->w_last = u32x2{s.wlast[0], s.wlast[1]};
-#pragma unroll
-            for (int k = 0; k < 20; k += 4) ST_STORE16(&q.hist->y2_last[k], s.y2p[k], s.y2p[k + 1], s.y2p[k + 2], s.y2p[k + 3]);
         }
     }
 }
@@ -559,11 +550,13 @@ __device__ __forceinline__ void st_iir_marks(const ChainLaunch &a, StIirSeg &q, 
 // FAST: every segment of the wave is cold and of full length (or not there at all), so the few things that happen at
 // particular positions happen at the SAME position in every lane - one scalar compare per window instead of a dozen
 // per-lane compare-and-select operations - and the lead-in has already been run by st_iir_lead_in().
-template <int V, bool FAST>
-__device__ __forceinline__ int st_iir_piece(const ChainLaunch &a, const StreamArgs &sa, uint8_t *ring_base, const uint32_t *full, uint32_t *consumed,
-                                             uint32_t &wg, StIirSeg &q, StIir &s, int pos, uint32_t rd_off0, uint32_t rd_swz, int lane,
-                                             int rec_pos_uniform)
+// yk: pieces this wave has handed to the audio wave so far (all rounds).
+template <bool FAST>
+__device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamArgs &sa, uint8_t *ring_base, const uint32_t *full, uint32_t *consumed,
+                                             uint32_t &wg, const StY2Ring &y2r, uint32_t &yk, StIirSeg &q, StIir &s, int pos, uint32_t rd_off0,
+                                             uint32_t rd_swz, int lane, int rec_pos_uniform)
 {
+    uint32_t y2_seen = 0;
 #pragma unroll
     for (int half = 0; half < 2; half++) {
         const int wpos = pos + 16 * half;
@@ -589,6 +582,7 @@ __device__ __forceinline__ int st_iir_piece(const ChainLaunch &a, const StreamAr
             u[4 * gq] = u2f(v.x); u[4 * gq + 1] = u2f(v.y); u[4 * gq + 2] = u2f(v.z); u[4 * gq + 3] = u2f(v.w);
         }
         if (half == 1) {   // both windows read: the ring is free for the next piece
+            y2_seen = lds_load_relaxed(y2r.consumed);                // asked early (it returns with the reads above), needed only before the hand-over
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the reads have returned
             lds_signal(consumed);
             ST_TRACE(s.stamps, s.ring, wg, 1);
@@ -604,18 +598,22 @@ __device__ __forceinline__ int st_iir_piece(const ChainLaunch &a, const StreamAr
             if (wpos == 0) ST_STORE16(q.hist->w_first, s.wq0[0], s.wq0[1], s.y1h[2], s.y1h[3]);   // (w_first, y1_first[0..1])
             else *(u32x2 *)&q.hist->y1_first[wpos >> 3] = u32x2{s.y1h[2], s.y1h[3]};
         }
-        const uint32_t mag = (uint32_t)(y2 < 0 ? -y2 : y2);
-        if (mag > (uint32_t)AUDIO40_SAFE) s.loud = 21;
         if (half == 0) s.y2lo = (uint32_t)y2;
-        else s.y2p[V + 20] = pack_lo16(s.y2lo, (uint32_t)y2);
+        else {   // the piece's pair goes to the audio wave: its slot is free once piece yk - ST_Y2_DEPTH has been read
+            const StY2Piece yp = st_y2_piece(yk, ST_Y2_DEPTH, ST_Y2_EVERY);
+            while ((int32_t)(y2_seen - yp.need_consumed) < 0) {
+                __builtin_amdgcn_s_sleep(IQD_ST_SLEEP_I);
+                y2_seen = lds_load_relaxed(y2r.consumed);
+                if (IQD_ST_WAITSTAT) s.n_sleeps++;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            *(uint32_t *)(y2r.lane_slot0 + yp.slot * ST_Y2_SLOT_BYTES) = pack_lo16(s.y2lo, (uint32_t)y2);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (yp.add_full) lds_signal(y2r.full, yp.add_full);
+            yk++;
+        }
     }
-    if (V == 3 && pos >= 96 && pos < 768 && q.sg.valid)   // the four pairs of this run of 128 samples (pos = its last piece)
-        ST_STORE16(&q.hist->y2_first[(pos - 96) >> 5], s.y2p[20], s.y2p[21], s.y2p[22], s.y2p[23]);
     ST_TRACE(s.stamps, s.ring, wg - 1, 2);
-    const bool quiet = !__any(s.loud > 0);
-    const int pcm = quiet ? st_audio<V>(sa, s, true, q.c14) : st_audio<V>(sa, s, false, q.c14);
-    if (s.loud > 0) s.loud--;
-    return pcm;
 }
 
 // The lead-in of a wave whose segments are all cold: only the de-emphasis recurrence (its state is what the lead-in is
@@ -656,18 +654,19 @@ __device__ __forceinline__ void st_iir_wave(const ChainLaunch &a, const StreamAr
     uint8_t *ring_base = lds + ST_TABLE_BYTES + ring * (ST_RING_SLOTS * ST_SLOT_BYTES);
     const uint32_t *full = sync + ring * 8;
     uint32_t *consumed = sync + ring * 8 + 4;
+    const StY2Ring y2r = st_y2_ring(lds, sync, ring, lane);
     const uint32_t rd_off0 = (uint32_t)lane * 64u, rd_swz = ((uint32_t)lane >> 2) & 3u;
     const int n_pieces = (ST_HALO + (int)a.tile_len) >> 5;       // a multiple of 4
     if (ring >= (int)sa.rings) return;
     const uint32_t wg_segs = 64u * sa.rings;
     uint32_t wg = 0;                                             // pieces read so far (all rounds)
+    uint32_t yk = 0;                                             // pieces handed to the audio wave so far (all rounds)
     for (uint32_t round = 0; round < sa.rounds; round++) {
         if ((round * chain_wgs(a) + chain_wg(a)) * wg_segs >= st_id_count(sa)) break;
         const uint32_t sid = (round * chain_wgs(a) + chain_wg(a)) * wg_segs + ring * 64 + lane;
         StIirSeg q;
         int rot_unused;
         q.sg = st_segment_of(a, sa, sid, rot_unused);
-        q.pcm_row = a.pcm + (size_t)q.sg.ch * a.pcm_stride;
         q.hist = sa.hist + (q.sg.valid ? (size_t)q.sg.li * a.tiles_per_ch + q.sg.tile : 0);
         q.back = -1;
         q.cy_y = q.cy_u = 0.f;
@@ -694,17 +693,13 @@ __device__ __forceinline__ void st_iir_wave(const ChainLaunch &a, const StreamAr
         q.rec.u_end = 0.f;
         q.rec.pad[0] = q.rec.pad[1] = 0;
         const bool keeps_restart = rp.keeps_restart != 0;
-        if (keeps_restart) q.sg.valid |= 2u;
         StIir s;
         s.y = 0.f; s.up = 0.f;
         s.wlast[0] = s.wlast[1] = 0;
         s.wq0[0] = s.wq0[1] = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) s.y1h[k] = 0;
-#pragma unroll
-        for (int k = 0; k < 24; k++) s.y2p[k] = 0;
         s.y2lo = 0;
-        s.loud = 0;
         s.n_sleeps = 0;
         s.ring = ring;
         s.stamps = a.stamps;
@@ -714,60 +709,20 @@ __device__ __forceinline__ void st_iir_wave(const ChainLaunch &a, const StreamAr
         s.t_to_consumed = 0;
         const long long t_iir0 = clock64();
 #endif
-        uint32_t pbuf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        // wide stores need whole 512-sample groups per lane (tile_len a multiple of 512) and 32-byte aligned rows
-        const bool wide = (a.tile_len & 511u) == 0 && (((uintptr_t)a.pcm | (a.pcm_stride * 2)) & 31u) == 0;
         // (a segment that is not there has tlen 0 and stores nothing: it may run along with any kind of wave)
-        // (the P waves evaluate the same predicate, st_cold_and_full(): a ring's waves must agree on its lead-in)
-        const bool fast = __all(!q.sg.valid || (q.back < 0 && q.sg.tlen == (int32_t)a.tile_len && !keeps_restart)) != 0;
+        // (the P waves evaluate the same predicate, st_cold_and_full(): a ring's waves must agree on its lead-in - and the audio
+        // wave this very one, st_audio_wave)
+        const bool fast = st_ring_is_fast(q.sg.valid, q.back, q.sg.tlen, a.tile_len, keeps_restart);
+        if (keeps_restart) q.sg.valid |= 2u;
         const int rec_pos_uniform = (int)a.tile_len - FORCED_BACK;
-        int pq0 = 0;
         if (fast) {
             st_iir_lead_in(sa, ring_base, full, consumed, wg, s, rd_off0, rd_swz, lead_cold);
             q.rec.y_in = s.y;                                    // the warmed-up state, checked against the predecessor's end
-            pq0 = ST_HALO / 32;
-        }
-        for (int pq = pq0; pq < n_pieces; pq += 4) {
-            const int pos = -ST_HALO + 32 * pq;
-            int p0, p1, p2, p3;
-            if (fast) {
-                p0 = st_iir_piece<0, true>(a, sa, ring_base, full, consumed, wg, q, s, pos, rd_off0, rd_swz, lane, rec_pos_uniform);
-                p1 = st_iir_piece<1, true>(a, sa, ring_base, full, consumed, wg, q, s, pos + 32, rd_off0, rd_swz, lane, rec_pos_uniform);
-                p2 = st_iir_piece<2, true>(a, sa, ring_base, full, consumed, wg, q, s, pos + 64, rd_off0, rd_swz, lane, rec_pos_uniform);
-                p3 = st_iir_piece<3, true>(a, sa, ring_base, full, consumed, wg, q, s, pos + 96, rd_off0, rd_swz, lane, rec_pos_uniform);
-            } else {
-                p0 = st_iir_piece<0, false>(a, sa, ring_base, full, consumed, wg, q, s, pos, rd_off0, rd_swz, lane, rec_pos_uniform);
-                p1 = st_iir_piece<1, false>(a, sa, ring_base, full, consumed, wg, q, s, pos + 32, rd_off0, rd_swz, lane, rec_pos_uniform);
-                p2 = st_iir_piece<2, false>(a, sa, ring_base, full, consumed, wg, q, s, pos + 64, rd_off0, rd_swz, lane, rec_pos_uniform);
-                p3 = st_iir_piece<3, false>(a, sa, ring_base, full, consumed, wg, q, s, pos + 96, rd_off0, rd_swz, lane, rec_pos_uniform);
-            }
-            // 128 samples = 4 PCM samples = 8 bytes.  Where the row allows it they are collected over 512 samples and
-            // leave as one aligned 32-byte sector (segments start on multiples of 512 samples of their channel's
-            // stream, so the phase below is the same for every lane); else 8 bytes at a time.
-            const uint32_t w0 = pack_lo16((uint32_t)p0, (uint32_t)p1), w1 = pack_lo16((uint32_t)p2, (uint32_t)p3);
-            const int phase = (pos >> 7) & 3;
-            if (phase == 0) { pbuf[0] = w0; pbuf[1] = w1; }
-            else if (phase == 1) { pbuf[2] = w0; pbuf[3] = w1; }
-            else if (phase == 2) { pbuf[4] = w0; pbuf[5] = w1; }
-            else { pbuf[6] = w0; pbuf[7] = w1; }
-            if (q.sg.valid) {
-                if (!wide) {
-                    if (pos >= 0 && pos < q.sg.tlen) *(u32x2 *)(q.pcm_row + ((q.sg.v0 + pos) >> 5)) = u32x2{w0, w1};
-                } else if (phase == 3) {
-                    const int g0 = pos - 384;                    // the group [g0, g0 + 512)
-                    int16_t *dst = q.pcm_row + ((q.sg.v0 + g0) >> 5);
-                    if (g0 >= 0 && g0 + 512 <= q.sg.tlen) {
-                        ST_STORE16(dst, pbuf[0], pbuf[1], pbuf[2], pbuf[3]);
-                        ST_STORE16(dst + 8, pbuf[4], pbuf[5], pbuf[6], pbuf[7]);
-                    } else {                                     // a segment's ragged end (or the lead-in): quarter by quarter
-#pragma unroll
-                        for (int k = 0; k < 4; k++)
-                            if (g0 + 128 * k >= 0 && g0 + 128 * k < q.sg.tlen) ((u32x2 *)dst)[k] = u32x2{pbuf[2 * k], pbuf[2 * k + 1]};
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 20; k++) s.y2p[k] = s.y2p[k + 4];
+            for (int pq = ST_HALO / 32; pq < n_pieces; pq++)
+                st_iir_piece<true>(a, sa, ring_base, full, consumed, wg, y2r, yk, q, s, -ST_HALO + 32 * pq, rd_off0, rd_swz, lane, rec_pos_uniform);
+        } else {
+            for (int pq = 0; pq < n_pieces; pq++)
+                st_iir_piece<false>(a, sa, ring_base, full, consumed, wg, y2r, yk, q, s, -ST_HALO + 32 * pq, rd_off0, rd_swz, lane, rec_pos_uniform);
         }
         st_iir_marks(a, q, s, (int)a.tile_len, rec_pos_uniform);
         if (q.sg.valid) {
@@ -794,13 +749,167 @@ __device__ __forceinline__ void st_iir_wave(const ChainLaunch &a, const StreamAr
     }
 }
 
+// ---- audio wave: the last decimator of every ring of the workgroup, pairs of stage-2 outputs -> PCM ---
+// /2, 40 taps over the pairs p[1..20] (p[20] newest): without clamps when no loud value is in reach, else in
+// the reference's order with the clamp after every MAC (Decimator_int16.cc:176-238)
+template <int V>
+__device__ __forceinline__ int st_audio(const StreamArgs &sa, const uint32_t (&y2p)[24], bool quiet, int c14)
+{
+    int acc = c14;
+    if (quiet) {
+#if IQD_ST_DOT2_FROM
+        acc = dot2_from(y2p[V + 20], sa.a40p[0], c14);
+#pragma unroll
+        for (int q = 1; q < 20; q++) acc = dot2(y2p[V + 20 - q], ST_TAP(a40p, q), acc);
+#else
+#pragma unroll
+        for (int q = 0; q < 20; q++) acc = dot2(y2p[V + 20 - q], ST_TAP(a40p, q), acc);
+#endif
+    } else {
+#pragma unroll
+        for (int q = 0; q < 20; q++) {
+            acc = clamp_q30(dot2(y2p[V + 20 - q], ST_TAP(a40p, q) & 0xffff0000u, acc));   // newer sample of the pair: h[2q]
+            acc = clamp_q30(dot2(y2p[V + 20 - q], ST_TAP(a40p, q) & 0x0000ffffu, acc));   // older: h[2q+1]
+        }
+    }
+    return acc >> 15;
+}
+
+struct StAudRing {         // one ring's share of the audio wave: its lane's segment of that ring
+    uint32_t y2p[24];      // stage-2 outputs as pairs; variant V of a piece uses [V+1 .. V+20]
+    uint32_t pbuf[2];      // PCM of the first half of a 256-sample group, which leaves as one 16-byte store
+    int16_t *pcm;          // the segment's first PCM sample
+    uint32_t hidx;         // its boundary record, ~0u: the segment is not there
+    int32_t tlen;
+};
+
+// One piece of one ring: take the pair, then the PCM sample it completes (returned).  `loud` (uniform): pieces for which a
+// |y2| > AUDIO40_SAFE of ANY lane stays in reach of the 40-tap window - the ring's lanes vote, as they did inside the IIR wave.
+template <int V>
+__device__ __forceinline__ uint32_t st_audio_piece(const StreamArgs &sa, const StY2Ring &y2r, uint32_t &ak, StAudRing &r, int &loud, int c14)
+{
+    const StY2Piece yp = st_y2_piece(ak, ST_Y2_DEPTH, ST_Y2_EVERY);
+    while ((int32_t)(lds_load_relaxed(y2r.full) - yp.need_full) < 0) __builtin_amdgcn_s_sleep(IQD_ST_SLEEP_A);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const uint32_t pair = *(const uint32_t *)(y2r.lane_slot0 + yp.slot * ST_Y2_SLOT_BYTES);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // the read has returned
+    lds_signal(y2r.consumed);
+    ak++;
+    r.y2p[V + 20] = pair;
+    const int lo = (int)(pair << 16) >> 16, hi = (int)pair >> 16;
+    const uint32_t mlo = (uint32_t)(lo < 0 ? -lo : lo), mhi = (uint32_t)(hi < 0 ? -hi : hi);
+    if (__any(mlo > (uint32_t)AUDIO40_SAFE || mhi > (uint32_t)AUDIO40_SAFE)) loud = 21;
+    const uint32_t pcm = (uint32_t)(loud == 0 ? st_audio<V>(sa, r.y2p, true, c14) : st_audio<V>(sa, r.y2p, false, c14));
+    if (loud > 0) loud--;
+    return pcm;
+}
+
+// Behind a ring's four pieces at pos .. pos + 127: 128 samples = 4 PCM samples = 8 bytes.  Where the row allows it they are
+// collected over 256 samples and leave as one aligned 16-byte store (segments start on multiples of 512 samples of their
+// channel's stream, so the phase below is the same for every lane); else 8 bytes at a time.  (The IIR lanes collected 512
+// samples for a whole 32-byte sector; three rings' worth of that - 24 registers - does not fit beside three histories.)
+__device__ __forceinline__ void st_audio_quad_done(const StreamArgs &sa, StAudRing &r, int pos, bool wide, uint32_t w0, uint32_t w1)
+{
+    const bool valid = r.hidx != ~0u;
+    if (pos >= 0 && pos < 768 - 96 && valid)   // the four pairs of this run of 128 samples, for the boundary fix-up
+        ST_STORE16(&sa.hist[r.hidx].y2_first[pos >> 5], r.y2p[20], r.y2p[21], r.y2p[22], r.y2p[23]);
+    if (!wide) {
+        if (valid && pos >= 0 && pos < r.tlen) *(u32x2 *)(r.pcm + (pos >> 5)) = u32x2{w0, w1};
+    } else if (((pos >> 7) & 1) == 0) {                  // (uniform) the group's first half waits for the second
+        r.pbuf[0] = w0;
+        r.pbuf[1] = w1;
+    } else if (valid) {
+        const int g0 = pos - 128;                        // the group [g0, g0 + 256)
+        int16_t *dst = r.pcm + (g0 >> 5);
+        if (g0 >= 0 && g0 + 256 <= r.tlen) {
+            ST_STORE16(dst, r.pbuf[0], r.pbuf[1], w0, w1);
+        } else {                                         // a segment's ragged end (or the lead-in): half by half
+            if (g0 >= 0 && g0 < r.tlen) ((u32x2 *)dst)[0] = u32x2{r.pbuf[0], r.pbuf[1]};
+            if (pos >= 0 && pos < r.tlen) ((u32x2 *)dst)[1] = u32x2{w0, w1};
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 20; k++) r.y2p[k] = r.y2p[k + 4];
+}
+
+// the segment's last 40 stage-2 outputs, when the quad that starts at `pos` starts behind its end (pos a multiple of 128: the
+// pair history sits in y2p[0..19] here)
+__device__ __forceinline__ void st_audio_end_mark(const StreamArgs &sa, const StAudRing &r, int pos)
+{
+    if (pos == r.tlen && r.hidx != ~0u) {
+#pragma unroll
+        for (int k = 0; k < 20; k += 4) ST_STORE16(&sa.hist[r.hidx].y2_last[k], r.y2p[k], r.y2p[k + 1], r.y2p[k + 2], r.y2p[k + 3]);
+    }
+}
+
+// (the rings by constant index: the three rings' histories are registers only as long as nothing indexes them at run time)
+static_assert(ST_RINGS == 3, "ST_FOR_RINGS names the rings");
+#define ST_FOR_RINGS(...) do { { constexpr int ring = 0; __VA_ARGS__ } { constexpr int ring = 1; __VA_ARGS__ } { constexpr int ring = 2; __VA_ARGS__ } } while (0)
+
+// What the audio wave's lane knows about its segment of ring `ring` in this round; returns the first piece the ring hands over.
+__device__ __forceinline__ int st_audio_ring_start(const ChainLaunch &a, const StreamArgs &sa, uint32_t round, int ring, int lane, StAudRing &r)
+{
+#pragma unroll
+    for (int k = 0; k < 24; k++) r.y2p[k] = 0;
+    r.pbuf[0] = r.pbuf[1] = 0;
+    const uint32_t sid = (round * chain_wgs(a) + chain_wg(a)) * (64u * sa.rings) + ring * 64 + lane;
+    int rot_unused;
+    const StSeg sg = st_segment_of(a, sa, sid, rot_unused);
+    // the ring's IIR wave decides on its fast path with these very values (st_iir_wave)
+    const int32_t back = sg.tile == 0 ? a.wbfm_carry[sg.ech].back : -1;
+    const StRecPlan rp = st_rec_plan(sg.valid, sg.tile, sg.v0, sg.tlen, sg.vlen, sg.tile == 0 ? back : ST_HALO);
+    const bool fast = st_ring_is_fast(sg.valid, back, sg.tlen, a.tile_len, rp.keeps_restart != 0);
+    r.pcm = a.pcm + (size_t)sg.ch * a.pcm_stride + (sg.v0 >> 5);   // (segments start on multiples of 128 samples)
+    r.hidx = sg.valid ? sg.li * a.tiles_per_ch + sg.tile : ~0u;
+    r.tlen = sg.tlen;
+    return fast ? ST_HALO / 32 : 0;
+}
+
+__device__ __forceinline__ void st_audio_wave(const ChainLaunch &a, const StreamArgs &sa, uint8_t *lds, uint32_t *sync, int lane)
+{
+    const int n_pieces = (ST_HALO + (int)a.tile_len) >> 5;       // a multiple of 4
+    // wide stores need whole 512-sample groups per lane (tile_len a multiple of 512) and 32-byte aligned rows
+    const bool wide = (a.tile_len & 511u) == 0 && (((uintptr_t)a.pcm | (a.pcm_stride * 2)) & 31u) == 0;
+    int c14 = 1 << 14;
+    asm volatile("" : "+v"(c14));
+    StY2Ring y2r[ST_RINGS];
+    uint32_t ak[ST_RINGS];                                       // pieces taken from each ring so far (all rounds)
+    ST_FOR_RINGS(y2r[ring] = st_y2_ring(lds, sync, ring, lane); ak[ring] = 0;);
+    for (uint32_t round = 0; round < sa.rounds; round++) {
+        if ((round * chain_wgs(a) + chain_wg(a)) * (64u * sa.rings) >= st_id_count(sa)) break;
+        StAudRing r[ST_RINGS];
+        int loud[ST_RINGS], pq0[ST_RINGS];
+        ST_FOR_RINGS(
+            loud[ring] = 0;
+            pq0[ring] = n_pieces;                                // (a ring that is not there never hands anything over)
+            if (ring < (int)sa.rings) pq0[ring] = st_audio_ring_start(a, sa, round, ring, lane, r[ring]);
+        );
+        for (int pq = 0; pq < n_pieces; pq += 4) {
+            const int pos = -ST_HALO + 32 * pq;
+            // a ring's four pieces, then the next ring's: the y2 rings are deep enough for an IIR wave to go on while the
+            // other two rings' quads are taken (piece by piece through the rings, the three rings' PCM words on their
+            // way - six registers more - did not fit)
+            ST_FOR_RINGS(if (pq >= pq0[ring]) {
+                st_audio_end_mark(sa, r[ring], pos);
+                const uint32_t p0 = st_audio_piece<0>(sa, y2r[ring], ak[ring], r[ring], loud[ring], c14);
+                const uint32_t p1 = st_audio_piece<1>(sa, y2r[ring], ak[ring], r[ring], loud[ring], c14);
+                const uint32_t p2 = st_audio_piece<2>(sa, y2r[ring], ak[ring], r[ring], loud[ring], c14);
+                const uint32_t p3 = st_audio_piece<3>(sa, y2r[ring], ak[ring], r[ring], loud[ring], c14);
+                st_audio_quad_done(sa, r[ring], pos, wide, pack_lo16(p0, p1), pack_lo16(p2, p3));
+            });
+        }
+        ST_FOR_RINGS(if (ring < (int)sa.rings) st_audio_end_mark(sa, r[ring], (int)a.tile_len););
+    }
+}
+#undef ST_FOR_RINGS
+
 // The workgroup's whole life: table into LDS, then the waves take their roles.  (A function of its own: the kernel below
 // calls it, and so does the launch that runs several families side by side, iqd_stream_mixed.hip.)
 template <int ROT, bool MAG, bool EPOCHS, bool GATED>
 __device__ __forceinline__ void wbfm_stream_body(const ChainLaunch &a, const StreamArgs &sa, uint8_t *st_lds)
 {
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)st_lds != 0u) __builtin_trap();   // st_table_read()
-    uint32_t *sync = (uint32_t *)(st_lds + ST_TABLE_BYTES + ST_RINGS * ST_RING_SLOTS * ST_SLOT_BYTES);
+    uint32_t *sync = (uint32_t *)(st_lds + ST_SYNC_OFF);
     const int tid = (int)threadIdx.x;
     {   // the table: every thread's loads in flight together, then its stores (round 5: written as one loop, the compiler waited for
         // each load before the next - nine trips to L2 one after the other at the start of every launch, 256 workgroups at once)
@@ -821,7 +930,11 @@ __device__ __forceinline__ void wbfm_stream_body(const ChainLaunch &a, const Str
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     uint32_t pc = 0;                                             // pieces this wave's ring has seen (all rounds)
+#if IQD_ST_TIMING   // which SIMD each of the workgroup's waves sits on (HW_ID), + 1: stamps[20000 + wave], tools/simd_of_waves.py
+    if (blockIdx.x == 0 && lane == 0) a.stamps[20000 + wave] = (unsigned long long)(st_simd_id() + 1);
+#endif
     if (wave < ST_RINGS) st_iir_wave(a, sa, st_lds, sync, wave, lane, ROT != 2 && !GATED && !EPOCHS ? IQD_ST_COLD_HALO : ST_HALO);
+    else if (wave == ST_AUDIO_WAVE) st_audio_wave(a, sa, st_lds, sync, lane);
     else if (ROT != 2) st_p_wave<ROT, MAG, EPOCHS, GATED>(a, sa, st_lds, sync, wave - ST_RINGS, lane, pc);
     else {   // channels of several rotation selectors: the groups in their order
         st_p_wave<1, MAG, EPOCHS, GATED, true>(a, sa, st_lds, sync, wave - ST_RINGS, lane, pc);

@@ -950,7 +950,7 @@ __device__ __forceinline__ void d4_stream_body(const ChainLaunch &a, const D4Arg
     uint32_t *sync = (uint32_t *)(d4_lds + ST_RINGS * D4_SLOTS * D4_SLOT_BYTES);
     const int tid = (int)threadIdx.x;
     if (tid < D4_SYNC_WORDS) sync[tid] = 0;
-    if (MAG && IQD_D4_MAGLUT == 1) st_maglut_build(d4_lds + D4_MAGLUT_OFF, tid, ST_THREADS);
+    if (MAG && IQD_D4_MAGLUT == 1) st_maglut_build(d4_lds + D4_MAGLUT_OFF, tid, D4_THREADS);
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
 #if IQD_D4_TIMING == 2
@@ -1008,7 +1008,7 @@ __device__ __forceinline__ void d4_stream_body(const ChainLaunch &a, const D4Arg
 
 #ifndef IQD_STREAM_BODIES_ONLY
 template <int MODE, bool MAG, bool GATED>
-__global__ __launch_bounds__(ST_THREADS, D4_WAVES_PER_SIMD(MODE)) void d4_stream_kernel(const ChainLaunch a, const D4Args da)
+__global__ __launch_bounds__(D4_THREADS, D4_WAVES_PER_SIMD(MODE)) void d4_stream_kernel(const ChainLaunch a, const D4Args da)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t d4_lds[];
     d4_stream_body<MODE, MAG, GATED>(a, da, d4_lds);
@@ -1038,7 +1038,7 @@ hipError_t launch_d4_stream(const ChainLaunch &a, const D4Args &da, int mode, bo
     const D4Kernel (&ks)[3][3] = d4_kernels;
     const bool gated = a.vlen_gated != nullptr;
     const int m = mode == D4_AM ? 0 : (mode == D4_SSB ? 1 : 2);
-    hipLaunchKernelGGL(ks[m][gated ? 2 : (mag ? 1 : 0)], dim3(grid), dim3(ST_THREADS), D4_LDS_BYTES, s, a, da);
+    hipLaunchKernelGGL(ks[m][gated ? 2 : (mag ? 1 : 0)], dim3(grid), dim3(D4_THREADS), D4_LDS_BYTES, s, a, da);
     return hipGetLastError();
 }
 

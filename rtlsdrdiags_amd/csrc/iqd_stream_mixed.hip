@@ -39,6 +39,9 @@ __global__ __launch_bounds__(ST_THREADS, 4) void mixed_stream_kernel(const Chain
         if (wbfm_rot == 0) wbfm_stream_body<0, MAG, false, GATED>(a_wbfm, sa, mx_lds);
         else if (wbfm_rot > 0) wbfm_stream_body<1, MAG, false, GATED>(a_wbfm, sa, mx_lds);
         else wbfm_stream_body<-1, MAG, false, GATED>(a_wbfm, sa, mx_lds);
+    } else if (threadIdx.x >= D4_THREADS) {
+        // (the other families' pipelines are 15 waves: the sixteenth leaves before their bodies' barrier, which counts the waves
+        // that are still there)
     } else if (b - a_fm.wg_first < a_fm.wg_count) {
         d4_stream_body<D4_FM, MAG, GATED>(a_fm, d_fm, mx_lds);
     } else if (b - a_ssb.wg_first < a_ssb.wg_count) {
