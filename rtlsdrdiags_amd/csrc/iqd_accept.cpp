@@ -74,6 +74,21 @@ int take_event_pair(iqd_t *e, CallCtx &x, hipStream_t s)
     HIP_TRY(e, hipEventRecord(x.evp.first, s));
     return IQD_OK;
 }
+
+// Channel c's last WBFM gain change has left its lead-ins' reach (wbfm_epoch_left went to 0): the chain has consumed TAIL
+// samples with the current K, the de-emphasis (0.949 per sample) has taken whatever state the earlier gains left down by
+// 3 10^-47, and the tile kernel's own rule (iqd_kernels.hip: wbfm_run_tile, K and the k_before in reach) sees the current K alone.
+// So wbfm_kmax - which keeps a call off the bounded (int16) casts, the streaming pipeline and the one launch - falls back to the K
+// the device runs with and the one a setter may have stored meanwhile; it used to stay at the largest K since creation, and
+// ONE overlarge gain kept the channel's calls on the tile kernel for good.  It still does above WBFM_KMAX_DECAYS (iqd_engine_impl.h),
+// and fm_kmax, which has no epoch mirror on the host to age it, never falls.  Call with e->mu held (iqd_set_gain raises wbfm_kmax
+// under it).
+void wbfm_gain_aged_out(iqd_t *e, uint32_t c)
+{
+    if (!(e->wbfm_kmax[c] < iqd_engine::WBFM_KMAX_DECAYS)) return;
+    const float applied = fabsf(e->k_applied[2 * c]), pending = fabsf(e->h_params[c].wbfm_k);
+    e->wbfm_kmax[c] = pending <= applied ? applied : pending;   // (a NaN just set: kept)
+}
 }  // namespace
 
 // Under the lock: the epoch mirror's ageing report, parameter upload, channel lists, AGC configuration.
@@ -87,6 +102,7 @@ static int prepare_call(iqd_t *e, CallCtx &x)
                 if (e->wbfm_epoch_left[c] && e->wbfm_epoch_seq[c] <= e->epoch_report_seq) {
                     e->wbfm_epoch_left[c] = 0;
                     e->wbfm_epochs_live--;
+                    wbfm_gain_aged_out(e, c);
                 }
         e->epoch_report_pending = false;
     }
@@ -428,13 +444,18 @@ static int queue_family(iqd_t *e, CallCtx &x, int f)
     }
     e->stats.kernel_launches++;
     if (fused) return IQD_OK;   // (one launch for all the families and one for what follows them: queue_commit)
-    if (f == FAM_WBFM && !x.gated && e->wbfm_epochs_live)   // every channel of the family has consumed vlen samples
+    if (f == FAM_WBFM && !x.gated && e->wbfm_epochs_live) {   // every channel of the family has consumed vlen samples
+        std::lock_guard<std::mutex> lk(e->mu);
         for (uint32_t c : e->h_lists[FAM_WBFM]) {
             uint32_t &left = e->wbfm_epoch_left[x.first_ch + c];
             if (!left) continue;
             left = left > x.vlen ? left - x.vlen : 0u;
-            if (!left) e->wbfm_epochs_live--;
+            if (!left) {
+                e->wbfm_epochs_live--;
+                wbfm_gain_aged_out(e, x.first_ch + c);
+            }
         }
+    }
     const bool rides_with_squelch = !forked && !x.gated && !e->demod_bypass &&
                                     (x.want_mag || x.pcm_count_dev || x.signal_present_dev || e->trace_on);
     if (f == FAM_WBFM) {

@@ -378,6 +378,8 @@ int iqd::upload_params(iqd_t *e)
             if (!e->wbfm_epoch_left[c]) e->wbfm_epochs_live++;
             e->wbfm_epoch_left[c] = (uint32_t)TAIL;
             e->wbfm_epoch_seq[c] = e->accept_seq + 1;
+        } else if (!e->wbfm_epoch_left[c] && e->wbfm_kmax[c] < iqd_engine::WBFM_KMAX_DECAYS) {
+            e->wbfm_kmax[c] = fabsf(p.wbfm_k);   // (a gain set and set back before any call ran with it: no change, no epoch to age it out)
         }
         if (f2u(p.fm_k) != f2u(e->k_applied[2 * c + 1])) {
             if (!(p.k_changed & 2u)) p.fm_k_prev = e->k_applied[2 * c + 1];

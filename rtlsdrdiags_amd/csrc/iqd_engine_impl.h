@@ -100,7 +100,10 @@ struct iqd_engine {
     std::vector<float> fm_kmax;          // [n_ch]: like wbfm_kmax, for the FM chain
     bool stream_ok = false;              // the half table's symmetry holds on this host's libm
     std::vector<uint32_t> mode_gen, rot_gen;   // [n_ch]: bumped by iqd_set_mode / iqd_set_rotation (iqd_demod_accept restores only what nobody set meanwhile)
-    std::vector<float> wbfm_kmax;        // [n_ch]: largest |K| a channel has run with since creation (casts stay bounded)
+    std::vector<float> wbfm_kmax;        // [n_ch]: largest |K| a lead-in of the channel can still reach, or that was set since (casts stay bounded; iqd_accept.cpp: wbfm_gain_aged_out)
+    // ... above this |K| it never falls back: 0.949^2048 = 3e-47 of K pi must lie below the 2^-100 under which the hand-off checks take
+    // two de-emphasis states as agreeing (else a silent input would show the residue as state_repairs), and inf / NaN do not decay
+    static constexpr float WBFM_KMAX_DECAYS = 1.0e15f;
     StreamArgs stream_args{};
     uint64_t stream_handoffs = 0;        // cold segments launched so far (their verification counts only mismatches)
     DevArray<uint32_t> d_counters;       // cumulative, read by iqd_get_stats

@@ -126,3 +126,35 @@ def test_gated_engine_returns_to_the_one_launch_path_after_a_gain_change_has_age
     assert call() == 2                                   # ... it has aged out, the device said so: one launch again
     assert call() == 3
     eng.close()
+
+
+def test_an_overlarge_gain_keeps_a_channel_off_the_bounded_casts_only_while_it_is_in_reach(capi, oracle):
+    """A WBFM gain so large that (int16)y can hit the "integer indefinite" value takes the channel to the tile kernel (the
+    streaming pipeline's casts are the bounded ones).  The engine used to remember the largest gain a channel ever had, so ONE
+    such gain kept its calls there - and a mixed call off the one-launch arrangement - for good; now only until the channel
+    has consumed the 2048 samples a lead-in can reach back over with the gain that followed (tests/test_gpu_one_launch.py has
+    the mixed call).  Calls of 1024 samples: the first call that streams again starts exactly where the reach ends, with
+    whatever the de-emphasis state still holds of the large gain's samples."""
+    big = 6.0e9
+    u8 = synth.fm_tone(16 * 1024, seed=31, deviation=60e3)
+    c = oracle.chain()
+    c.set_mode("wbfm")
+    eng = capi.Engine(1, block_bytes=2048, flags=0x4)      # IQD_F_WBFM_STREAM: streams wherever the rules allow
+    eng.set_mode("wbfm")
+    usual = eng.channel_gain(0, "wbfm")
+    streamed = []
+    for k, gains in enumerate([(), (big, usual), (big,), (), (), (usual,), (), (), (), (big,), (usual,), (), (), ()]):
+        for gain in gains:                 # (call 1: set and set back before any sample ran with it - nothing to age out)
+            c.set_gain(3, gain)
+            eng.set_gain("wbfm", gain)
+        piece = u8[2048 * k:2048 * (k + 1)]
+        before = eng.stats()["stream_launches"]
+        pcm, cnt, mag, _ = eng.accept(piece)
+        streamed.append(eng.stats()["stream_launches"] - before)
+        ref, ref_mag, _ = c.accept_stream(piece, 2048)
+        assert cnt[0] == len(ref) and np.array_equal(pcm[0, :cnt[0]], ref), (k, gains, np.flatnonzero(pcm[0, :cnt[0]] != ref)[:8])
+        assert np.array_equal(mag[0], ref_mag), k
+    #                   big          usual                big usual (set before consecutive calls)
+    assert streamed == [1, 1, 0, 0, 0, 0, 0, 1, 1, 0, 0, 0, 1, 1], streamed
+    assert eng.stats()["state_repairs"] == 0
+    eng.close()

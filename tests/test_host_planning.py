@@ -396,3 +396,41 @@ def test_the_taps_the_kernels_carry_as_literals_are_the_ones_the_host_quantises(
     lib.emu_stream_taps.argtypes = [C.c_void_p, C.c_void_p]
     lib.emu_stream_taps(lit.ctypes.data, host.ctypes.data)
     assert host.any() and np.array_equal(lit, host), (lit, host)
+
+
+def test_plan_call_pins_the_small_one_launch_shapes():
+    """The shapes tests/test_gpu_one_launch.py runs on the device (tests/one_launch_shapes.py): 100 mixed channels x 2^14
+    samples are ONE launch of 14 workgroups, in every variant (squelch-gated or not, with magnitudes or without) and for every
+    WBFM rotation selector; the row lengths, family subsets and smallest calls of that file; what takes such a call off the one
+    launch.  A planner change that makes those GPU cases vacuous fails here first."""
+    import itertools
+    import one_launch_shapes as S
+    for s in S.SHAPES.values():
+        variants = itertools.product(S.SELECTORS, (False, True), (0, 1)) if s.wbfm_rots is None else [(1, False, 0)]
+        for wbfm_rot, gated, flags in variants:
+            p, _ = S.hold(plan_call, s, wbfm_rot=wbfm_rot, gated=gated, flags=flags)
+            fams = S.plan_fams(s, wbfm_rot)
+            check_plan(p, s.n, flags, 0, True, 256, fams)
+    mix = S.SHAPES["mix"]
+    assert mix.counts == {"am": 20, "fm": 20, "wbfm": 20, "ssb": 40} and (mix.mix_wgs, mix.segs) == (14, 22)
+    assert [S.SHAPES[n].segs for n in S.ROW_LENGTHS] == [22, 22, 23, 43, 64, 107]
+    assert len(S.SUBSETS) == 11 and all(S.SHAPES[n].fused for n in S.SUBSETS)
+    # pinned to its streaming kernels (flags = 4) the same call is a kernel per family
+    assert not plan_call(mix.n, S.plan_fams(mix), flags=F_STREAM)["fused"]
+    # the smallest WBFM family: the size rule weighs the call, so beside 60 + 60 + 120 channels every w >= 1 is one launch ...
+    for w in range(1, 61):
+        p = plan_call(1 << 14, S.plan_fams(S.SHAPES["wbfm_1"]._replace(counts={"am": 60, "fm": 60, "wbfm": w, "ssb": 120})))
+        assert p["fused"] and p["fam"]["wbfm"]["path"] == PLAN_STREAM and p["fam"]["wbfm"]["rings"] == 3, w
+    assert S.SMALLEST_WBFM == 1
+    # ... and the boundary lies in the call's size: m + m + m + 2 m channels are one launch from m = 18
+    for m in range(1, 41):
+        s = mix._replace(counts={"am": m, "fm": m, "wbfm": m, "ssb": 2 * m})
+        assert plan_call(1 << 14, S.plan_fams(s))["fused"] == (m >= S.SMALLEST_MIX), m
+    # the 16-byte PCM stores of the audio wave need WBFM segments of whole 512-sample groups on rows of whole groups: none of the
+    # small shapes has them (768), `bench.py --config 3` and the at-size tests of tests/test_gpu_scale.py do
+    # (AM, FM, WBFM, SSB channels: bench.py --config 3; tests/test_gpu_scale.py: _mixed_setup at 4096 x 2^16, 16384 x 2^14, 1410 x 2^16)
+    for n, counts, seg in ((1 << 16, (819, 819, 819, 1639), 3072), (1 << 16, (820, 819, 819, 1638), 3072),
+                           (1 << 14, (3277, 3277, 3277, 6553), 3584), (1 << 16, (282, 282, 282, 564), 1024)):
+        fams = {f: ((c, 0, 0) if f == "wbfm" else S.cycle_counts(c), True, False) for f, c in zip(FAMS, counts)}
+        p = plan_call(n, fams)
+        assert p["fused"] and p["fam"]["wbfm"]["tile_len"] == seg and seg % 512 == 0 and n % 512 == 0, (n, counts, p["fam"]["wbfm"])
