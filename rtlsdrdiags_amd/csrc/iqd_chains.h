@@ -599,7 +599,7 @@ IQD_DEV void dc_store(const DcLds &lds, int nseg, int lane, int16_t *pcm /* of t
     uint32_t *dst = (uint32_t *)pcm;
     for (int d = lane; d < nseg * (DC_S / 2); d += 64) {
         const uint32_t w = lds.row[(d / (DC_S / 2)) * DC_ROW + (d % (DC_S / 2))];
-#if !defined(IQD_NO_WT_STORES) && IQD_ON_DEVICE
+#if IQD_ON_DEVICE
         // write-through (sc1): what a launch leaves dirty in the L2s is written back at its end, in front of whatever follows it on
         // the stream (B / 6 TB/s: MI355X_MICROARCH.md, kernel boundaries) - the closing launch's PCM and tails go out while it still
         // runs instead (round 6, profiles/r6_wt_ab.txt: AM 4096 x 2^16 -0.8 %, 4096 x 2^14 -1.7 %, configs[4] -0.9 %; the pipelines'
@@ -617,35 +617,20 @@ template <class Exec, class SRC>
 IQD_DEV void dc_block_wave(Exec &ex, const Consts &c, DcLds &lds, const SRC *x, int n, float gain,
                            DcCarry &st, int16_t *pcm)
 {
-#if defined(IQD_DC_TIMING) && IQD_ON_DEVICE   // measurement build (tools/variant.sh dctiming iqd_kernels.hip -DIQD_DC_TIMING=1, tools/r6/r6_dctiming.sh):
-    long long tm[8];                           // where a row's pass goes, in shader clocks; profiles/r6_dc_timing.txt
-    const long long wall0 = wall_clock64();
-#define DC_T(K) tm[K] = clock64()
-    int redos = 0;
-#else
-#define DC_T(K)
-#endif
-    DC_T(0);
+    // (where a row's pass goes, in shader clocks: profiles/r6_dc_timing.txt, docs/EXPERIMENTS.md)
     ex.wave0([&](int lane) { if (lane == 0) { lds.x_carry = st.x_prev; lds.y_carry = st.y_prev; } });
     for (int base = 0; base < n; base += DC_SUPER) {
         const int len = n - base < DC_SUPER ? n - base : DC_SUPER;
         const int nfull = len / DC_S;             // whole segments: the segmented scheme
         if (nfull > 0) {
             ex.wave0([&](int lane) { dc_fill(lds, x, base, nfull, lane, true); });
-            DC_T(1);
             ex.wave0([&](int lane) { dc_guess(c, lds, nfull, lane); });
-            DC_T(2);
             ex.wave0([&](int lane) { dc_warm(c, lds, nfull, lane); });
-            DC_T(3);
             for (bool again = false;; again = true) {
-#if defined(IQD_DC_TIMING) && IQD_ON_DEVICE
-                redos += again;
-#endif
                 if (again) ex.wave0([&](int lane) { dc_fill(lds, x, base, nfull, lane, false); });   // (the rows hold PCM by now)
                 ex.wave0([&](int lane) { dc_real(c, lds, nfull, lane, gain); });
                 if (ex.wave0_all([&](int lane) { return dc_check(lds, nfull, lane, __builtin_fabsf(gain) <= 1e6f); })) break;
             }
-            DC_T(4);
             ex.wave0([&](int lane) {
                 if (pcm) dc_store(lds, nfull, lane, pcm + base);
                 if (lane == 0) {
@@ -667,16 +652,6 @@ IQD_DEV void dc_block_wave(Exec &ex, const Consts &c, DcLds &lds, const SRC *x, 
     }
     st.x_prev = lds.x_carry;
     st.y_prev = lds.y_carry;
-#if defined(IQD_DC_TIMING) && IQD_ON_DEVICE
-    DC_T(5);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    DC_T(6);
-    if ((threadIdx.x & 63) == 0 && (blockIdx.x % 331) == 7 && n == DC_SUPER)
-        printf("dc row wg %u: wall start %lld (x10 ns) | fill %lld guess %lld warm %lld real+check %lld (redos %d) store-issue %lld store-done %lld | total %lld clocks, wall %lld\n",
-               blockIdx.x, wall0, tm[1] - tm[0], tm[2] - tm[1], tm[3] - tm[2], tm[4] - tm[3], redos, tm[5] - tm[4], tm[6] - tm[5], tm[6] - tm[0],
-               wall_clock64() - wall0);
-#endif
-#undef DC_T
 }
 
 // ---- long streams, many waves per channel -------------------------------------------------------------

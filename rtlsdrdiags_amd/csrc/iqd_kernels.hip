@@ -118,11 +118,7 @@ __device__ __forceinline__ void wbfm_run_tile(const ChainLaunch &a, WbfmLds &lds
     t.pcm_row = a.pcm + (size_t)ch * a.pcm_stride;
     t.mag_row = MAG ? a.mag_sums + (size_t)ch * a.n_blocks : nullptr;
     DeviceExec ex{(int)threadIdx.x};
-#ifdef IQD_WBFM_SERIAL_PHASES   // the first driver: IIR phase not overlapped (kept for A/B measurements)
-    wbfm_tile<GATED, MAG>(ex, t, g_consts, lds, start, &a.records[(size_t)li * a.tiles_per_ch + tile]);
-#else
     wbfm_tile_pipe<GATED, MAG>(ex, t, g_consts, lds, start, &a.records[(size_t)li * a.tiles_per_ch + tile]);
-#endif
     if (ex.tid == 0 && lds.repair_count) atomicAdd(&a.counters[CNT_SEG_REPAIRS], lds.repair_count);
 #ifdef IQD_STAMPS
     if (a.stamps && (ex.tid == 0 || ex.tid == 64))
@@ -130,11 +126,8 @@ __device__ __forceinline__ void wbfm_run_tile(const ChainLaunch &a, WbfmLds &lds
 #endif
 }
 
-#ifndef IQD_WBFM_MIN_WAVES
-#define IQD_WBFM_MIN_WAVES 1
-#endif
 template <bool GATED, bool MAG>
-__global__ __launch_bounds__(WB_THREADS, IQD_WBFM_MIN_WAVES) void wbfm_chain_kernel(const ChainLaunch a)
+__global__ __launch_bounds__(WB_THREADS, 1) void wbfm_chain_kernel(const ChainLaunch a)
 {
     __shared__ WbfmLds lds;
     const uint32_t li = blockIdx.x / a.tiles_per_ch, tile = blockIdx.x - li * a.tiles_per_ch;
@@ -219,7 +212,7 @@ __device__ __forceinline__ void wbfm_repair_body(const ChainLaunch &a, WbfmLds &
 }
 
 template <bool GATED>
-__global__ __launch_bounds__(WB_THREADS, IQD_WBFM_MIN_WAVES) void wbfm_repair_kernel(const ChainLaunch a)
+__global__ __launch_bounds__(WB_THREADS, 1) void wbfm_repair_kernel(const ChainLaunch a)
 {
     __shared__ WbfmLds lds;
     wbfm_repair_body<GATED>(a, lds, blockIdx.x);
@@ -486,16 +479,12 @@ __device__ __forceinline__ void tail_update_body(const ChainLaunch &a, int famil
     uint4 val{};
     if (mine) val = *(const uint4 *)src;
     __syncthreads();
-#ifndef IQD_NO_WT_STORES   // write-through, like the DC pass's PCM (iqd_chains.h: dc_store)
-    if (mine) {
+    if (mine) {   // write-through, like the DC pass's PCM (iqd_chains.h: dc_store)
         typedef uint32_t wt4 __attribute__((ext_vector_type(4)));
         const wt4 vv = {val.x, val.y, val.z, val.w};
         const void *dst = tail + TAIL_BYTES - 2 * keep + 16 * (int)threadIdx.x;
         asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(vv) : "memory");
     }
-#else
-    if (mine) ((uint4 *)(tail + TAIL_BYTES - 2 * keep))[threadIdx.x] = val;
-#endif
 }
 
 __global__ __launch_bounds__(256) void tail_update_kernel(const ChainLaunch a, int family)
@@ -581,7 +570,7 @@ __global__ __launch_bounds__(256) void tail_dc_squelch_kernel(const ChainLaunch 
 
 // The same for a call whose one family is WBFM: hand-off repair check, state commit and tail (workgroups 0 .. n_list-1)
 // beside the squelch pass's first part.
-__global__ __launch_bounds__(WB_THREADS, IQD_WBFM_MIN_WAVES) void wbfm_repair_squelch_kernel(const ChainLaunch a, const SquelchLaunch q, int always_open)
+__global__ __launch_bounds__(WB_THREADS, 1) void wbfm_repair_squelch_kernel(const ChainLaunch a, const SquelchLaunch q, int always_open)
 {
     __shared__ WbfmLds lds;
     if (blockIdx.x < a.n_list) wbfm_repair_body<false>(a, lds, blockIdx.x);
@@ -673,9 +662,6 @@ __global__ void squelch_track_kernel(const SquelchLaunch q, int always_open)
 // together; with a fixed gain the decisions are independent (allowed = present | present of the block before) and
 // the open-block list is a ballot/popcount compaction; with a running AGC the wave steps through the 64 values in
 // order from registers (the recurrence stays serial, the memory latency is gone).
-#ifndef IQD_AGC_RUNS
-#define IQD_AGC_RUNS 1   // 0: every block of a channel with a running AGC takes the serial step (A/B builds)
-#endif
 __global__ __launch_bounds__(64) void squelch_track_wave_kernel(const SquelchLaunch q, int always_open)
 {
     const uint32_t ch = blockIdx.x, lane = threadIdx.x;
@@ -726,7 +712,7 @@ __global__ __launch_bounds__(64) void squelch_track_wave_kernel(const SquelchLau
                 allowed = present | before;
                 tracking = (uint32_t)__shfl((int)present, (int)count - 1);
             }
-        } else if (IQD_AGC_RUNS && cfg.enabled && !sc.scanning) {
+        } else if (cfg.enabled && !sc.scanning) {
             // A running AGC (round 4).  The recurrence over blocks is serial only where the AGC MOVES: while the error stays
             // inside the deadband (or is pinned at a gain limit) a step changes nothing but the two "last seen" values, and
             // while the measurements behind an adjustment are blanked it only counts.  Runs of such blocks are found with one

@@ -60,42 +60,11 @@ __device__ __forceinline__ uint4 st_front(uint4 raw, uint32_t zero)
     return uint4{d[0], d[1], d[2], d[3]};
 }
 
-// sum over the 2 samples of a dword of signed bytes of max(|I|,|Q|) + min(|I|,|Q|)/2, added into two 16-bit
-// lanes of acc (SignalDetector.cc:227-247).  |x| of all four bytes at once: (x ^ m) + t with t the sign bits.
-__device__ __forceinline__ uint32_t st_mag_dword(uint32_t sx, uint32_t acc)
-{
-    const uint32_t t = (sx >> 7) & 0x01010101u;
-    uint32_t t8 = t << 8;
-    asm("" : "+v"(t8));                                    // (else hipcc folds this into a quarter-rate v_mul_lo_u32 by 255)
-    const uint32_t m = t8 - t;
-    const uint32_t ab = (sx ^ m) + t;                      // bytes |I0| |Q0| |I1| |Q1|, each <= 128
-    const us2 a = __builtin_bit_cast(us2, ab & 0x00ff00ffu);
-    const us2 b = __builtin_bit_cast(us2, (ab >> 8) & 0x00ff00ffu);
-    const us2 mx = __builtin_elementwise_max(a, b), mn = __builtin_elementwise_min(a, b);
-    return acc + __builtin_bit_cast(uint32_t, mx) + __builtin_bit_cast(uint32_t, (us2)(mn >> 1));
-}
-
-
-// The same from the RAW bytes (offset binary I0 Q0 I1 Q1): |u - 128| of one byte is one masked v_msad_u8 (bytes whose
-// reference byte is 0 do not count), two of them join into a 16-bit pair with one v_lshl_or_b32: ten operations per
-// dword against twelve for the byte-parallel arithmetic above.
-__device__ __forceinline__ uint32_t st_mag_raw_dword(uint32_t raw, uint32_t acc)
-{
-    uint32_t a0, b0, a1, b1;
-    asm("v_msad_u8 %0, %1, %2, 0" : "=v"(a0) : "v"(raw), "s"(0x00000080u));
-    asm("v_msad_u8 %0, %1, %2, 0" : "=v"(b0) : "v"(raw), "s"(0x00008000u));
-    asm("v_msad_u8 %0, %1, %2, 0" : "=v"(a1) : "v"(raw), "s"(0x00800000u));
-    asm("v_msad_u8 %0, %1, %2, 0" : "=v"(b1) : "v"(raw), "s"(0x80000000u));
-    const us2 a = __builtin_bit_cast(us2, a0 | (a1 << 16)), b = __builtin_bit_cast(us2, b0 | (b1 << 16));
-    const us2 mx = __builtin_elementwise_max(a, b), mn = __builtin_elementwise_min(a, b);
-    return acc + __builtin_bit_cast(uint32_t, mx) + __builtin_bit_cast(uint32_t, (us2)(mn >> 1));
-}
-
-// The same with ONE quad-SAD: the dword's bytes are put in the order I0 I1 Q0 Q1 (v_perm_b32) and v_mqsad_pk_u16_u8 against
-// the reference 0x00000080 - only its byte 0 counts, at the four byte positions in turn - leaves |I0 - 128|, |I1 - 128| as
-// the halves of one register and |Q0 - 128|, |Q1 - 128| of the next: six instructions per dword against ten (the quad-SAD
-// issues at a quarter of the rate, tools/ubench: the kernel's time is the same either way, 0.3288 against 0.3324 ms on one
-// box).  IQD_ST_MQSAD=0 selects the single SADs below (A/B builds).
+// sum over the 2 samples of a dword of RAW bytes (offset binary I0 Q0 I1 Q1) of max(|I|,|Q|) + min(|I|,|Q|)/2, added into two
+// 16-bit lanes of acc (SignalDetector.cc:227-247), with ONE quad-SAD: the dword's bytes are put in the order I0 I1 Q0 Q1
+// (v_perm_b32) and v_mqsad_pk_u16_u8 against the reference 0x00000080 - only its byte 0 counts, at the four byte positions in
+// turn - leaves |I0 - 128|, |I1 - 128| as the halves of one register and |Q0 - 128|, |Q1 - 128| of the next: six instructions per
+// dword (the quad-SAD issues at a quarter of the rate, tools/ubench).
 __device__ __forceinline__ uint32_t st_mag_raw_dword_q(uint32_t raw, uint32_t acc)
 {
     const uint32_t p = __builtin_amdgcn_perm(raw, raw, 0x03010200u);
@@ -106,113 +75,13 @@ __device__ __forceinline__ uint32_t st_mag_raw_dword_q(uint32_t raw, uint32_t ac
     const us2 mx = __builtin_elementwise_max(a, b), mn = __builtin_elementwise_min(a, b);
     return acc + __builtin_bit_cast(uint32_t, mx) + __builtin_bit_cast(uint32_t, (us2)(mn >> 1));
 }
-#ifndef IQD_ST_MQSAD
-#define IQD_ST_MQSAD 1
-#endif
-
 // 8 raw samples (one lane's 16 bytes of a piece) added into the two 16-bit partial sums of acc
 __device__ __forceinline__ uint32_t st_mag_raw_chunk(const uint4 &raw, uint32_t acc)
 {
-    if (IQD_ST_MQSAD) {
-        acc = st_mag_raw_dword_q(raw.x, acc);
-        acc = st_mag_raw_dword_q(raw.y, acc);
-        acc = st_mag_raw_dword_q(raw.z, acc);
-        return st_mag_raw_dword_q(raw.w, acc);
-    }
-    // eight |u - 128| at a time, then their packed arithmetic: interleaved dword by dword the compiler pads the SAD ->
-    // packed-16 dependences with s_nop; all sixteen first costs eight more live registers (the launch that holds all four
-    // pipelines then spills vector registers to scratch)
-    const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-    for (int h = 0; h < 4; h += 2) {
-        uint32_t a0[2], b0[2], a1[2], b1[2];
-#pragma unroll
-        for (int d = 0; d < 2; d++) {
-            asm volatile("v_msad_u8 %0, %1, %2, 0" : "=v"(a0[d]) : "v"(w[h + d]), "s"(0x00000080u));
-            asm volatile("v_msad_u8 %0, %1, %2, 0" : "=v"(b0[d]) : "v"(w[h + d]), "s"(0x00008000u));
-            asm volatile("v_msad_u8 %0, %1, %2, 0" : "=v"(a1[d]) : "v"(w[h + d]), "s"(0x00800000u));
-            asm volatile("v_msad_u8 %0, %1, %2, 0" : "=v"(b1[d]) : "v"(w[h + d]), "s"(0x80000000u));
-        }
-#pragma unroll
-        for (int d = 0; d < 2; d++) {
-            const us2 a = __builtin_bit_cast(us2, a0[d] | (a1[d] << 16)), b = __builtin_bit_cast(us2, b0[d] | (b1[d] << 16));
-            const us2 mx = __builtin_elementwise_max(a, b), mn = __builtin_elementwise_min(a, b);
-            acc = acc + __builtin_bit_cast(uint32_t, mx) + __builtin_bit_cast(uint32_t, (us2)(mn >> 1));
-        }
-    }
-    return acc;
-}
-
-__device__ __forceinline__ uint32_t st_mag_chunk(const uint4 &s)   // 8 samples of signed bytes
-{
-    uint32_t m16 = st_mag_dword(s.x, 0u);
-    m16 = st_mag_dword(s.y, m16);
-    m16 = st_mag_dword(s.z, m16);
-    m16 = st_mag_dword(s.w, m16);
-    return (m16 & 0xffffu) + (m16 >> 16);
-}
-
-// ---- the same through a table in LDS (kernels with 68 KiB of LDS to spare) ----
-// One byte per raw sample (I, Q as they come from the tuner, offset binary): max(|I-128|, |Q-128|) + min(..)/2 <= 192.
-// Rows are 272 bytes apart, not 256: the bank is then 4 Q + I/4 and weak signals - every lane's I and Q within a few
-// counts of 128 - spread over the banks instead of piling onto two of them.  Two operations form a sample's address
-// straight from the raw dword (SDWA picks the bytes), one ds_read_u8 fetches the magnitude: 3.5 operations per sample
-// with the sums, against 6.5 for the arithmetic above.
-constexpr int ST_MAGLUT_PITCH = 272;
-constexpr int ST_MAGLUT_BYTES = 256 * ST_MAGLUT_PITCH;
-__device__ __forceinline__ void st_maglut_build(uint8_t *lut, int tid, int n_threads)
-{
-    for (int e = tid; e < 256 * (ST_MAGLUT_PITCH / 4); e += n_threads) {
-        const int q = e / (ST_MAGLUT_PITCH / 4), i0 = 4 * (e % (ST_MAGLUT_PITCH / 4));
-        const int b = q < 128 ? 128 - q : q - 128;
-        uint32_t w = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int i = (i0 + k) & 255;                        // (columns 256..271 are padding)
-            const int a = i < 128 ? 128 - i : i - 128;
-            w |= (uint32_t)(a > b ? a + (b >> 1) : b + (a >> 1)) << (8 * k);
-        }
-        *(uint32_t *)(lut + 4 * e) = w;
-    }
-}
-// magnitudes of the two samples of a raw dword (bytes I0 Q0 I1 Q1)
-__device__ __forceinline__ void st_maglut_pair(const uint8_t *lut, uint32_t w, uint32_t four, uint32_t &m0, uint32_t &m1)
-{
-    uint32_t t0, a0, t1, a1;
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(t0) : "v"(four), "v"(w));
-    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(a0) : "v"(t0), "v"(w));
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(t1) : "v"(four), "v"(w));
-    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(a1) : "v"(t1), "v"(w));
-    m0 = lut[a0];                                                // 256 Q + I + 16 Q
-    m1 = lut[a1];
-}
-// The same with the table at a known LDS ADDRESS (the kernel's dynamic LDS starts at address 0, checked at kernel start):
-// through a generic pointer the compiler adds the LDS base - a relocated zero - to every one of the eight addresses.
-typedef __attribute__((address_space(3))) const uint8_t lds_cu8;
-__device__ __forceinline__ uint32_t st_maglut_chunk_at(uint32_t lut_lds_address, const uint4 &raw, uint32_t four)   // 8 raw samples
-{
-    const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-    uint32_t m[8];
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-        uint32_t t0, a0, t1, a1;
-        asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(t0) : "v"(four), "v"(w[d]));
-        asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(a0) : "v"(t0), "v"(w[d]));
-        asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(t1) : "v"(four), "v"(w[d]));
-        asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(a1) : "v"(t1), "v"(w[d]));
-        m[2 * d] = *(lds_cu8 *)(uintptr_t)(lut_lds_address + a0);
-        m[2 * d + 1] = *(lds_cu8 *)(uintptr_t)(lut_lds_address + a1);
-    }
-    return (m[0] + m[1] + m[2]) + (m[3] + m[4] + m[5]) + (m[6] + m[7]);
-}
-__device__ __forceinline__ uint32_t st_maglut_chunk(const uint8_t *lut, const uint4 &raw, uint32_t four)   // 8 raw samples
-{
-    uint32_t m[8];
-    st_maglut_pair(lut, raw.x, four, m[0], m[1]);
-    st_maglut_pair(lut, raw.y, four, m[2], m[3]);
-    st_maglut_pair(lut, raw.z, four, m[4], m[5]);
-    st_maglut_pair(lut, raw.w, four, m[6], m[7]);
-    return (m[0] + m[1] + m[2]) + (m[3] + m[4] + m[5]) + (m[6] + m[7]);
+    acc = st_mag_raw_dword_q(raw.x, acc);
+    acc = st_mag_raw_dword_q(raw.y, acc);
+    acc = st_mag_raw_dword_q(raw.z, acc);
+    return st_mag_raw_dword_q(raw.w, acc);
 }
 
 // ---- input prefetch of the streaming kernels ----
@@ -268,10 +137,6 @@ __device__ __forceinline__ void gload_wait(uint32_t &r)
 {
     asm volatile("s_waitcnt vmcnt(%1) ; arrived %0" : "+v"(r) : "n"(N_YOUNGER));
 }
-
-#ifndef IQD_RINGS_IN_A_ROW
-#define IQD_RINGS_IN_A_ROW 0
-#endif
 
 // ---- producer / consumer plumbing of the streaming kernels (waves of one workgroup talking through LDS rings) ----
 // (through the LDS address space: on the generic pointer this is a flat_load, which travels the vector-memory path

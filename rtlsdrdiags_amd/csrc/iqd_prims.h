@@ -138,13 +138,9 @@ IQD_DEV uint32_t neg_bytes(uint32_t x, uint32_t mask)
 // operations per sample against fewer L1 misses).
 IQD_DEV uint32_t lut_index(uint32_t off)
 {
-#ifndef IQD_LUT_ROWS   // (row-major table: the A/B alternative)
     uint32_t t = (((off << 2) ^ off) & 0x03e0u) ^ off;      // bits 9..5 <- x7..x3       (v_lshlrev, v_bfi)
     t = (((off >> 5) ^ t) & 0x0018u) ^ t;                   // bits 4..3 <- y1 y0         (v_lshrrev, v_bfi)
     return t;
-#else
-    return off;
-#endif
 }
 
 // Branch-cut handling of the FM discriminators (WbFmDemodulator.cc:472-480,
@@ -197,10 +193,9 @@ IQD_DEV int dot2_from(uint32_t a, uint32_t b_scalar, int start)
 
 // Two such casts and the packing of their low halves in two instructions instead of three: v_cvt_i32_f32 with an SDWA
 // destination puts the low 16 bits of its result into one half of the register and leaves (or clears) the other.
-// (round 5; IQD_NO_CVT_SDWA: the two plain conversions and a v_perm_b32, for the A/B)
 IQD_DEV uint32_t cast_pack_i16_bounded(float lo, float hi)
 {
-#if IQD_ON_DEVICE && !defined(IQD_NO_CVT_SDWA)
+#if IQD_ON_DEVICE
     uint32_t r;
     asm("v_cvt_i32_f32_sdwa %0, %1 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD" : "=v"(r) : "v"(lo));
     asm("v_cvt_i32_f32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(r) : "v"(hi));

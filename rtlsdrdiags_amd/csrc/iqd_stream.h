@@ -51,11 +51,7 @@ constexpr int ST_AHEAD = IQD_ST_AHEAD;      // pieces of input a P wave keeps in
 constexpr int ST_MIN_TILE = 768;            // a segment's own end histories must not reach back before its start
 constexpr int ST_FIX_PCM = 21;              // PCM samples of a cold segment that depend on its predecessor's histories
 constexpr int ST_ROW_FLOATS = 260;          // half-table row stride (1040 B: bank = x + 4 r)
-#ifndef IQD_ST_FAKE_SHIFT
-#define IQD_ST_FAKE_SHIFT 0                 // TIMING PROBES ONLY (wrong PCM): the LDS copy of the table with its columns 2^shift apart dropped
-#endif
-constexpr int ST_LDS_ROW_FLOATS = IQD_ST_FAKE_SHIFT ? (256 >> IQD_ST_FAKE_SHIFT) + 4 : ST_ROW_FLOATS;
-constexpr int ST_TABLE_BYTES = 129 * ST_LDS_ROW_FLOATS * 4;
+constexpr int ST_TABLE_BYTES = 129 * ST_ROW_FLOATS * 4;
 constexpr int ST_SLOT_BYTES = 64 * 16 * 4;  // one window of one ring: 64 segments x 16 samples, f32
 #ifndef IQD_ST_DEPTH
 #define IQD_ST_DEPTH 1

@@ -11,20 +11,8 @@
 
 namespace iqd {
 
-// IQD_ST_WT_STORES (measurement build, tools/variant.sh): the IIR lanes' 16-byte stores - a lane's PCM leaves as whole 32-byte sectors,
-// its boundary record in 16-byte parts - as write-through stores, so that the launch leaves nothing dirty in the L2s for the
-// kernel boundary to write back (28.6 MB per 2^28-sample launch: PCM + records)
-#ifdef IQD_ST_WT_STORES
-__device__ __forceinline__ void st_store16(void *p, v4u v)
-{
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
-}
-#define ST_STORE16(P, A, B, C, D) st_store16((void *)(P), v4u{A, B, C, D})
-#elif defined(IQD_ST_NT_STORES)   // the same as non-temporal stores (the compiler's own: no register tuple forced on the lanes)
-#define ST_STORE16(P, A, B, C, D) __builtin_nontemporal_store(v4u{A, B, C, D}, (v4u *)(P))
-#else
+// The IIR lanes' and the audio wave's 16-byte stores: a lane's PCM and the parts of its boundary record.
 #define ST_STORE16(P, A, B, C, D) (*(u32x4 *)(P) = u32x4{A, B, C, D})
-#endif
 
 
 // The angle table starts at LDS address 0 (the kernel has no static LDS; checked when the kernel starts), so a table
@@ -52,34 +40,9 @@ __device__ __forceinline__ uint32_t st_table_read(uint32_t byte_offset) { return
 #ifndef IQD_ST_SLEEP_A    // the audio wave waiting for a piece of a y2 ring
 #define IQD_ST_SLEEP_A 10
 #endif
-#ifndef IQD_ST_RUNPTR     // 1: the P waves' input addresses as a running pointer (0: piece_address() per piece, A/B builds)
-#define IQD_ST_RUNPTR 1
-#endif
 // The IIR lanes' decimator taps: literals of the v_dot2c instructions (the designs are fixed, iqd_taps.h: STREAM_TAPS) instead of
 // 30 scalar registers that the wave could not keep (85 of its scalar registers spilled to vector lanes, 14 v_readlane per piece).
-// IQD_ST_TAPS_IN_SGPRS: from the kernel arguments as before (the A/B).
-#ifdef IQD_ST_TAPS_IN_SGPRS
-#define ST_TAP(WHICH, Q) sa.WHICH[Q]
-#else
 #define ST_TAP(WHICH, Q) (uint32_t)taps::STREAM_TAPS.WHICH[Q]
-#endif
-#ifndef IQD_ST_DOT2_FROM   // a chain's first product in the three-address form (iqd_prims.h: dot2_from); 0: the A/B
-#define IQD_ST_DOT2_FROM 1
-#endif
-#ifndef IQD_ST_YOUNG_SHIFT
-#define IQD_ST_YOUNG_SHIFT 0
-#endif
-#ifndef IQD_ST_LEVEL_PROBE
-#define IQD_ST_LEVEL_PROBE 0
-#endif
-// Lead-in of a ring whose 64 segments are all cold and of full length (the IIR wave's fast path): a cold segment's lead-in only
-// has to make its de-emphasis state exact (its decimators' histories are replaced by the boundary fix-up), which takes 319 steps
-// on average, p99.9 446, maximum 554 over 10^6 starts (tools/deemph_convergence.py); a state that has not converged is caught by
-// the hand-off verification and repaired by the tile kernel.  768 = every segment runs the full ST_HALO (rounds 2-4).
-#ifndef IQD_ST_COLD_HALO
-#define IQD_ST_COLD_HALO 768
-#endif
-static_assert(IQD_ST_COLD_HALO % 128 == 0 && IQD_ST_COLD_HALO <= 768 && IQD_ST_COLD_HALO >= 256, "cold lead-in: whole quads of pieces within ST_HALO");
 #ifndef IQD_ST_TRACE      // diagnostic build: workgroup 5 writes clock64() of (hardware wave, piece, event k) to stamps[64 + ((wave * 256 + piece) * 4 + k)]
 #define IQD_ST_TRACE 0
 #endif
@@ -115,14 +78,7 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
     // a ring's four P waves are every third wave, not four in a row: the hardware issues oldest wave first, and with
     // rings of neighbouring waves ring 0 ran a third ahead of ring 2 (per-wave end times 115 / 137 / 155 us), which left
     // the last ring to finish on a nearly empty CU.  Now every ring has a wave of each age.
-#if IQD_RINGS_IN_A_ROW
-    const int ring = pw / ST_P_PER_RING, cg = pw % ST_P_PER_RING;
-#else
-    // (IQD_ST_YOUNG_SHIFT: the three youngest P waves - hardware waves 12-14, each the last-served wave of a SIMD that also
-    // carries an IIR wave - feed the ring of ANOTHER SIMD's IIR wave: a ring's IIR wave starts its burst when the ring's last
-    // writer has signalled, i.e. exactly when that writer begins its next piece)
-    const int cg = pw / ST_RINGS, ring = (pw + (cg == ST_P_PER_RING - 1 ? IQD_ST_YOUNG_SHIFT : 0)) % ST_RINGS;
-#endif
+    const int cg = pw / ST_RINGS, ring = pw % ST_RINGS;
     if (ring >= (int)sa.rings) return;                           // (a workgroup of fewer rings: this wave's is not there)
     const uint32_t wg_segs = 64u * sa.rings;                     // segments per workgroup and round
     const int g = lane >> 4, c = lane & 15;
@@ -152,14 +108,6 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
         int rot_of_id = ROT;
         const StSeg sg = BYGROUP ? st_segment_of(a, sa, sid, rot_of_id) : st_segment(a, sid, sa.n_segments);
         if (BYGROUP && __builtin_amdgcn_readfirstlane(rot_of_id) != ROT) continue;   // (uniform: groups are padded to 16 ids)
-        // pieces of the lead-in this ring skips (IQD_ST_COLD_HALO): the IIR wave's `fast` predicate, evaluated here over the ring's
-        // 64 ids, one per lane - the ring's five waves must agree on it
-        int q_first = 0;
-        if (IQD_ST_COLD_HALO < ST_HALO && !BYGROUP && !GATED && !EPOCHS) {
-            const StSeg ps = st_segment(a, sid - row + (uint32_t)lane, sa.n_segments);
-            q_first = __all(st_cold_and_full(ps, a.tile_len)) ? (ST_HALO - IQD_ST_COLD_HALO) / 32 : 0;
-        }
-        const int lead = ST_HALO - 32 * q_first;                 // this ring's lead-in, samples
         const ChanParams &p = a.params[sg.ech];
         const uint8_t *iq_ch = a.iq + (size_t)sg.ch * a.ch_stride_bytes;
         const uint8_t *tail = a.tails + ((size_t)sg.ech * FAM_COUNT + FAM_WBFM) * TAIL_BYTES + TAIL_BYTES;
@@ -213,11 +161,11 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
         // first segment's lead-in ends (below, once per segment) - instead of piece_address()'s six operations per piece.
         const int32_t pos_last = pos_max & ~31;
         const bool from_tail = sg.v0 == 0;                       // (tile_len >= ST_MIN_TILE = ST_HALO: only a first segment's lead-in reads the tail inside the loop)
-        const uint8_t *nxt = piece_address(-lead + 32 * ST_AHEAD);
-        uint4 prev = st_front<ROT>(*(const uint4 *)piece_address(-lead - 32), zero);
+        const uint8_t *nxt = piece_address(-ST_HALO + 32 * ST_AHEAD);
+        uint4 prev = st_front<ROT>(*(const uint4 *)piece_address(-ST_HALO - 32), zero);
         v4u raw[ST_AHEAD];
 #pragma unroll
-        for (int j = 0; j < ST_AHEAD; j++) raw[j] = gload16_untracked(piece_address(-lead + 32 * j));
+        for (int j = 0; j < ST_AHEAD; j++) raw[j] = gload16_untracked(piece_address(-ST_HALO + 32 * j));
         // theta' of the sample before the lead-in (a warm segment's carried state applies from the lead-in's very first
         // sample, whose delta theta needs it): the last output of the piece before, from that piece's "N" window
         float last_prev;                                         // theta'[3] of this lane's previous window
@@ -249,13 +197,6 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
             const int pos = -ST_HALO + 32 * q;
             ST_TRACE(a.stamps, pw + 3, q, 0);
             ST_T(t0);
-#ifdef IQD_ST_BURN_SIMD   // measurement build: the P waves of ONE SIMD (hardware wave % 4) issue IQD_ST_BURN_N idle vector instructions per piece
-            if (((pw + ST_RINGS) & 3) == IQD_ST_BURN_SIMD) {
-                float burn = 1.0f;
-#pragma unroll
-                for (int k = 0; k < IQD_ST_BURN_N; k++) asm volatile("v_add_f32 %0, %0, %0" : "+v"(burn));
-            }
-#endif
             gload_wait<ST_AHEAD - 1>(raw[j]);                    // younger than this buffer's load: the other buffers' loads
             ST_T(t1);
             const uint4 raw_cur = as_uint4(raw[j]);              // (offset binary, as loaded: the squelch magnitudes below)
@@ -286,9 +227,9 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
                     const uint32_t tq = (uint32_t)acc[half][2][r] + ((uint32_t)acc[half][3][r] << 8);
                     uint32_t rr;                                 // |y| = |byte 2 of tq - 128|
                     asm("v_msad_u8 %0, %1, %2, 0" : "=v"(rr) : "v"(tq), "s"(0x00800000u));
-                    const uint32_t x4 = bfe(ti, 16 + IQD_ST_FAKE_SHIFT, 8 - IQD_ST_FAKE_SHIFT) << 2;
+                    const uint32_t x4 = bfe(ti, 16, 8) << 2;
                     uint32_t addr;                               // row |y|, column x of the half table
-                    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(rr), "s"((uint32_t)(ST_LDS_ROW_FLOATS * 4)), "v"(x4));
+                    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(rr), "s"((uint32_t)(ST_ROW_FLOATS * 4)), "v"(x4));
                     traw[half][r] = st_table_read(addr);
                     tqs[half][r] = tq;
                 }
@@ -296,23 +237,9 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
             uint32_t seen = lds_load_relaxed(consumed);          // asked early, needed only before the ring stores
             // phase B: squelch magnitudes of this lane's 8 samples, while the gathers are in flight (two packed 16-bit sums,
             // folded and booked once per group of pieces: at most 4 x 4 x 192 per half)
-            if (MAG && pos >= 0) {
-#if IQD_ST_LEVEL_PROBE   // TIMING PROBE ONLY (wrong magnitudes): what levelling the SIMDs could buy at most - the P waves of the three
-                         // SIMDs that carry an IIR wave skip the magnitude arithmetic, those of the fourth do it four times
-                if (IQD_ST_LEVEL_PROBE == 1 && (pw & 3) == 0) {   // (2: nobody does them)
-                    uint4 rc = raw_cur;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        asm volatile("" : "+v"(rc.x), "+v"(rc.y), "+v"(rc.z), "+v"(rc.w));
-                        gm16 = st_mag_raw_chunk(rc, gm16);
-                    }
-                }
-#else
-                gm16 = st_mag_raw_chunk(raw_cur, gm16);
-#endif
-            }
+            if (MAG && pos >= 0) gm16 = st_mag_raw_chunk(raw_cur, gm16);
             // (after the last use of the buffer's old contents)
-            if (GATED || !IQD_ST_RUNPTR) {
+            if (GATED) {
                 raw[j] = gload16_untracked(piece_address(pos + 32 * ST_AHEAD));
             } else {
                 raw[j] = gload16_untracked(nxt);
@@ -343,12 +270,8 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
                     m.y = __builtin_rintf(m.y);
                     d = __builtin_elementwise_fma(-m, v2f{6.28318548202514648f, 6.28318548202514648f}, d);
                     d = __builtin_elementwise_fma(-m, v2f{-1.74845553146951715e-7f, -1.74845553146951715e-7f}, d);
-#if IQD_RELAXED_TOL   // (timing A/B only: one rounding instead of two)
-                    const v2f w = d * v2f{kk * sa.b0, kk * sa.b0};
-#else
                     const v2f v = d * v2f{kk, kk};
                     const v2f w = v2f{sa.b0, sa.b0} * v;
-#endif
                     u[half][r] = w.x;
                     u[half][r + 1] = w.y;
                 }
@@ -377,14 +300,14 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
 #endif
         };
         uint4 other;
-        for (int q = q_first; q < n_pieces; q += ST_AHEAD) {   // (n_pieces and q_first are multiples of 4)
+        for (int q = 0; q < n_pieces; q += ST_AHEAD) {   // (n_pieces is a multiple of 4)
 #pragma unroll
             for (int j = 0; j < ST_AHEAD; j += 2) {
                 do_piece(q + j, j, prev, other);
                 do_piece(q + j + 1, j + 1, other, prev);
             }
             const int gpos = -ST_HALO + 32 * q;                  // the group's first sample
-            if (!GATED && IQD_ST_RUNPTR && gpos + 64 * ST_AHEAD == 0)   // (recomputed here, once per segment: two registers fewer through the loop)
+            if (!GATED && gpos + 64 * ST_AHEAD == 0)   // (recomputed here, once per segment: two registers fewer through the loop)
                 nxt = from_tail ? a.iq + (size_t)sg.ch * a.ch_stride_bytes + 16 * g : nxt;   // the next piece asked for is the one at position 0
             if (MAG && gpos >= 0) {
                 const uint32_t m = (gm16 & 0xffffu) + (gm16 >> 16);
@@ -460,12 +383,7 @@ __device__ __forceinline__ int st_iir_window(const StreamArgs &sa, StIir &s, con
     uint32_t y1[4];
 #pragma unroll
     for (int o = 0; o < 4; o++) {                      // window x[4m-4 .. 4m+3] <-> taps h[7 .. 0]
-#if IQD_ST_DOT2_FROM
         int acc = dot2_from(wq[2 * o], sa.d1p2[0], c15);
-#else
-        int acc = c15;
-        acc = dot2(wq[2 * o], ST_TAP(d1p2, 0), acc);
-#endif
         acc = dot2(wq[2 * o + 1], ST_TAP(d1p2, 1), acc);
         acc = dot2(wq[2 * o + 2], ST_TAP(d1p2, 2), acc);
         acc = dot2(wq[2 * o + 3], ST_TAP(d1p2, 3), acc);
@@ -473,15 +391,9 @@ __device__ __forceinline__ int st_iir_window(const StreamArgs &sa, StIir &s, con
     }
     // stage 2: output k from y1[4k-8 .. 4k+3], 12 taps, newest pair first
     const uint32_t d[6] = {s.y1h[0], s.y1h[1], s.y1h[2], s.y1h[3], pack_hi16(y1[0], y1[1]), pack_hi16(y1[2], y1[3])};
-#if IQD_ST_DOT2_FROM
     int acc = dot2_from(d[5], sa.p12p[0], c14);
 #pragma unroll
     for (int q = 1; q < 6; q++) acc = dot2(d[5 - q], ST_TAP(p12p, q), acc);
-#else
-    int acc = c14;
-#pragma unroll
-    for (int q = 0; q < 6; q++) acc = dot2(d[5 - q], ST_TAP(p12p, q), acc);
-#endif
     s.y1h[0] = d[2];
     s.y1h[1] = d[3];
     s.y1h[2] = d[4];
@@ -619,11 +531,11 @@ __device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamA
 // The lead-in of a wave whose segments are all cold: only the de-emphasis recurrence (its state is what the lead-in is
 // for; a cold segment's decimators start with histories that the boundary fix-up replaces anyway).
 __device__ __forceinline__ void st_iir_lead_in(const StreamArgs &sa, uint8_t *ring_base, const uint32_t *full, uint32_t *consumed,
-                                               uint32_t &wg, StIir &s, uint32_t rd_off0, uint32_t rd_swz, int lead)
+                                               uint32_t &wg, StIir &s, uint32_t rd_off0, uint32_t rd_swz)
 {
     float y = s.y, up = s.up;
     const float a1 = sa.a1;
-    for (int piece = 0; piece < lead / 32; piece++) {   // (the ring's P waves skip the same pieces: st_p_wave, q_first)
+    for (int piece = 0; piece < ST_HALO / 32; piece++) {
         const uint32_t target = 4u * (wg / (uint32_t)ST_DEPTH + 1u);
         while ((int32_t)(lds_load_relaxed(ST_DEPTH > 1 ? full + (wg & (uint32_t)(ST_DEPTH - 1)) : full) - target) < 0) __builtin_amdgcn_s_sleep(IQD_ST_SLEEP_I);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -646,10 +558,8 @@ __device__ __forceinline__ void st_iir_lead_in(const StreamArgs &sa, uint8_t *ri
     s.up = up;
 }
 
-// lead_cold: the lead-in of a ring whose segments are all cold and of full length (IQD_ST_COLD_HALO where the launch's P waves
-// take it, ST_HALO otherwise)
 __device__ __forceinline__ void st_iir_wave(const ChainLaunch &a, const StreamArgs &sa, uint8_t *lds, uint32_t *sync,
-                                            int ring, int lane, int lead_cold)
+                                            int ring, int lane)
 {
     uint8_t *ring_base = lds + ST_TABLE_BYTES + ring * (ST_RING_SLOTS * ST_SLOT_BYTES);
     const uint32_t *full = sync + ring * 8;
@@ -710,13 +620,12 @@ __device__ __forceinline__ void st_iir_wave(const ChainLaunch &a, const StreamAr
         const long long t_iir0 = clock64();
 #endif
         // (a segment that is not there has tlen 0 and stores nothing: it may run along with any kind of wave)
-        // (the P waves evaluate the same predicate, st_cold_and_full(): a ring's waves must agree on its lead-in - and the audio
-        // wave this very one, st_audio_wave)
+        // (the audio wave evaluates this very predicate: st_audio_ring_start)
         const bool fast = st_ring_is_fast(q.sg.valid, q.back, q.sg.tlen, a.tile_len, keeps_restart);
         if (keeps_restart) q.sg.valid |= 2u;
         const int rec_pos_uniform = (int)a.tile_len - FORCED_BACK;
         if (fast) {
-            st_iir_lead_in(sa, ring_base, full, consumed, wg, s, rd_off0, rd_swz, lead_cold);
+            st_iir_lead_in(sa, ring_base, full, consumed, wg, s, rd_off0, rd_swz);
             q.rec.y_in = s.y;                                    // the warmed-up state, checked against the predecessor's end
             for (int pq = ST_HALO / 32; pq < n_pieces; pq++)
                 st_iir_piece<true>(a, sa, ring_base, full, consumed, wg, y2r, yk, q, s, -ST_HALO + 32 * pq, rd_off0, rd_swz, lane, rec_pos_uniform);
@@ -757,14 +666,9 @@ __device__ __forceinline__ int st_audio(const StreamArgs &sa, const uint32_t (&y
 {
     int acc = c14;
     if (quiet) {
-#if IQD_ST_DOT2_FROM
         acc = dot2_from(y2p[V + 20], sa.a40p[0], c14);
 #pragma unroll
         for (int q = 1; q < 20; q++) acc = dot2(y2p[V + 20 - q], ST_TAP(a40p, q), acc);
-#else
-#pragma unroll
-        for (int q = 0; q < 20; q++) acc = dot2(y2p[V + 20 - q], ST_TAP(a40p, q), acc);
-#endif
     } else {
 #pragma unroll
         for (int q = 0; q < 20; q++) {
@@ -933,7 +837,7 @@ __device__ __forceinline__ void wbfm_stream_body(const ChainLaunch &a, const Str
 #if IQD_ST_TIMING   // which SIMD each of the workgroup's waves sits on (HW_ID), + 1: stamps[20000 + wave], tools/simd_of_waves.py
     if (blockIdx.x == 0 && lane == 0) a.stamps[20000 + wave] = (unsigned long long)(st_simd_id() + 1);
 #endif
-    if (wave < ST_RINGS) st_iir_wave(a, sa, st_lds, sync, wave, lane, ROT != 2 && !GATED && !EPOCHS ? IQD_ST_COLD_HALO : ST_HALO);
+    if (wave < ST_RINGS) st_iir_wave(a, sa, st_lds, sync, wave, lane);
     else if (wave == ST_AUDIO_WAVE) st_audio_wave(a, sa, st_lds, sync, lane);
     else if (ROT != 2) st_p_wave<ROT, MAG, EPOCHS, GATED>(a, sa, st_lds, sync, wave - ST_RINGS, lane, pc);
     else {   // channels of several rotation selectors: the groups in their order

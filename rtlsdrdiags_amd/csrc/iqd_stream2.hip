@@ -3,8 +3,8 @@
 // at a time.
 //
 //   12 P waves, 16 segments each: raw bytes (four pieces of input in flight per wave, iqd_mfma.h: gload16_untracked)
-//       -> squelch magnitude of the raw samples, one quad-SAD per dword (rounds 3-4: through a 68 KiB table in LDS; since round 5
-//       that LDS holds rings of 16 pieces instead of 8, IQD_D4_MAGLUT / IQD_D4_SLOTS) -> signed, rotation signs (SDWA) -> the
+//       -> squelch magnitude of the raw samples, one quad-SAD per dword (no table: the LDS holds rings of 16 pieces,
+//       IQD_D4_SLOTS) -> signed, rotation signs (SDWA) -> the
 //       chain's first /4 decimator on both rails as v_mfma_i32_16x16x64_i8 (FM: 32-tap tuner filter, AM/SSB: 8 taps;
 //       the part of the window that lies in the previous piece through a second, chained MFMA) ->
 //       AM/SSB: 8 + 8 int16 outputs per piece into the ring
@@ -34,42 +34,9 @@
 #include "iqd_mfma.h"
 #include "iqd_taps.h"
 
-// build-time experiments (tools/variant.sh): all off in the shipped library
-#ifndef IQD_D4_SPLIT
-#define IQD_D4_SPLIT 0
-#endif
-#ifndef IQD_D4_PRIO
-#define IQD_D4_PRIO 0
-#endif
-#ifndef IQD_D4_TIMING
-#define IQD_D4_TIMING 0
-#endif
-// 1: a segment's four lanes LOAD as neighbours (lane 4 c + k: 64 contiguous bytes per segment and load instruction) and four
-// ds_bpermute put the bytes where the matrix instruction wants them (lane 16 k + c).  Built in round 3 and then ±2 %: the LDS
-// pipe was busy with the magnitude table's gathers.  With those gone (IQD_D4_MAGLUT=3) the permutes are cheap and the better
-// read pattern shows: FM 0.2439 -> 0.2207 ms, USB 0.1961 -> 0.1849, AM 0.1731 -> 0.1707 (profiles/r5_d4_ring_depth.txt).  0: the A/B.
-#ifndef IQD_D4_TRANSPOSE
-#define IQD_D4_TRANSPOSE 1
-#endif
-// Squelch magnitudes of the P waves: 3 = one quad-SAD per dword on the raw bytes (iqd_mfma.h: st_mag_raw_chunk), no table; 1 = the
-// 68 KB table in LDS of rounds 3-4.  Round 5 (profiles/r5_d4_ring_depth.txt, one box, interleaved): these kernels do not wait for
-// issue slots - 32 idle vector instructions per piece in the P waves or in the consumer waves cost +0.5 % - so the SADs' extra
-// instructions are free, and the LDS the table leaves behind holds rings of 16 pieces instead of 8: AM 0.1913 -> 0.1826 (no
-// table) -> 0.1821 (16 slots), USB 0.2057 -> 0.1982 -> 0.1915, FM 0.2495 -> 0.2443 -> 0.2435 ms.
-#ifndef IQD_D4_MAGLUT
-#define IQD_D4_MAGLUT 3
-#endif
-#ifndef IQD_D4_WAITSTAT
-#define IQD_D4_WAITSTAT 0
-#endif
 // The FM consumer lanes' decimator taps as literals of the v_dot2c instructions (iqd_taps.h: STREAM_TAPS, the designs are fixed)
 // instead of 26 scalar registers (the FM kernels had 33-35 of their scalar registers spilled to vector lanes).
-// IQD_D4_TAPS_IN_SGPRS: from the kernel arguments as before (the A/B).
-#ifdef IQD_D4_TAPS_IN_SGPRS
-#define D4_TAP(WHICH, Q) da.WHICH[Q]
-#else
 #define D4_TAP(WHICH, Q) (uint32_t)taps::STREAM_TAPS.WHICH[Q]
-#endif
 #ifndef IQD_D4_SLEEP_P      // s_sleep argument (x 64 cycles) between two looks at a ring counter: P waves / consumer waves
 #define IQD_D4_SLEEP_P 1
 #endif
@@ -88,22 +55,15 @@ constexpr int D4_QUADS = D4_SLOTS / 4;            // the waves shake hands once 
 // a "consumed" counter per ring (quads the consumer wave has read)
 constexpr int D4_SYNC_WORDS = ST_RINGS * D4_QUADS + 8;
 static_assert(D4_SLOTS % 4 == 0 && (D4_QUADS & (D4_QUADS - 1)) == 0 && D4_QUADS >= 2, "ring depth");
-// Pieces of input a P wave keeps in flight: 4.  (FM's two angle loads per piece are counted with them.  IQD_D4_AHEAD_AM=8: AM / SSB
-// with eight - built and bit-exact in round 5 on the thought that kernels which do not wait for issue slots wait for memory; they
-// do not: AM 0.1735 -> 0.1811 ms, USB 0.1931 -> 0.1936, profiles/r5_d4_ring_depth.txt.)
-#ifndef IQD_D4_AHEAD_AM
-#define IQD_D4_AHEAD_AM 4
-#endif
-template <int MODE> constexpr int d4_ahead() { return MODE == D4_FM ? 4 : IQD_D4_AHEAD_AM; }
+constexpr int D4_AHEAD = 4;                       // pieces of input a P wave keeps in flight (FM's two angle loads per piece are counted with them)
 constexpr int D4_SLOT_BYTES = 64 * 32;            // 64 segments x (4 lanes x 8 bytes) per piece
-constexpr int D4_MAGLUT_OFF = (ST_RINGS * D4_SLOTS * D4_SLOT_BYTES + D4_SYNC_WORDS * 4 + 15) & ~15;   // squelch magnitude table (iqd_mfma.h)
 // Round 6 (iqd_stream.h, d4_geom): every consumer lane keeps the inputs of its segment's first outputs here - the y2 pairs of pieces 4..7
 // (AM / SSB, both rails: 8 words), SSB's 8 kS/s rails of pieces 8..39 (32 words), FM's y2 pairs of pieces 4..23 (20 words) - and
 // replays those outputs at the end of its run with its predecessor's end state, which sits in the lane below.  [word][segment].
 constexpr int D4_HEAD_WORDS = 40;   // per segment: AM 2 x 4 pairs; SSB those + 32 rails; FM 20 pairs
 static_assert(D4_HEAD_WORDS >= 2 * D4_REPLAY_PAIRS_AMSSB + (D4_REPLAY_SSB - D4_REPLAY_PAIRS_AMSSB) && D4_HEAD_WORDS >= D4_REPLAY_FM, "head store");
 static_assert(D4_RAILS_FROM_PIECE == 4 + D4_REPLAY_PAIRS_AMSSB && D4_REPLAY_AM == D4_REPLAY_PAIRS_AMSSB, "replay layout");
-constexpr int D4_HEAD_OFF = D4_MAGLUT_OFF + (IQD_D4_MAGLUT == 1 ? ST_MAGLUT_BYTES : 0);
+constexpr int D4_HEAD_OFF = (ST_RINGS * D4_SLOTS * D4_SLOT_BYTES + D4_SYNC_WORDS * 4 + 15) & ~15;
 constexpr int D4_LDS_BYTES = D4_HEAD_OFF + D4_HEAD_WORDS * ST_SEGS * 4;
 static_assert(D4_LDS_BYTES <= 160 * 1024, "rings + head store must fit the CU's LDS");
 
@@ -162,19 +122,15 @@ __device__ __forceinline__ uint32_t d4_ring_off(uint32_t row, uint32_t g) { retu
 // where its bytes are) and looks the next one up when it leaves it - once per block_samples / 32 pieces.
 template <int MODE, bool MAG, int ROT, bool GATED>
 __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &da, const D4Seg &sg, const D4Seg &sgl, uint8_t *ring_base,
-                                           const uint32_t *full, const uint32_t *consumed, uint32_t *sync, uint32_t wr_off,
+                                           const uint32_t *full, const uint32_t *consumed, uint32_t wr_off,
                                            int g, int lane, uint32_t &pg)
 {
-#if IQD_D4_TRANSPOSE
         const int gl = lane & 3;                                 // k group of the bytes this lane loads
         const int from_lane4 = (4 * (lane & 15) + (lane >> 4)) << 2;   // ds_bpermute address: who loaded this lane's operand
-#else
-        const int gl = g;
-#endif
         const int rot = ROT;
         const v4i cround = {1 << 14, 1 << 14, 1 << 14, 1 << 14}, czero = {0, 0, 0, 0};
         uint32_t zero = 0, four = 4;
-        asm volatile("" : "+v"(zero), "+v"(four));
+        asm volatile("" : "+v"(zero), "+v"(four));               // (four: nothing reads it any more; its register goes with the next change that may move the assembly)
         const int n_pieces = (da.halo + (int)a.tile_len) >> 5;
         const v4i *am = (const v4i *)da.amat + (size_t)(rot + 1) * 4 * 64;
         const v4i A0 = am[0 * 64 + lane], A1 = am[1 * 64 + lane], A2 = am[2 * 64 + lane], A3 = am[3 * 64 + lane];
@@ -190,9 +146,6 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
         auto load_piece = [&](int pos) -> v4u {
             const int32_t pc = pos < pos_max ? pos : pos_max;
             if (!GATED) {
-#ifdef IQD_D4_PROBE_CACHED   // TIMING PROBE ONLY (wrong results): every lane re-reads a 512-byte window of its segment - the loads hit L2
-                return gload16_untracked(base_iq + 2 * (int64_t)(pc & 0xff));
-#endif
                 const uint8_t *base = pc < -vlane ? base_tail : base_iq;
                 return gload16_untracked(base + 2 * (int64_t)pc);
             }
@@ -206,22 +159,15 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
             const uint8_t *addr = vv < 0 ? base_tail + 2 * (int64_t)pc : gb_base + 2 * (int64_t)vv;
             return gload16_untracked(addr);
         };
-#if IQD_D4_TRANSPOSE
         auto front = [&](uint4 raw) -> uint4 {                   // signed bytes, rotation signs, then to the matrix arrangement
             const uint4 f = st_front<ROT>(raw, zero);
             return uint4{(uint32_t)__builtin_amdgcn_ds_bpermute(from_lane4, (int)f.x), (uint32_t)__builtin_amdgcn_ds_bpermute(from_lane4, (int)f.y),
                          (uint32_t)__builtin_amdgcn_ds_bpermute(from_lane4, (int)f.z), (uint32_t)__builtin_amdgcn_ds_bpermute(from_lane4, (int)f.w)};
         };
-#else
-        auto front = [&](uint4 raw) -> uint4 { return st_front<ROT>(raw, zero); };
-#endif
         uint32_t *mag_row = MAG ? a.mag_sums + (size_t)sgl.ch * a.n_blocks : nullptr;
         const bool mcount = MAG && sgl.valid;
         const int32_t mlimit = sgl.tlen - 8 * gl;
         const int32_t mfirst = sgl.skip;                          // (a cold segment: what lies before its first output is lead-in)
-#if IQD_D4_TIMING
-        long long t_ring_wait = 0;
-#endif
         uint32_t macc = 0;
         uint32_t mblk = sgl.v0 < 0 ? 0u : (uint32_t)(sgl.v0 + 8 * gl) / a.block_samples;
         int32_t minblk = sgl.v0 + 8 * gl - (int32_t)(mblk * a.block_samples);   // position in the block (negative: before the call)
@@ -230,31 +176,12 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
         // before a quad's first store - its four slots are free once the consumer has read the quad D4_QUADS back - and
         // the quad is published after its last.
         auto hand_over = [&](u32x2 payload, int sq) {
-#ifdef IQD_D4_DYNPRIO
-            // A P wave that runs ahead of its ring's consumer yields to the ones that lag (the SIMD serves oldest first: the in-kernel
-            // timing shows the youngest P wave of a ring getting what the three older ones leave - 2200 cycles per piece against their
-            // 900 - while those then wait for ring space): priority by lag, once per quad, from the counter the wave reads anyway.
-            if (sq == 0) {
-                const uint32_t seen0 = lds_load_relaxed(consumed);
-                if ((int32_t)(pg - seen0) >= IQD_D4_DYNPRIO) __builtin_amdgcn_s_setprio(0);
-                else __builtin_amdgcn_s_setprio(2);
-            }
-#endif
             if (sq == 0 && pg >= (uint32_t)D4_QUADS) {
                 uint32_t seen = lds_load_relaxed(consumed);
-#if IQD_D4_TIMING
-                const long long tw0 = clock64();
-#endif
                 while ((int32_t)(seen - (pg - (D4_QUADS - 1))) < 0) {
-#if IQD_D4_WAITSTAT
-                    if (lane == 0) atomicAdd(&sync[D4_SYNC_WORDS - 2], 1u);
-#endif
                     __builtin_amdgcn_s_sleep(IQD_D4_SLEEP_P);
                     seen = lds_load_relaxed(consumed);
                 }
-#if IQD_D4_TIMING
-                t_ring_wait += clock64() - tw0;
-#endif
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             }
             uint8_t *slot = ring_base + ((pg & (D4_QUADS - 1)) * 4 + (uint32_t)sq) * D4_SLOT_BYTES + wr_off;
@@ -280,9 +207,6 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
             asm volatile("" :: "v"(k_now), "v"(reach));
         }
         uint32_t asked_a[2] = {0, 0}, asked_b[2] = {0, 0};
-#if IQD_D4_TIMING
-        long long t_wait_raw = 0, t_front_mag = 0, t_post_hand = 0;
-#endif
         auto fm_finish = [&](int pos, uint32_t ta_bits, uint32_t tb_bits, int sq) {
             const float ta = u2f(ta_bits), tb = u2f(tb_bits);
             const float give_a = g == 3 ? last_a : ta, give_b = g == 3 ? last_b : tb;
@@ -303,8 +227,7 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
         // buffers of a loop unrolled by four: handing a buffer on with register moves would wait for the load it has
         // just issued.  Waits count the loads issued since (iqd_mfma.h): per piece one of these, for FM two angles more.
         constexpr int PER_PIECE = MODE == D4_FM ? 3 : 1;
-        constexpr int D4_AHEAD = d4_ahead<MODE>();             // (4 or 8: whole quads; the ring slot of buffer j is j & 3)
-        static_assert(D4_AHEAD % 4 == 0 && (PER_PIECE == 1 || D4_AHEAD == 4), "prefetch depth");
+        static_assert(D4_AHEAD == 4, "the ring slot of buffer j is j: a quad");
         v4u raw_before = load_piece(-da.halo - 32);
         v4u raw[D4_AHEAD];
 #pragma unroll
@@ -316,25 +239,11 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
         // time made the compiler copy the buffer, still in flight, in front of one of the two waits.
         auto piece = [&](auto first, int q0, int j) {
             const int pos = -da.halo + 32 * (q0 + j);
-#ifdef IQD_D4_BURN_SIMD   // measurement build: the P waves of ONE SIMD (hardware wave % 4) issue IQD_D4_BURN_N idle vector instructions per piece
-            if (((int)(threadIdx.x >> 6) & 3) == IQD_D4_BURN_SIMD) {
-                float burn = 1.0f;
-#pragma unroll
-                for (int k = 0; k < IQD_D4_BURN_N; k++) asm volatile("v_add_f32 %0, %0, %0" : "+v"(burn));
-            }
-#endif
-#if IQD_D4_TIMING
-            const long long tA = clock64();
-#endif
             // younger than raw[j]: the other three buffers' loads, plus the angles asked for since its own issue (in
             // the first trip: since the start)
             if (PER_PIECE == 1 || !decltype(first)::value) gload_wait<D4_AHEAD - 1 + (PER_PIECE - 1) * D4_AHEAD>(raw[j]);
             else gload_wait_n(raw[j], D4_AHEAD - 1 + (PER_PIECE - 1) * j);
             const uint4 rawj = as_uint4(raw[j]);
-#if IQD_D4_TIMING
-            const long long tB = clock64();
-            t_wait_raw += tB - tA;
-#endif
             const uint4 cur = front(rawj);
             const v4i bc = {(int)cur.x, (int)cur.y, (int)cur.z, (int)cur.w};
             const v4i bp = {(int)prev.x, (int)prev.y, (int)prev.z, (int)prev.w};
@@ -343,20 +252,8 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
             lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(A2, bp, lo, 0, 0, 0);
             hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(A3, bp, hi, 0, 0, 0);
             if (MAG && pos >= 0) {
-#if IQD_D4_MAGLUT == 1
-                const uint32_t m = st_maglut_chunk_at((uint32_t)D4_MAGLUT_OFF, rawj, four);
-#elif IQD_D4_MAGLUT == 2   // masked SADs on the raw bytes (iqd_mfma.h: st_mag_raw_dword), no table
-                uint32_t m16 = st_mag_raw_dword(rawj.x, 0u);
-                m16 = st_mag_raw_dword(rawj.y, m16);
-                m16 = st_mag_raw_dword(rawj.z, m16);
-                m16 = st_mag_raw_dword(rawj.w, m16);
+                const uint32_t m16 = st_mag_raw_chunk(rawj, 0u);   // one quad-SAD per dword (iqd_mfma.h: st_mag_raw_dword_q)
                 const uint32_t m = (m16 & 0xffffu) + (m16 >> 16);
-#elif IQD_D4_MAGLUT == 3   // one quad-SAD per dword (iqd_mfma.h: st_mag_raw_dword_q), no table: AM -0.5 %, USB -1 %, FM +5 % (round 4)
-                const uint32_t m16 = st_mag_raw_chunk(rawj, 0u);
-                const uint32_t m = (m16 & 0xffffu) + (m16 >> 16);
-#else
-                const uint32_t m = st_mag_chunk(cur);
-#endif
                 macc += mcount && pos < mlimit && pos >= mfirst ? m : 0u;
                 if ((j & 3) == 3) {   // blocks, segments and lead-ins are whole quads: the boundary test once per quad
                     minblk += 128;
@@ -368,10 +265,6 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
                     }
                 }
             }
-#if IQD_D4_TIMING
-            const long long tC = clock64();
-            t_front_mag += tC - tB;
-#endif
             // the buffer's next load only now, after the last use of its old contents: while those are live the new
             // load would get other registers and the loop would have to move it back - reading registers in flight
             raw[j] = load_piece(pos + 32 * D4_AHEAD);
@@ -392,14 +285,7 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
                 hand_over(u32x2{pack_lo16((uint32_t)y[0], (uint32_t)y[2]), pack_lo16((uint32_t)y[1], (uint32_t)y[3])}, j & 3);
             }
             prev = cur;
-#if IQD_D4_TIMING
-            const long long tD = clock64();
-            t_post_hand += tD - tC;
-#endif
         };
-#if IQD_D4_TIMING
-        const long long t_round0 = clock64();
-#endif
         int q_start = 0;
         if (PER_PIECE > 1) {                                    // (n_pieces is a multiple of 4 and at least 12)
 #pragma unroll
@@ -411,12 +297,6 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
 #pragma unroll
             for (int j = 0; j < D4_AHEAD; j++) piece(std::false_type{}, q0, j);
         }
-        // eight in flight and an odd number of quads: the last quad is the start of another trip (buffers 0 .. 3; the loads
-        // younger than each of them are the same seven as in every trip)
-        if (D4_AHEAD > 4 && q0 < n_pieces) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) piece(std::false_type{}, q0, j);
-        }
         // the loads asked for beyond the last piece (clamped re-reads) must have landed before their registers move on
 #pragma unroll
         for (int j = 0; j < D4_AHEAD; j++) gload_wait<0>(raw[j]);
@@ -426,11 +306,6 @@ __device__ __forceinline__ void d4_p_round(const ChainLaunch &a, const D4Args &d
             fm_finish(-da.halo + 32 * (n_pieces - 1), asked_a[(D4_AHEAD - 1) & 1], asked_b[(D4_AHEAD - 1) & 1], 3);
         }
         if (MAG && macc) atomicAdd(&mag_row[mblk], macc);
-#if IQD_D4_TIMING
-        if ((blockIdx.x & 63) == 7 && lane == 0)
-            printf("wg %u P wave %d: round %lld cycles for %d pieces: wait_raw %lld front+mfma+mag %lld post+handover %lld (of which ring-space wait %lld)\n", blockIdx.x,
-                   (int)(threadIdx.x >> 6), clock64() - t_round0, n_pieces, t_wait_raw, t_front_mag, t_post_hand, t_ring_wait);
-#endif
 }
 
 template <int MODE, bool MAG, bool GATED>
@@ -439,15 +314,8 @@ __device__ __forceinline__ void d4_p_wave(const ChainLaunch &a, const D4Args &da
     // a ring's four P waves are every third wave, not four in a row: the hardware issues oldest wave first, and with
     // rings of neighbouring waves ring 0 ran a third ahead of ring 2 (per-wave end times 115 / 137 / 155 us), which left
     // the last ring to finish on a nearly empty CU.  Now every ring has a wave of each age.
-#if IQD_RINGS_IN_A_ROW
-    const int ring = pw / ST_P_PER_RING, cg = pw % ST_P_PER_RING;
-#else
     const int ring = pw % ST_RINGS, cg = pw / ST_RINGS;
-#endif
     if (ring >= (int)da.rings) return;                         // (a workgroup of fewer rings, D4Args::rings: this wave's is not there)
-#ifdef IQD_D4_PRIO_YOUNG   // measurement build: the youngest P wave of every ring (hardware waves 12-14, the fourth wave of SIMDs 0-2) at a raised priority
-    if (pw >= 3 * (ST_P_PER_RING - 1)) __builtin_amdgcn_s_setprio(IQD_D4_PRIO_YOUNG);
-#endif
     const uint32_t wg_segs = 64u * da.rings;
     const int g = lane >> 4, c = lane & 15;
     const uint32_t row = (uint32_t)(16 * cg + c);
@@ -460,15 +328,11 @@ __device__ __forceinline__ void d4_p_wave(const ChainLaunch &a, const D4Args &da
         if ((round * chain_wgs(a) + chain_wg(a)) * wg_segs >= da.group_start[3]) break;   // nothing left for this workgroup
         const uint32_t sid0 = (round * chain_wgs(a) + chain_wg(a)) * wg_segs + ring * 64 + 16 * cg;
         const D4Seg sg = d4_segment(a, da, sid0 + (uint32_t)c);
-#if IQD_D4_TRANSPOSE
-        const D4Seg sgl = d4_segment(a, da, sid0 + (uint32_t)(lane >> 2));
-#else
-        const D4Seg &sgl = sg;
-#endif
+        const D4Seg sgl = d4_segment(a, da, sid0 + (uint32_t)(lane >> 2));   // the segment whose bytes this lane loads
         const int rot = __builtin_amdgcn_readfirstlane(sg.rot);
-        if (rot == 0) d4_p_round<MODE, MAG, 0, GATED>(a, da, sg, sgl, ring_base, full, consumed, sync, wr_off, g, lane, pg);
-        else if (rot > 0) d4_p_round<MODE, MAG, 1, GATED>(a, da, sg, sgl, ring_base, full, consumed, sync, wr_off, g, lane, pg);
-        else d4_p_round<MODE, MAG, -1, GATED>(a, da, sg, sgl, ring_base, full, consumed, sync, wr_off, g, lane, pg);
+        if (rot == 0) d4_p_round<MODE, MAG, 0, GATED>(a, da, sg, sgl, ring_base, full, consumed, wr_off, g, lane, pg);
+        else if (rot > 0) d4_p_round<MODE, MAG, 1, GATED>(a, da, sg, sgl, ring_base, full, consumed, wr_off, g, lane, pg);
+        else d4_p_round<MODE, MAG, -1, GATED>(a, da, sg, sgl, ring_base, full, consumed, wr_off, g, lane, pg);
     }
 }
 
@@ -494,28 +358,10 @@ __device__ __forceinline__ void d4_read_row(const uint8_t *slot, uint32_t row, u
     for (int g = 0; g < 4; g++) p[g] = *(const u32x2 *)(slot + d4_ring_off(row, (uint32_t)g));
 }
 
-#if IQD_D4_WAITSTAT || IQD_D4_TIMING
-__device__ __forceinline__ uint32_t *d4_stat_word(int i)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t d4_lds[];
-    return (uint32_t *)(d4_lds + ST_RINGS * D4_SLOTS * D4_SLOT_BYTES) + i;
-}
-#endif
 __device__ __forceinline__ void d4_wait_quad(const uint32_t *full, uint32_t pg)   // all four P waves have stored quad pg
 {
     const uint32_t target = 4u * ((pg / D4_QUADS) + 1u);
-#if IQD_D4_TIMING
-    const long long tw0 = clock64();
-#endif
-    while ((int32_t)(lds_load_relaxed(&full[pg & (D4_QUADS - 1)]) - target) < 0) {
-#if IQD_D4_WAITSTAT
-        if ((threadIdx.x & 63) == 0) atomicAdd(d4_stat_word(D4_SYNC_WORDS - 1), 1u);
-#endif
-        __builtin_amdgcn_s_sleep(IQD_D4_SLEEP_C);
-    }
-#if IQD_D4_TIMING   // cycles this consumer wave waited for its P waves, per hardware wave 0..2 (= ring)
-    if ((threadIdx.x & 63) == 0) atomicAdd(d4_stat_word(ST_RINGS * D4_QUADS + ST_RINGS + (int)(threadIdx.x >> 6)), (uint32_t)(clock64() - tw0));
-#endif
+    while ((int32_t)(lds_load_relaxed(&full[pg & (D4_QUADS - 1)]) - target) < 0) __builtin_amdgcn_s_sleep(IQD_D4_SLEEP_C);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 // piece V of quad pg: its slot; the consumer waits before a quad's first piece and hands the quad back after its last
@@ -541,16 +387,8 @@ __device__ __forceinline__ uint32_t d4_from_lane_below(uint32_t v)
     return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xf, 0xf, false);
 }
 
-// a consumer lane's 8-byte store of four outputs (IQD_D4_WT_STORES: measurement build, write-through - 64 narrow write-throughs per
-// instruction: USB 4096 x 2^16 +4 %, configs[4] +2.6 %, profiles/r6_wt_ab.txt; the closing launch's coalesced stores do go out that way)
-#ifdef IQD_D4_WT_STORES
-#define d4_store4(P, LO, HI) __hip_atomic_store((unsigned long long *)(P), (unsigned long long)(LO) | ((unsigned long long)(HI) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#elif defined(IQD_D4_NT_STORES)   // (non-temporal)
-typedef uint32_t d4_v2u __attribute__((ext_vector_type(2)));
-#define d4_store4(P, LO, HI) __builtin_nontemporal_store(d4_v2u{LO, HI}, (d4_v2u *)(P))
-#else
+// a consumer lane's 8-byte store of four outputs
 #define d4_store4(P, LO, HI) (*(u32x2 *)(P) = u32x2{LO, HI})
-#endif
 
 // AM / SSB -----------------------------------------------------------------------------------------------
 struct D4Rail {
@@ -586,15 +424,8 @@ __device__ __forceinline__ int d4_am_rail(const D4Args &da, D4Rail &r, const uin
     for (int k = 0; k < 4; k++) r.y1h[k] = n1[k];
     r.y2[V + 7] = pack_hi16((uint32_t)a0, (uint32_t)a1);
     int s3 = c14;                                      // /2, 16 taps: from y2[2i-14 .. 2i+1]
-#if IQD_D4_SPLIT
-    int s3b = 0;                                       // (two half-length chains: int32 sums wrap, so any order is exact)
-#pragma unroll
-    for (int q = 0; q < 4; q++) { s3 = dot2(r.y2[V + 7 - q], da.s3p[q], s3); s3b = dot2(r.y2[V + 3 - q], da.s3p[q + 4], s3b); }
-    s3 += s3b;
-#else
 #pragma unroll
     for (int q = 0; q < 8; q++) s3 = dot2(r.y2[V + 7 - q], da.s3p[q], s3);
-#endif
     return s3 >> 15;
 }
 
@@ -660,13 +491,6 @@ __device__ __forceinline__ int d4_am_piece(const D4Args &da, const uint8_t *ring
     d4_read_row(d4_take_piece<V>(ring_base, full, pg), row, p);
     d4_piece_taken<V>(consumed, pg);
     const uint32_t ni[4] = {p[0].x, p[1].x, p[2].x, p[3].x}, nq[4] = {p[0].y, p[1].y, p[2].y, p[3].y};
-#ifdef IQD_D4_BURN_CONSUMER   // measurement build: the consumer waves issue this many idle vector instructions per piece
-    {
-        float burn = 1.0f;
-#pragma unroll
-        for (int k = 0; k < IQD_D4_BURN_CONSUMER; k++) asm volatile("v_add_f32 %0, %0, %0" : "+v"(burn));
-    }
-#endif
     const int iv = d4_am_rail<V>(da, ri, ni, c14, c15), qv = d4_am_rail<V>(da, rq, nq, c14, c15);
     if (MODE == D4_SSB) rails = pack_lo16((uint32_t)iv, (uint32_t)qv);
     return d4_detect<MODE, V>(da, sb, iv, qv, lsb);
@@ -814,20 +638,8 @@ __device__ __forceinline__ int d4_fm_audio(D4Fm &s, uint32_t pair)
     s.y2p[V + 20] = pair;
     int acc = 1 << 14;                                 // /2, 40 taps -> PCM
     if (!__any(s.loud_y2 > 0)) {
-#if IQD_D4_SPLIT
-        int accb = 0, accc = 0, accd = 0;              // (four chains of 5: without the clamps int32 sums wrap, any order is exact)
-#pragma unroll
-        for (int q = 0; q < 5; q++) {
-            acc = dot2(s.y2p[V + 20 - q], D4_TAP(a40p, q), acc);
-            accb = dot2(s.y2p[V + 15 - q], D4_TAP(a40p, q + 5), accb);
-            accc = dot2(s.y2p[V + 10 - q], D4_TAP(a40p, q + 10), accc);
-            accd = dot2(s.y2p[V + 5 - q], D4_TAP(a40p, q + 15), accd);
-        }
-        acc = (acc + accb) + (accc + accd);
-#else
 #pragma unroll
         for (int q = 0; q < 20; q++) acc = dot2(s.y2p[V + 20 - q], D4_TAP(a40p, q), acc);
-#endif
     } else {
 #pragma unroll
         for (int q = 0; q < 20; q++) {
@@ -937,78 +749,30 @@ __device__ __forceinline__ void d4_fm_wave(const ChainLaunch &a, const D4Args &d
     }
 }
 
-#ifndef IQD_D4_AM_TWO_WGS
-#define IQD_D4_AM_TWO_WGS 0
-#endif
-#define D4_WAVES_PER_SIMD(MODE) ((MODE) == D4_AM && IQD_D4_AM_TWO_WGS ? 8 : 4)
 // (a function of its own: the kernel below calls it, and so does the launch that runs several families side by side,
 // iqd_stream_mixed.hip)
 template <int MODE, bool MAG, bool GATED>
 __device__ __forceinline__ void d4_stream_body(const ChainLaunch &a, const D4Args &da, uint8_t *d4_lds)
 {
-    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)d4_lds != 0u) __builtin_trap();   // st_maglut_chunk_at()
+    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)d4_lds != 0u) __builtin_trap();   // (no static LDS: the rings start at LDS address 0)
     uint32_t *sync = (uint32_t *)(d4_lds + ST_RINGS * D4_SLOTS * D4_SLOT_BYTES);
     const int tid = (int)threadIdx.x;
     if (tid < D4_SYNC_WORDS) sync[tid] = 0;
-    if (MAG && IQD_D4_MAGLUT == 1) st_maglut_build(d4_lds + D4_MAGLUT_OFF, tid, D4_THREADS);
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-#if IQD_D4_TIMING == 2
-    const long long t_wave0 = clock64();
-    const long long t_real0 = wall_clock64();
-#endif
-#ifdef IQD_D4_CONSUMERS_ON_SIMD3   // measurement build: the consumer waves are hardware waves 3, 7, 11 (all on the SIMD that holds three waves)
-    const bool is_consumer = (wave & 3) == 3;
-    const int c_ring = wave >> 2, p_index = wave - (wave > 3) - (wave > 7) - (wave > 11);
-#else
     const bool is_consumer = wave < ST_RINGS;
     const int c_ring = wave, p_index = wave - ST_RINGS;
-#endif
     if (is_consumer) {
-        if (IQD_D4_PRIO) __builtin_amdgcn_s_setprio(IQD_D4_PRIO);
-#if IQD_D4_TIMING == 1
-        const long long t_c0 = clock64();
-#endif
         if (MODE == D4_FM) d4_fm_wave(a, da, d4_lds, sync, c_ring, lane);
         else d4_am_wave<MODE>(a, da, d4_lds, sync, c_ring, lane);
-#if IQD_D4_TIMING == 1
-        if ((blockIdx.x & 63) == 7 && lane == 0)
-            printf("wg %u consumer wave %d: %lld cycles for %d pieces, of which waiting for a full quad %u\n", blockIdx.x, wave, clock64() - t_c0,
-                   (da.halo + (int)a.tile_len) >> 5, sync[ST_RINGS * D4_QUADS + ST_RINGS + wave]);
-#endif
     } else {
         d4_p_wave<MODE, MAG, GATED>(a, da, d4_lds, sync, p_index, lane);
     }
-#if IQD_D4_TIMING == 2
-    {
-        uint32_t hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        const long long t_end = wall_clock64();
-        __shared__ long long t_rec[32];            // per wave: run time in 10 ns ticks, HW_ID (which SIMD it sat on)
-        if (lane == 0) {
-            t_rec[wave * 2] = t_end - t_real0;
-            t_rec[wave * 2 + 1] = hwid;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const long long *r = t_rec;
-            unsigned long long simds = 0;
-            for (int w = 0; w < 15; w++) simds |= (unsigned long long)((r[2 * w + 1] >> 4) & 3) << (4 * w);
-            printf("T wg %u simds %llx cu %lld se %lld t %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", blockIdx.x, simds,
-                   (r[1] >> 8) & 15, (r[1] >> 13) & 7, r[0], r[2], r[4], r[6], r[8], r[10], r[12], r[14], r[16], r[18], r[20], r[22], r[24], r[26], r[28]);
-        }
-    }
-#endif
-#if IQD_D4_WAITSTAT
-    __syncthreads();
-    if (tid == 0 && (blockIdx.x & 63) == 5)
-        printf("wg %u: P sleeps %u (12 waves), consumer sleeps %u (3 waves), pieces %d\n", blockIdx.x, sync[D4_SYNC_WORDS - 2], sync[D4_SYNC_WORDS - 1], (da.halo + (int)a.tile_len) >> 5);
-#endif
 }
 
 #ifndef IQD_STREAM_BODIES_ONLY
 template <int MODE, bool MAG, bool GATED>
-__global__ __launch_bounds__(D4_THREADS, D4_WAVES_PER_SIMD(MODE)) void d4_stream_kernel(const ChainLaunch a, const D4Args da)
+__global__ __launch_bounds__(D4_THREADS, 4) void d4_stream_kernel(const ChainLaunch a, const D4Args da)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t d4_lds[];
     d4_stream_body<MODE, MAG, GATED>(a, da, d4_lds);

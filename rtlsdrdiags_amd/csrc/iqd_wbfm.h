@@ -206,13 +206,8 @@ IQD_DEV void p1_front(const WbfmTile &t, const Consts &c, const P1Raw &r, uint32
 #pragma unroll
     for (int j = 0; j < 8; j++) rotate4(t, s[2 * j], s[2 * j + 1], xi[j], xq[j]);
     int ai[17], aq[17];
-#ifdef IQD_ABL_NOFIR   // diagnostic build: skip the FIR arithmetic, keep its inputs alive
-#pragma unroll
-    for (int k = 0; k < 17; k++) { ai[k] = (int)(xi[k & 7] + k); aq[k] = (int)(xq[k & 7] ^ k); }
-#else
     fir16_window(xi, c, ai);
     fir16_window(xq, c, aq);
-#endif
 #pragma unroll
     for (int k = 0; k < 17; k++)  // float index of lut[(uint8)(Q'+128)][(uint8)(I'+128)]: byte 2 of each sum
         off[k] = perm((uint32_t)aq[k], (uint32_t)ai[k], 0x0c0c0602u);
@@ -222,11 +217,7 @@ IQD_DEV void p1_gather(const WbfmTile &t, const uint32_t (&off)[17], float (&th)
 {
 #pragma unroll
     for (int k = 0; k < 17; k++) {
-#ifdef IQD_ABL_NOLUT   // diagnostic build: no table gather
-        th[k] = u2f(0x3f000000u | (off[k] & 0xffu));
-#else
         th[k] = t.lut[lut_index(off[k])];
-#endif
     }
 }
 
@@ -305,24 +296,12 @@ IQD_DEV void wbfm_phase1(const WbfmTile &t, const Consts &c, WbfmLds &lds, const
                          int cstart, int clen, int tid)
 {
     const int ngroups = clen >> 4;
-#ifdef IQD_ABL_NOMAG
-    const bool want_mag = false;
-#else
     const bool want_mag = MAG && cstart >= 0;
-#endif
-#ifdef IQD_P1_SINGLE
-    for (int g0 = tid; (g0 & ~63) < ngroups; g0 += WB_THREADS) {
-#else
     for (int g0 = tid; (g0 & ~63) < ngroups; g0 += 2 * WB_THREADS) {   // wave-uniform trip count
-#endif
         // lanes past the end redo the chunk's last group and drop the result (no divergence)
         const int ga = g0 < ngroups ? g0 : ngroups - 1;
         const bool va = g0 < ngroups;
-#ifdef IQD_P1_SINGLE   // experiment: one group per lane and pass (fewer VGPRs)
-        const bool wave_has_b = false;
-#else
         const bool wave_has_b = ((g0 & ~63) + WB_THREADS) < ngroups;
-#endif
         const int gb = g0 + WB_THREADS < ngroups ? g0 + WB_THREADS : ngroups - 1;
         const bool vb = g0 + WB_THREADS < ngroups;
         const P1Raw ra = p1_load<GATED>(t, t.v0 + cstart + 16 * ga);
@@ -420,16 +399,6 @@ IQD_DEV void iir_guess(const Consts &c, WbfmLds &lds, int nseg, int lane, const 
 
 // One de-emphasis step, exactly as IirFilter::filterData evaluates it (IirFilter.cc:161-176):
 // y = (b0 x[n] + b1 x[n-1]) - (a1 y[n-1]), every operation rounded to binary32.
-#ifndef IQD_RELAXED_TOL
-#define IQD_RELAXED_TOL 0   // 1: TIMING A/B ONLY ("is bit-exactness what caps the roofline?") - the recurrence with one
-#endif                      // fused multiply-add, K b0 folded into one factor: PCM within +-1 LSB of the reference instead of identical.  Never shipped.
-#if IQD_RELAXED_TOL
-#define IQD_IIR_STEP(U)                              \
-    {                                                \
-        y = __builtin_fmaf(-a1, y, (U) + up);        \
-        up = (U);                                    \
-    }
-#else
 #define IQD_IIR_STEP(U)            \
     {                              \
         const float tn_ = (U) + up; \
@@ -437,7 +406,6 @@ IQD_DEV void iir_guess(const Consts &c, WbfmLds &lds, int nseg, int lane, const 
         y = tn_ - r_;              \
         up = (U);                  \
     }
-#endif
 
 // lane j >= 1: run segment j-1 from the guessed state to get the state entering segment j.
 IQD_DEV void iir_warm(const Consts &c, WbfmLds &lds, int nseg, int lane, int first_skip = 0)
@@ -1023,13 +991,8 @@ IQD_DEV void p1s_front(Exec &ex, int tid, const WbfmTile &t, const Consts &c, co
     xq[2] = ex.template shr1<SLOT0 + 6>(tid, xq[6]);
     xq[3] = ex.template shr1<SLOT0 + 7>(tid, xq[7]);
     int ai[17], aq[17];
-#ifdef IQD_ABL_NOFIR   // diagnostic build: skip the FIR arithmetic, keep its inputs alive
-#pragma unroll
-    for (int k = 1; k < 17; k++) { ai[k] = (int)(xi[k & 7] + k); aq[k] = (int)(xq[k & 7] ^ k); }
-#else
     fir16_window<1>(xi, c, ai);
     fir16_window<1>(xq, c, aq);
-#endif
 #pragma unroll
     for (int k = 1; k < 17; k++) off[k] = perm((uint32_t)aq[k], (uint32_t)ai[k], 0x0c0c0602u);
 }
@@ -1038,11 +1001,7 @@ IQD_DEV void p1s_gather(const WbfmTile &t, const uint32_t (&off)[17], float (&th
 {
 #pragma unroll
     for (int k = 1; k < 17; k++) {
-#ifdef IQD_ABL_NOLUT   // diagnostic build: no table gather
-        th[k] = u2f(0x3f000000u | (off[k] & 0xffu));
-#else
         th[k] = t.lut[lut_index(off[k])];
-#endif
     }
 }
 
@@ -1121,11 +1080,7 @@ IQD_DEV void wbfm_tile_pipe(Exec &ex, const WbfmTile &t, const Consts &c, WbfmLd
     typename Exec::template Local<P1Own> raw0;   // wave 0's prefetched group
     auto chunk_len = [&](int cs) { return wbfm_chunk_len(t, cs, WBFM_CHUNK, exact_from); };
     const bool tiny_ok = t.k_min >= 1.0f;
-#ifdef IQD_ABL_NOMAG
-    const bool mag_on = false;
-#else
     const bool mag_on = MAG;
-#endif
 
     // iteration -1 only produces chunk 0; iteration k runs the IIR of chunk k, phase 1 of chunk k+1 and the
     // last two decimation stages of chunk k-1; one more iteration drains the last chunk's decimation

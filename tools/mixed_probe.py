@@ -1,5 +1,5 @@
-"""Diagnostic: how long each family's workgroups of the fused mixed launch run (build iqd_stream_mixed.hip with
--DIQD_MIXED_TIMING=1: tools/variant.sh mxt iqd_stream_mixed.hip -DIQD_MIXED_TIMING=1).
+"""Diagnostic: how long each family's workgroups of the fused mixed launch run (build with
+-DIQD_MIXED_TIMING=1: tools/variant.sh mxt -DIQD_MIXED_TIMING=1).
     IQD_LIB=tmp_variants/lib_mxt.so [IQD_FAMILY_WEIGHTS=am,fm,wbfm,ssb] python3 tools/mixed_probe.py [channels] [log2 samples]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,6 @@
 """Which SIMD each wave of a WBFM streaming workgroup sits on (a build with -DIQD_ST_TIMING=1, see iqd_stream.hip):
-IQD_LIB=<variant> python3 tools/simd_of_waves.py"""
+    tools/variant.sh timing -DIQD_ST_TIMING=1
+    IQD_LIB=tmp_variants/lib_timing.so python3 tools/simd_of_waves.py"""
 import os
 import sys
 

@@ -1,5 +1,6 @@
 """Diagnostic: per-phase cycle shares of the WBFM chain kernel.  Needs a library built with -DIQD_STAMPS:
-   IQD_LIB=.../libiqdemod_stamps.so python tools/stamps_probe.py"""
+    tools/variant.sh stamps -DIQD_STAMPS
+    IQD_LIB=tmp_variants/lib_stamps.so python tools/stamps_probe.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

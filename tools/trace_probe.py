@@ -1,5 +1,6 @@
-"""Diagnostic: event times of one workgroup's waves, piece by piece (build with -DIQD_ST_TRACE=1).
-IQD_LIB=<variant> python3 tools/trace_probe.py"""
+"""Diagnostic: event times of one workgroup's waves, piece by piece (build with -DIQD_ST_TRACE=1):
+    tools/variant.sh trace -DIQD_ST_TRACE=1
+    IQD_LIB=tmp_variants/lib_trace.so python3 tools/trace_probe.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,5 +1,7 @@
 """Diagnostic: ring waits and per-wave phase cycles of the WBFM streaming kernel (builds with -DIQD_ST_WAITSTAT=1
--DIQD_ST_TIMING=1, see iqd_stream.hip).  IQD_LIB=<variant> python3 tools/waitstat_probe.py"""
+-DIQD_ST_TIMING=1, see iqd_stream.hip):
+    tools/variant.sh waitstat -DIQD_ST_WAITSTAT=1 -DIQD_ST_TIMING=1
+    IQD_LIB=tmp_variants/lib_waitstat.so python3 tools/waitstat_probe.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rtlsdrdiags_amd import capi, synth
