@@ -155,13 +155,22 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
         // CU cap the chip near 1.5 TB/s whatever the arithmetic costs).  The loads are the untracked ones of iqd_mfma.h:
         // the compiler's own wait placement would join the loop's back edge to vmcnt(0).  A buffer is re-asked right after
         // the last use of its old contents, in ST_AHEAD copies of the loop body with named buffers.
-        // Not GATED: the address of the next piece to ask for is a running pointer - 64 bytes on per piece, held at the
-        // last piece that lies wholly inside the channel's samples (what is computed from a repeated piece lies beyond the
-        // segment's end and is never stored or counted), and moved from the kept tail to the call's own samples when a
-        // first segment's lead-in ends (below, once per segment) - instead of piece_address()'s six operations per piece.
+        // Not GATED: the piece to ask for next advances by 64 bytes per piece and is held at the last piece that lies wholly
+        // inside the channel's samples (what is computed from a repeated piece lies beyond the segment's end and is never
+        // stored or counted), and moves from the kept tail to the call's own samples when a first segment's lead-in ends
+        // (below, once per segment) - instead of piece_address()'s six operations per piece.  Its address is
+        // `nxt` + min(2 (position - ST_NXT_ORIGIN), nxt_max): the position is the same in all lanes, a scalar, so a piece pays
+        // one v_min_u32 and the 64-bit add of the load's address.  `nxt` is piece_address() of the first request; a lane
+        // whose samples end before that one (pos_last < ST_NXT_ORIGIN) stays there: nxt_max = 0.
         const int32_t pos_last = pos_max & ~31;
         const bool from_tail = sg.v0 == 0;                       // (tile_len >= ST_MIN_TILE = ST_HALO: only a first segment's lead-in reads the tail inside the loop)
         const uint8_t *nxt = piece_address(-ST_HALO + 32 * ST_AHEAD);
+        constexpr int ST_NXT_ORIGIN = -ST_HALO + 32 * ST_AHEAD;
+        auto nxt_room = [&](int32_t from) -> uint32_t {   // bytes from position `from` to the last whole piece, 0 if it lies before
+            const int64_t room = 2 * ((int64_t)pos_last - from);
+            return room < 0 ? 0u : room > 0x7fffff00 ? 0x7fffff00u : (uint32_t)room;
+        };
+        uint32_t nxt_max = nxt_room(ST_NXT_ORIGIN);
         uint4 prev = st_front<ROT>(*(const uint4 *)piece_address(-ST_HALO - 32), zero);
         v4u raw[ST_AHEAD];
 #pragma unroll
@@ -242,55 +251,60 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
             if (GATED) {
                 raw[j] = gload16_untracked(piece_address(pos + 32 * ST_AHEAD));
             } else {
-                raw[j] = gload16_untracked(nxt);
-                nxt += pos + 32 * ST_AHEAD < pos_last ? 64 : 0;
+                const uint32_t at = (uint32_t)(2 * (pos + 32 * ST_AHEAD - ST_NXT_ORIGIN));   // (uniform)
+                raw[j] = gload16_untracked(nxt + (at < nxt_max ? at : nxt_max));
             }
-            // phase C, both windows: sign, delta theta, branch cut, K, b0
-            float u[2][4];
+            // phase C, both windows: sign, delta theta, branch cut, K, b0.  A window's angles are kept as the ALIGNED register
+            // pairs X = (theta0, theta2), Y = (before, theta1), Z = (theta1, theta3): (d0, d2) = X - Y and (d1, d3) = Z - X are
+            // then two packed subtractions of pairs as they stand.  Pairs of neighbours - (before, theta0) with (theta0, theta1) -
+            // put theta0 and theta2 into two pairs at different halves: four register moves per piece.  Here only theta1 sits
+            // in two pairs, and its v_bfi_b32 is simply issued twice.  The ring chunk holds (u0, u2, u1, u3): st_iir_piece, st_iir_lead_in.
+            v2f u[2][2];
 #pragma unroll
             for (int half = 0; half < 2; half++) {
                 const int wpos = pos + 16 * half;
-                float th[4];
+                uint32_t th[4], th1_z;          // the table holds |theta|; theta' = -theta carries the sign bit of y >= 0 (index bit 7)
 #pragma unroll
-                for (int r = 0; r < 4; r++) {   // the table holds |theta|; theta' = -theta carries the sign bit of y >= 0 (index bit 7)
-                    uint32_t bits;
-                    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bits) : "s"(0x7fffffffu), "v"(traw[half][r]), "v"(tqs[half][r] << 8));
-                    th[r] = u2f(bits);
-                }
-                const float give = g == 3 ? last_prev : th[3];
+                for (int r = 0; r < 4; r++)
+                    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(th[r]) : "s"(0x7fffffffu), "v"(traw[half][r]), "v"(tqs[half][r] << 8));
+                // (another text: two identical statements are one to the compiler, and the copy comes back)
+                asm("v_bfi_b32 %0, %1, %2, %3 ; theta1 of the pair Z" : "=v"(th1_z) : "s"(0x7fffffffu), "v"(traw[half][1]), "v"(tqs[half][1] << 8));
+                const float give = g == 3 ? last_prev : u2f(th[3]);
                 const float before = u2f((uint32_t)__builtin_amdgcn_ds_bpermute(src_lane4, (int)f2u(give)));
-                last_prev = th[3];
+                last_prev = u2f(th[3]);
                 float kk = kneg;
                 if (EPOCHS && ep_any && ep_reach) kk = -epoch_gain_search(ep, p.wbfm_k, sg.v0 + wpos);   // (rare: right after a gain change)
+                const v2f X = {u2f(th[0]), u2f(th[2])}, Y = {before, u2f(th[1])}, Z = {u2f(th1_z), u2f(th[3])};
 #pragma unroll
-                for (int r = 0; r < 4; r += 2) {   // two samples per packed operation; wrap_delta() of iqd_prims.h operation by operation
-                    v2f d = {th[r] - (r == 0 ? before : th[r - 1]), th[r + 1] - th[r]};   // = -(delta theta)
+                for (int e = 0; e < 2; e++) {   // two samples per packed operation; wrap_delta() of iqd_prims.h operation by operation
+                    v2f d = e == 0 ? X - Y : Z - X;   // = -(delta theta) of samples (0, 2), then (1, 3)
                     v2f m = pk_mul_s(d, inv_2pi);
                     m.x = __builtin_rintf(m.x);
                     m.y = __builtin_rintf(m.y);
                     d = __builtin_elementwise_fma(-m, v2f{6.28318548202514648f, 6.28318548202514648f}, d);
                     d = __builtin_elementwise_fma(-m, v2f{-1.74845553146951715e-7f, -1.74845553146951715e-7f}, d);
                     const v2f v = d * v2f{kk, kk};
-                    const v2f w = v2f{sa.b0, sa.b0} * v;
-                    u[half][r] = w.x;
-                    u[half][r + 1] = w.y;
+                    u[half][e] = v2f{sa.b0, sa.b0} * v;
                 }
             }
             // hand the 2 x 4 samples to the IIR wave: the ring's two slots hold one piece (window 0, window 1), free once
             // the IIR wave has read the previous piece.  One signal per piece in each direction.
             ST_T(t2);
             ST_TRACE(a.stamps, pw + 3, q, 1);
+            // (the counter is one LDS word, the same in every lane: one v_readfirstlane_b32 and the test runs on the scalar unit)
+            seen = (uint32_t)__builtin_amdgcn_readfirstlane((int)seen);
             while ((int32_t)(seen + (uint32_t)(ST_DEPTH - 1) - pc) < 0) {   // piece pc - ST_DEPTH has been read: its slots are free
                 __builtin_amdgcn_s_sleep(IQD_ST_SLEEP_P);
                 seen = lds_load_relaxed(consumed);
+                seen = (uint32_t)__builtin_amdgcn_readfirstlane((int)seen);
                 if (IQD_ST_WAITSTAT) n_sleeps++;
             }
             ST_T(t3);
             ST_TRACE(a.stamps, pw + 3, q, 2);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             uint8_t *const slot = ring_base + (ST_DEPTH > 1 ? (pc & (uint32_t)(ST_DEPTH - 1)) * (2 * ST_SLOT_BYTES) : 0u) + wr_off;
-            *(u32x4 *)slot = u32x4{f2u(u[0][0]), f2u(u[0][1]), f2u(u[0][2]), f2u(u[0][3])};
-            *(u32x4 *)(slot + ST_SLOT_BYTES) = u32x4{f2u(u[1][0]), f2u(u[1][1]), f2u(u[1][2]), f2u(u[1][3])};
+            *(u32x4 *)slot = u32x4{f2u(u[0][0].x), f2u(u[0][0].y), f2u(u[0][1].x), f2u(u[0][1].y)};
+            *(u32x4 *)(slot + ST_SLOT_BYTES) = u32x4{f2u(u[1][0].x), f2u(u[1][0].y), f2u(u[1][1].x), f2u(u[1][1].y)};
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             lds_signal(ST_DEPTH > 1 ? full + (pc & (uint32_t)(ST_DEPTH - 1)) : full);
             ST_TRACE(a.stamps, pw + 3, q, 3);
@@ -300,26 +314,36 @@ __device__ __forceinline__ void st_p_wave(const ChainLaunch &a, const StreamArgs
 #endif
         };
         uint4 other;
-        for (int q = 0; q < n_pieces; q += ST_AHEAD) {   // (n_pieces is a multiple of 4)
+        // The groups in two runs of one loop: the lead-in's up to the last request for a sample before position 0, then the
+        // rest.  Between them - a scalar branch, once per segment - a first segment's requests move from the kept tail to the
+        // call's own samples.
+        const int q_samples = !GATED ? ST_HALO / 32 - ST_AHEAD : n_pieces;   // (n_pieces >= ST_HALO / 16)
+        int q = 0;
+#pragma unroll 1
+        for (int q_end = q_samples; q < n_pieces; q_end = n_pieces) {
+            for (; q < q_end; q += ST_AHEAD) {   // (n_pieces is a multiple of 4)
 #pragma unroll
-            for (int j = 0; j < ST_AHEAD; j += 2) {
-                do_piece(q + j, j, prev, other);
-                do_piece(q + j + 1, j + 1, other, prev);
-            }
-            const int gpos = -ST_HALO + 32 * q;                  // the group's first sample
-            if (!GATED && gpos + 64 * ST_AHEAD == 0)   // (recomputed here, once per segment: two registers fewer through the loop)
-                nxt = from_tail ? a.iq + (size_t)sg.ch * a.ch_stride_bytes + 16 * g : nxt;   // the next piece asked for is the one at position 0
-            if (MAG && gpos >= 0) {
-                const uint32_t m = (gm16 & 0xffffu) + (gm16 >> 16);
-                gm16 = 0;
-                macc += gpos < mlim ? m : 0u;
-                minblk += 32 * ST_AHEAD;
-                if (minblk >= a.block_samples) {                 // the next group belongs to the next block
-                    if (macc) atomicAdd(mag_at, macc);
-                    macc = 0;
-                    mag_at++;
-                    minblk -= a.block_samples;
+                for (int j = 0; j < ST_AHEAD; j += 2) {
+                    do_piece(q + j, j, prev, other);
+                    do_piece(q + j + 1, j + 1, other, prev);
                 }
+                const int gpos = -ST_HALO + 32 * q;                  // the group's first sample
+                if (MAG && gpos >= 0) {
+                    const uint32_t m = (gm16 & 0xffffu) + (gm16 >> 16);
+                    gm16 = 0;
+                    macc += gpos < mlim ? m : 0u;
+                    minblk += 32 * ST_AHEAD;
+                    if (minblk >= a.block_samples) {                 // the next group belongs to the next block
+                        if (macc) atomicAdd(mag_at, macc);
+                        macc = 0;
+                        mag_at++;
+                        minblk -= a.block_samples;
+                    }
+                }
+            }
+            if (!GATED && q == q_samples && from_tail) {   // the next piece asked for is the one at position 0
+                nxt = (const uint8_t *)((uintptr_t)(a.iq + (size_t)sg.ch * a.ch_stride_bytes + 16 * g) + (intptr_t)(2 * ST_NXT_ORIGIN));
+                nxt_max = nxt_room(0) + (uint32_t)(-2 * ST_NXT_ORIGIN);
             }
         }
 #pragma unroll
@@ -491,7 +515,7 @@ __device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamA
 #pragma unroll
         for (int gq = 0; gq < 4; gq++) {
             const u32x4 v = *(const u32x4 *)(slot + (((uint32_t)gq ^ rd_swz) << 4));
-            u[4 * gq] = u2f(v.x); u[4 * gq + 1] = u2f(v.y); u[4 * gq + 2] = u2f(v.z); u[4 * gq + 3] = u2f(v.w);
+            u[4 * gq] = u2f(v.x); u[4 * gq + 2] = u2f(v.y); u[4 * gq + 1] = u2f(v.z); u[4 * gq + 3] = u2f(v.w);   // a chunk holds (u0, u2, u1, u3): st_p_wave, phase C
         }
         if (half == 1) {   // both windows read: the ring is free for the next piece
             y2_seen = lds_load_relaxed(y2r.consumed);                // asked early (it returns with the reads above), needed only before the hand-over
@@ -551,7 +575,7 @@ __device__ __forceinline__ void st_iir_lead_in(const StreamArgs &sa, uint8_t *ri
         wg++;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            IQD_IIR_STEP(u2f(v[k].x)) IQD_IIR_STEP(u2f(v[k].y)) IQD_IIR_STEP(u2f(v[k].z)) IQD_IIR_STEP(u2f(v[k].w))
+            IQD_IIR_STEP(u2f(v[k].x)) IQD_IIR_STEP(u2f(v[k].z)) IQD_IIR_STEP(u2f(v[k].y)) IQD_IIR_STEP(u2f(v[k].w))   // a chunk holds (u0, u2, u1, u3)
         }
     }
     s.y = y;
