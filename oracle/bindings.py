@@ -145,6 +145,7 @@ class Oracle:
         _sig(L.iqo_get_taps_q15, C.c_int, [C.c_int, vp])
         _sig(L.iqo_get_taps_f32, C.c_int, [C.c_int, vp])
         _sig(L.iqo_wbfm_stages, None, [vp, sz, C.c_float, vp, vp, vp, vp, vp, vp])
+        _sig(L.iqo_dc_stages, None, [vp, sz, C.c_int, vp, vp])
 
     def chain(self):
         L = self.lib
@@ -265,6 +266,15 @@ class Oracle:
         self.lib.iqo_wbfm_stages(_ptr(rot_s8), n, C.c_float(gain), _ptr(out["ip"]),
                                  _ptr(out["qp"]), _ptr(out["theta"]), _ptr(out["dtheta"]),
                                  _ptr(out["deemph"]), _ptr(out["w"]))
+        return out
+
+    def dc_stages(self, rot_s8, mode):
+        """AM / SSB: the detector stream entering the DC-removal recurrence and the recurrence's output before the gain"""
+        rot_s8 = np.ascontiguousarray(rot_s8, dtype=np.int8)
+        n = len(rot_s8) // 2
+        assert n % 32 == 0
+        out = dict(det=np.zeros(n // 32, np.float32), dc=np.zeros(n // 32, np.float32))
+        self.lib.iqo_dc_stages(_ptr(rot_s8), n, int(MODES.get(mode, mode)), _ptr(out["det"]), _ptr(out["dc"]))
         return out
 
 

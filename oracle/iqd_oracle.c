@@ -562,7 +562,7 @@ static size_t front32_run(iqo_chain *c, q15_filter *s1i, q15_filter *s1q, q15_fi
 }
 
 /* AmDemodulator.cc:434-471 */
-static size_t am_run(iqo_chain *c, am_t *a, const int8_t *iq, size_t n, int16_t *pcm)
+static size_t am_run(iqo_chain *c, am_t *a, const int8_t *iq, size_t n, int16_t *pcm, float *t_det, float *t_dc)
 {
     size_t i, m;
     m = front32_run(c, &a->s1i, &a->s1q, &a->s2i, &a->s2q, &a->s3i, &a->s3q, iq, n,
@@ -572,6 +572,8 @@ static size_t am_run(iqo_chain *c, am_t *a, const int8_t *iq, size_t n, int16_t 
         int16_t qm = (int16_t)abs((int)c->d16[i]);
         int16_t in = (im > qm) ? (int16_t)(im + (qm >> 1)) : (int16_t)(qm + (im >> 1));
         float y = f32_iir_step(&a->dc, (float)in);
+        if (t_det) t_det[i] = (float)in;
+        if (t_dc) t_dc[i] = y;
         pcm[i] = iqo_cast_i16(a->gain * y);
     }
     return m;
@@ -596,7 +598,7 @@ static void ssb_reset(ssb_t *s)
 }
 
 /* SsbDemodulator.cc:563-598 */
-static size_t ssb_run(iqo_chain *c, ssb_t *s, const int8_t *iq, size_t n, int16_t *pcm)
+static size_t ssb_run(iqo_chain *c, ssb_t *s, const int8_t *iq, size_t n, int16_t *pcm, float *t_det, float *t_dc)
 {
     size_t i, m;
     m = front32_run(c, &s->s1i, &s->s1q, &s->s2i, &s->s2q, &s->s3i, &s->s3q, iq, n,
@@ -606,6 +608,8 @@ static size_t ssb_run(iqo_chain *c, ssb_t *s, const int8_t *iq, size_t n, int16_
     for (i = 0; i < m; i++) {
         float o = s->lsb ? (float)(c->a16[i] - c->b16[i]) : (float)(c->a16[i] + c->b16[i]);
         float y = f32_iir_step(&s->dc, o);
+        if (t_det) t_det[i] = o;
+        if (t_dc) t_dc[i] = y;
         pcm[i] = iqo_cast_i16(s->gain * y);
     }
     return m;
@@ -936,10 +940,10 @@ void iqo_set_rotation(iqo_chain *c, int r) { c->rotation = r; }
 static size_t run_demod(iqo_chain *c, int mode, const int8_t *s8, size_t n, int16_t *pcm)
 {
     switch (mode) {
-    case IQO_AM: return am_run(c, &c->am, s8, n, pcm);
+    case IQO_AM: return am_run(c, &c->am, s8, n, pcm, 0, 0);
     case IQO_FM: return fm_run(c, &c->fm, s8, n, pcm);
     case IQO_WBFM: return wbfm_run(c, &c->wbfm, s8, n, pcm, 0, 0, 0, 0, 0, 0);
-    case IQO_LSB: case IQO_USB: return ssb_run(c, &c->ssb, s8, n, pcm);
+    case IQO_LSB: case IQO_USB: return ssb_run(c, &c->ssb, s8, n, pcm, 0, 0);
     default: return 0;
     }
 }
@@ -1064,6 +1068,22 @@ void iqo_wbfm_stages(const int8_t *rot, size_t n, float gain, int8_t *ip, int8_t
         size_t m = (n - off < MAX_BLOCK_SAMPLES) ? (n - off) : MAX_BLOCK_SAMPLES;
         wbfm_run(c, &c->wbfm, rot + 2 * off, m, pcm, ip + off, qp + off, theta + off,
                  dtheta + off, deemph + off, w + off);
+    }
+    iqo_destroy(c);
+}
+
+/* The AM / SSB chain on signed, rotated samples from the zero state: the detector stream that enters the DC-removal
+ * recurrence (integers, as floats) and the recurrence's output before the gain and the cast, one per 32 samples. */
+void iqo_dc_stages(const int8_t *rot, size_t n, int mode, float *det, float *dc)
+{
+    iqo_chain *c = iqo_create();
+    int16_t pcm[MAX_BLOCK_SAMPLES / 32 + 8];
+    size_t off;
+    iqo_set_mode(c, mode);
+    for (off = 0; off < n; off += MAX_BLOCK_SAMPLES) {
+        size_t m = (n - off < MAX_BLOCK_SAMPLES) ? (n - off) : MAX_BLOCK_SAMPLES;
+        if (mode == IQO_AM) am_run(c, &c->am, rot + 2 * off, m, pcm, det + off / 32, dc + off / 32);
+        else ssb_run(c, &c->ssb, rot + 2 * off, m, pcm, det + off / 32, dc + off / 32);
     }
     iqo_destroy(c);
 }

@@ -125,6 +125,9 @@ int iqo_get_taps_f32(int which, float *h);
 void iqo_wbfm_stages(const int8_t *rot, size_t n_samples, float gain,
                      int8_t *ip, int8_t *qp, float *theta, float *dtheta,
                      float *deemph, int16_t *w);
+/* The same for the AM (mode IQO_AM) / SSB (IQO_LSB, IQO_USB) chains: the detector stream entering the DC-removal
+ * recurrence and the recurrence's output (before the gain), n_samples / 32 values each; n_samples a multiple of 32. */
+void iqo_dc_stages(const int8_t *rot, size_t n_samples, int mode, float *det, float *dc);
 
 #ifdef __cplusplus
 }

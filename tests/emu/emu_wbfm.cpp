@@ -29,8 +29,10 @@ struct HostExec {
     {
         bool ok = true;
         for (int l = 0; l < 64; l++) ok = f(l) && ok;
+        if (!ok) failed_checks++;
         return ok;
     }
+    int failed_checks = 0;   // wave-wide checks that sent their loop round again
     void sync() const {}
     template <class F> void others(F f) { for (int t = 64; t < iqd::WB_THREADS; t++) f(t); }
     template <class F> void all_nosync(F f) { for (int t = 0; t < iqd::WB_THREADS; t++) f(t); }
@@ -309,7 +311,8 @@ void emu_plan_call(const uint32_t *knobs, uint32_t vlen, uint32_t pcm_per_ch, ui
 
 // ---- the AM / SSB DC-removal pass of one channel row, one wave, IN PLACE over int16 detector values (round 6: what runs behind the
 // streaming pipelines, iqd_kernels.hip: dc_channel_wave) or from an int32 stream into a PCM row.  tests/test_emu_chains.py
-void emu_dc_row(int in_place, const int32_t *x32, int16_t *row, int n, float gain, iqd::DcCarry *st)
+// Returns how often a pass's segments did not chain up and were run again (dc_block_wave's `again` loop).
+int emu_dc_row(int in_place, const int32_t *x32, int16_t *row, int n, float gain, iqd::DcCarry *st)
 {
     using namespace iqd;
     static Consts c;
@@ -319,6 +322,7 @@ void emu_dc_row(int in_place, const int32_t *x32, int16_t *row, int n, float gai
     HostExec ex;
     if (in_place) dc_block_wave(ex, c, lds, (const int16_t *)row, n, gain, *st, row);
     else dc_block_wave(ex, c, lds, x32, n, gain, *st, row);
+    return ex.failed_checks;
 }
 void emu_dc_serial(const int32_t *x32, int16_t *row, int n, float gain, iqd::DcCarry *st)
 {
@@ -410,6 +414,13 @@ void emu_stream_taps(uint32_t *literal30, uint32_t *host30)
     for (int q = 0; q < 20; q++) host30[10 + q] = sa.a40p[q];
 }
 
+float emu_dc_a1()
+{
+    iqd::Consts c;
+    iqd::build_consts(c);
+    return c.dc_a1;
+}
+
 uint32_t emu_plan_const(int which)   // geometry constants the plan tests need
 {
     switch (which) {
@@ -417,6 +428,9 @@ uint32_t emu_plan_const(int which)   // geometry constants the plan tests need
     case 1: return iqd::ST_MIN_TILE;
     case 2: return iqd::ST_HALO;
     case 3: return iqd::DC_TILE;
+    case 4: return iqd::COLD_HALO;
+    case 5: return iqd::DC_WARM;
+    case 6: return iqd::FORCED_BACK;
     default: return 0;
     }
 }

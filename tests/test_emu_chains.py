@@ -163,3 +163,45 @@ def test_dc_pass_in_place_over_int16_rows_is_the_serial_recurrence():
         assert np.array_equal(got32, want), (trial, n, gain)
         for s in (s_a, s_b):
             assert s.x_prev == s_ref.x_prev and (s.y_prev == s_ref.y_prev or abs(s.y_prev) < 1e-30 and abs(s_ref.y_prev) < 1e-30), (trial, s.y_prev, s_ref.y_prev)
+
+
+def test_dc_pass_runs_its_segments_again_where_the_tiny_state_rule_does_not_hold(oracle):
+    """The `again` loop of dc_block_wave, stepped on the host over the row of tests/repair_cases.py's `dc_again_loop` (which
+    tests/test_gpu_repairs.py runs on the device, where no counter shows the loop): a modulated stretch, then a noiseless carrier -
+    the detector output is constant, the true state sticks at a denormal, a lane's warmed-up start state sits at exactly 0.  At a
+    gain of 1e6 the two count as agreeing; one ulp above, bit equality is the rule, so the wave's segments are run again - and the
+    PCM is the oracle's either way (in place over the int16 detector values, as behind the streaming pipelines)."""
+    import ctypes as C
+    from tests import handoff_model as H, repair_cases as R
+    L = emu_bind.lib()
+
+    class Dc(C.Structure):
+        _fields_ = [("x_prev", C.c_float), ("y_prev", C.c_float)]
+    L.emu_dc_row.restype = C.c_int
+    L.emu_dc_row.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+    u8 = R.CASES["dc_again_loop"].build(None)[0][0]
+    det = oracle.dc_stages(H.rotated(oracle, u8, 1), "am")["det"]
+    assert np.all(det[800:] == det[800]) and np.ptp(det[:700]) > 10          # constant behind the stretch, live inside it
+    rounds = {}
+    for gain in (R.DC_GAIN_AGREES, R.DC_GAIN_ABOVE):
+        o = oracle.chain()
+        o.set_mode("am")
+        o.set_gain(1, float(gain))
+        ref, _, _ = o.accept_stream(u8)
+        row, st = det.astype(np.int16), Dc(0.0, 0.0)
+        rounds[float(gain)] = L.emu_dc_row(1, None, row.ctypes.data, len(row), float(gain), C.byref(st))
+        assert np.array_equal(row, ref), gain
+    # (the live stretch sends segments round again at either gain; the constant part only above 1e6)
+    assert rounds[float(R.DC_GAIN_ABOVE)] > rounds[float(R.DC_GAIN_AGREES)] and rounds[float(R.DC_GAIN_ABOVE)] > 1, rounds
+    # the second pass of the wave lies wholly in the constant part: entered with the state stuck at a denormal, nothing goes round
+    # again at 1e6, every segment but the first does one ulp above - and the PCM is the serial recurrence's either way
+    L.emu_dc_serial.restype = None
+    L.emu_dc_serial.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+    quiet = np.ascontiguousarray(det[2048:], np.int32)
+    for gain, again in ((R.DC_GAIN_AGREES, False), (R.DC_GAIN_ABOVE, True)):
+        row, want = quiet.astype(np.int16), np.zeros(len(quiet), np.int16)
+        st, st_ref = Dc(float(det[2047]), 1e-44), Dc(float(det[2047]), 1e-44)
+        n_again = L.emu_dc_row(1, None, row.ctypes.data, len(row), float(gain), C.byref(st))
+        L.emu_dc_serial(quiet.ctypes.data, want.ctypes.data, len(quiet), float(gain), C.byref(st_ref))
+        assert (n_again > 1) == again and (again or n_again == 0), (gain, n_again)
+        assert np.array_equal(row, want), gain

@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 from rtlsdrdiags_amd import synth
-from tests import emu_bind
+from tests import emu_bind, handoff_model
 
 f32 = np.float32
 
@@ -58,18 +58,9 @@ class Model:
 
     def iir_run(self, y, up, g0, n):
         """n steps of IQD_IIR_STEP from global sample g0 (u = 0 before the stream's start)."""
-        a1 = self.a1
-        for g in range(g0, g0 + n):
-            x = self.u[g] if g >= 0 else f32(0)
-            tn = f32(x + up)
-            r = f32(a1 * y)
-            y = f32(tn - r)
-            up = x
-        return y, up
+        return handoff_model.iir_run(self.u, self.a1, y, up, g0, n)
 
-    @staticmethod
-    def agree(a, b):
-        return a.tobytes() == b.tobytes() or (abs(float(a)) < 2.0 ** -100 and abs(float(b)) < 2.0 ** -100)
+    agree = staticmethod(handoff_model.agree)
 
     def stream_call(self, pos0, vlen, carry):
         """One streamed call of `vlen` samples starting at global sample pos0; carry = (y, u, back).  Returns the new carry, or

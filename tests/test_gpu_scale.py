@@ -84,7 +84,12 @@ def test_config5_ssb_rotation_squelch(capi, oracle):
 def test_wbfm_handoff_repair_on_periodic_input(capi, oracle):
     """Strictly periodic input can keep two de-emphasis trajectories one ulp apart for ever, so the
     zero-state lead-in of a tile never lands on the exact state: the verification must notice and the
-    repair path must restore bit-exactness."""
+    repair path must restore bit-exactness.  One channel of 2^19 samples is the tile kernel's by the planner's choice (75 tiles,
+    every hand-off bad); tests/test_gpu_repairs.py reaches the repair paths of every launch form at small shapes, with the bad
+    hand-offs predicted on the CPU."""
+    from test_host_planning import plan_call
+    q = plan_call(1 << 19, {"wbfm": ((1, 0, 0), True, False)})["fam"]["wbfm"]
+    assert q["path"] == 0 and q["tiles_per_ch"] >= 3, q                                      # PLAN_TILES
     pattern = np.tile(np.array([255, 255, 255, 255, 0, 0, 0, 0], dtype=np.uint8), 1 << 17)   # 2^19 samples
     o = oracle.chain()
     o.set_mode("wbfm")
@@ -95,6 +100,7 @@ def test_wbfm_handoff_repair_on_periodic_input(capi, oracle):
     assert np.array_equal(pcm[0, :cnt[0]], ref)
     st = eng.stats()
     assert st["state_repairs"] >= 1 and st["state_checks"] >= 1      # repaired on the device, then chained up
+    assert st["stream_launches"] == 0 and st["mixed_launches"] == 0  # ... behind the tile kernel (wbfm_verify_kernel, verify_at_end 0)
 
 
 def _carrier(n, amp=60):
