@@ -155,6 +155,20 @@ __device__ __forceinline__ void lds_signal(const uint32_t *p, uint32_t n = 1u)
     asm volatile("s_mov_b64 exec, 1\n\tds_add_u32 %0, %1\n\ts_mov_b64 exec, -1" :: "v"(addr), "v"(n) : "memory");
 }
 
+// The same two for a wave that keeps the LDS byte address of its ring's sync words in a vector register (st_iir_wave): the word
+// OFF bytes behind it, the constant in the instruction's offset field - through a uniform pointer the address is a scalar that
+// has to be moved into a vector register in front of every look.  lds_word_uniform: the word is the same in every lane, so the
+// value goes to the scalar unit (one v_readfirstlane_b32) and whatever is tested on it is scalar arithmetic and a scalar branch.
+__device__ __forceinline__ uint32_t lds_word_uniform(uint32_t base, uint32_t off)
+{
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_load_relaxed((const uint32_t *)(uintptr_t)(base + off)));
+}
+template <int OFF>
+__device__ __forceinline__ void lds_signal_at(uint32_t base, uint32_t n = 1u)
+{
+    asm volatile("s_mov_b64 exec, 1\n\tds_add_u32 %0, %1 offset:%2\n\ts_mov_b64 exec, -1" :: "v"(base), "v"(n), "n"(OFF) : "memory");
+}
+
 // byte offset of granule q (4 samples) of ring row j inside a slot: XOR swizzle, conflict-free for the
 // P waves' ds_write_b128 and the IIR lanes' ds_read_b128
 __device__ __forceinline__ uint32_t st_slot_off(uint32_t j, uint32_t q) { return j * 64u + ((q ^ ((j >> 2) & 3u)) << 4); }

@@ -20,6 +20,14 @@ namespace iqd {
 // relocated zero - to every one of the eight addresses of a piece.
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
 __device__ __forceinline__ uint32_t st_table_read(uint32_t byte_offset) { return *(lds_cu32 *)(uintptr_t)byte_offset; }
+// One 16-byte chunk of a ring slot, by its LDS address (the IIR lanes: st_iir_wave keeps the addresses).
+typedef uint32_t st_u32v4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) const st_u32v4 lds_cu32v4;
+__device__ __forceinline__ u32x4 st_ring_read(uint32_t lds_address)
+{
+    const st_u32v4 v = *(lds_cu32v4 *)(uintptr_t)lds_address;   // (as one vector: one ds_read_b128)
+    return u32x4{v.x, v.y, v.z, v.w};
+}
 
 #ifndef IQD_ST_WAITSTAT   // diagnostic build: how often each side of a ring sleeps on the other (per-wave counts, added once
 #define IQD_ST_WAITSTAT 0 // per wave to ChainLaunch::stamps[0..3] = P sleeps, IIR sleeps, P pieces, IIR pieces; iqd_debug_stamps)
@@ -378,20 +386,40 @@ struct StIir {
 #endif
 };
 
+// The de-emphasis filter's input sums t[n] = u[n] + u[n-1] of one window, from its four ring chunks (u0, u2, u1, u3) and the sample
+// before.  (t1, t3) = (u1, u3) + (u0, u2) is ONE packed addition of the two register pairs as ds_read_b128 delivers them - the same
+// IEEE addition per element, and off the recurrence's chain; t2 = u2 + u1 and t0 = u0 + (u3 of the chunk before) are single ones.
+__device__ __forceinline__ void st_iir_sums(const u32x4 (&v)[4], float up, float (&sum)[16])
+{
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const float u0 = u2f(v[g].x), u2 = u2f(v[g].y), u1 = u2f(v[g].z), u3 = u2f(v[g].w);
+        sum[4 * g] = u0 + up;
+        const v2f t13 = v2f{u1, u3} + v2f{u0, u2};
+        sum[4 * g + 1] = t13.x;
+        sum[4 * g + 3] = t13.y;
+        sum[4 * g + 2] = u2 + u1;
+        up = u3;
+    }
+}
+
 // 16 samples of one segment: de-emphasis (IirFilter.cc:161-176 op by op), (int16), /4 with 8 taps, then one
 // /4 output with 12 taps.  Returns that stage-2 output.
-__device__ __forceinline__ int st_iir_window(const StreamArgs &sa, StIir &s, const float (&u)[16], int c14, int c15)
+__device__ __forceinline__ int st_iir_window(const StreamArgs &sa, StIir &s, const u32x4 (&v)[4], int c14, int c15)
 {
     uint32_t wq[10];                                   // 20 samples: the last quad, then this window's four
-    float y = s.y, up = s.up;
+    float y = s.y;
     const float a1 = sa.a1;
+    float sum[16];
+    st_iir_sums(v, s.up, sum);
 #pragma unroll
-    for (int k = 0; k < 8; k++) {
-        IQD_IIR_STEP(u[2 * k])
+    for (int k = 0; k < 8; k++) {                      // (IQD_IIR_STEP with its sum formed ahead: r = a1 y, y = t - r)
+        y = sum[2 * k] - a1 * y;
         const float y_even = y;
-        IQD_IIR_STEP(u[2 * k + 1])
+        y = sum[2 * k + 1] - a1 * y;
         wq[2 + k] = cast_pack_i16_bounded(y_even, y);
     }
+    const float up = u2f(v[3].w);
     s.y = y;
     s.up = up;
     wq[0] = s.wlast[0];
@@ -486,11 +514,12 @@ __device__ __forceinline__ void st_iir_marks(const ChainLaunch &a, StIirSeg &q, 
 // FAST: every segment of the wave is cold and of full length (or not there at all), so the few things that happen at
 // particular positions happen at the SAME position in every lane - one scalar compare per window instead of a dozen
 // per-lane compare-and-select operations - and the lead-in has already been run by st_iir_lead_in().
+// sync_a: the LDS byte address of the ring's sync words, in a vector register (lds_word_uniform).
 // yk: pieces this wave has handed to the audio wave so far (all rounds).
 template <bool FAST>
-__device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamArgs &sa, uint8_t *ring_base, const uint32_t *full, uint32_t *consumed,
-                                             uint32_t &wg, const StY2Ring &y2r, uint32_t &yk, StIirSeg &q, StIir &s, int pos, uint32_t rd_off0,
-                                             uint32_t rd_swz, int lane, int rec_pos_uniform)
+__device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamArgs &sa, const uint32_t (&rd_a)[4], uint32_t sync_a,
+                                             uint32_t &wg, const StY2Ring &y2r, uint32_t &yk, StIirSeg &q, StIir &s, int pos, int lane,
+                                             int rec_pos_uniform)
 {
     uint32_t y2_seen = 0;
 #pragma unroll
@@ -498,10 +527,12 @@ __device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamA
         const int wpos = pos + 16 * half;
         if (half == 0) {   // the four P waves of the ring have written piece `wg` (both windows) when `full` reaches 4 (wg + 1)
             const uint32_t target = 4u * (wg / (uint32_t)ST_DEPTH + 1u);
-            const uint32_t *const fullp = ST_DEPTH > 1 ? full + (wg & (uint32_t)(ST_DEPTH - 1)) : full;
+            const uint32_t full_off = ST_DEPTH > 1 ? 4u * (wg & (uint32_t)(ST_DEPTH - 1)) : 0u;
             ST_T(tw0);
-            while ((int32_t)(lds_load_relaxed(fullp) - target) < 0) {
+            uint32_t seen = lds_word_uniform(sync_a, full_off);
+            while ((int32_t)(seen - target) < 0) {
                 __builtin_amdgcn_s_sleep(IQD_ST_SLEEP_I);
+                seen = lds_word_uniform(sync_a, full_off);
                 if (IQD_ST_WAITSTAT) s.n_sleeps++;
             }
 #if IQD_ST_TIMING
@@ -510,17 +541,15 @@ __device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamA
             ST_TRACE(s.stamps, s.ring, wg, 0);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
-        const uint8_t *slot = ring_base + (ST_DEPTH > 1 ? (wg & (uint32_t)(ST_DEPTH - 1)) * (2 * ST_SLOT_BYTES) : 0u) + half * ST_SLOT_BYTES + rd_off0;
-        float u[16];
+        const uint32_t slot = (ST_DEPTH > 1 ? (wg & (uint32_t)(ST_DEPTH - 1)) * (2 * ST_SLOT_BYTES) : 0u) + half * ST_SLOT_BYTES;
+        u32x4 v[4];                                    // a chunk holds (u0, u2, u1, u3): st_p_wave, phase C
 #pragma unroll
-        for (int gq = 0; gq < 4; gq++) {
-            const u32x4 v = *(const u32x4 *)(slot + (((uint32_t)gq ^ rd_swz) << 4));
-            u[4 * gq] = u2f(v.x); u[4 * gq + 2] = u2f(v.y); u[4 * gq + 1] = u2f(v.z); u[4 * gq + 3] = u2f(v.w);   // a chunk holds (u0, u2, u1, u3): st_p_wave, phase C
-        }
+        for (int gq = 0; gq < 4; gq++) v[gq] = st_ring_read(rd_a[gq] + slot);
         if (half == 1) {   // both windows read: the ring is free for the next piece
-            y2_seen = lds_load_relaxed(y2r.consumed);                // asked early (it returns with the reads above), needed only before the hand-over
+            // asked early (it returns with the reads above), needed only before the hand-over
+            y2_seen = lds_load_relaxed((const uint32_t *)(uintptr_t)(sync_a + 4u * ST_SYNC_Y2_CONSUMED));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the reads have returned
-            lds_signal(consumed);
+            lds_signal_at<16>(sync_a);
             ST_TRACE(s.stamps, s.ring, wg, 1);
             wg++;
 #if IQD_ST_TIMING
@@ -529,7 +558,7 @@ __device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamA
         }
         if (!FAST) st_iir_marks(a, q, s, wpos, rec_pos_uniform);
         else if (wpos == rec_pos_uniform) { q.rec.y_out = s.y; q.rec.u_out = s.up; }
-        const int y2 = st_iir_window(sa, s, u, q.c14, q.c15);
+        const int y2 = st_iir_window(sa, s, v, q.c14, q.c15);
         if (wpos >= 0 && wpos < 48 && q.sg.valid) {    // (uniform) the segment's first values, for the boundary fix-up
             if (wpos == 0) ST_STORE16(q.hist->w_first, s.wq0[0], s.wq0[1], s.y1h[2], s.y1h[3]);   // (w_first, y1_first[0..1])
             else *(u32x2 *)&q.hist->y1_first[wpos >> 3] = u32x2{s.y1h[2], s.y1h[3]};
@@ -537,15 +566,17 @@ __device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamA
         if (half == 0) s.y2lo = (uint32_t)y2;
         else {   // the piece's pair goes to the audio wave: its slot is free once piece yk - ST_Y2_DEPTH has been read
             const StY2Piece yp = st_y2_piece(yk, ST_Y2_DEPTH, ST_Y2_EVERY);
+            // (one LDS word, the same in every lane: the test runs on the scalar unit)
+            y2_seen = (uint32_t)__builtin_amdgcn_readfirstlane((int)y2_seen);
             while ((int32_t)(y2_seen - yp.need_consumed) < 0) {
                 __builtin_amdgcn_s_sleep(IQD_ST_SLEEP_I);
-                y2_seen = lds_load_relaxed(y2r.consumed);
+                y2_seen = lds_word_uniform(sync_a, 4u * ST_SYNC_Y2_CONSUMED);
                 if (IQD_ST_WAITSTAT) s.n_sleeps++;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             *(uint32_t *)(y2r.lane_slot0 + yp.slot * ST_Y2_SLOT_BYTES) = pack_lo16(s.y2lo, (uint32_t)y2);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (yp.add_full) lds_signal(y2r.full, yp.add_full);
+            if (yp.add_full) lds_signal_at<4 * ST_SYNC_Y2_FULL>(sync_a, yp.add_full);
             yk++;
         }
     }
@@ -554,28 +585,36 @@ __device__ __forceinline__ void st_iir_piece(const ChainLaunch &a, const StreamA
 
 // The lead-in of a wave whose segments are all cold: only the de-emphasis recurrence (its state is what the lead-in is
 // for; a cold segment's decimators start with histories that the boundary fix-up replaces anyway).
-__device__ __forceinline__ void st_iir_lead_in(const StreamArgs &sa, uint8_t *ring_base, const uint32_t *full, uint32_t *consumed,
-                                               uint32_t &wg, StIir &s, uint32_t rd_off0, uint32_t rd_swz)
+__device__ __forceinline__ void st_iir_lead_in(const StreamArgs &sa, const uint32_t (&rd_a)[4], uint32_t sync_a,
+                                               uint32_t &wg, StIir &s)
 {
     float y = s.y, up = s.up;
     const float a1 = sa.a1;
     for (int piece = 0; piece < ST_HALO / 32; piece++) {
         const uint32_t target = 4u * (wg / (uint32_t)ST_DEPTH + 1u);
-        while ((int32_t)(lds_load_relaxed(ST_DEPTH > 1 ? full + (wg & (uint32_t)(ST_DEPTH - 1)) : full) - target) < 0) __builtin_amdgcn_s_sleep(IQD_ST_SLEEP_I);
+        const uint32_t full_off = ST_DEPTH > 1 ? 4u * (wg & (uint32_t)(ST_DEPTH - 1)) : 0u;
+        uint32_t seen = lds_word_uniform(sync_a, full_off);
+        while ((int32_t)(seen - target) < 0) {
+            __builtin_amdgcn_s_sleep(IQD_ST_SLEEP_I);
+            seen = lds_word_uniform(sync_a, full_off);
+        }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        u32x4 v[8];
+        u32x4 v[2][4];
 #pragma unroll
         for (int half = 0; half < 2; half++)
 #pragma unroll
             for (int gq = 0; gq < 4; gq++)
-                v[4 * half + gq] = *(const u32x4 *)(ring_base + (ST_DEPTH > 1 ? (wg & (uint32_t)(ST_DEPTH - 1)) * (2 * ST_SLOT_BYTES) : 0u) +
-                                                    half * ST_SLOT_BYTES + rd_off0 + (((uint32_t)gq ^ rd_swz) << 4));
+                v[half][gq] = st_ring_read(rd_a[gq] + (ST_DEPTH > 1 ? (wg & (uint32_t)(ST_DEPTH - 1)) * (2 * ST_SLOT_BYTES) : 0u) + half * ST_SLOT_BYTES);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the reads have returned
-        lds_signal(consumed);
+        lds_signal_at<16>(sync_a);
         wg++;
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            IQD_IIR_STEP(u2f(v[k].x)) IQD_IIR_STEP(u2f(v[k].z)) IQD_IIR_STEP(u2f(v[k].y)) IQD_IIR_STEP(u2f(v[k].w))   // a chunk holds (u0, u2, u1, u3)
+        for (int half = 0; half < 2; half++) {
+            float sum[16];
+            st_iir_sums(v[half], up, sum);
+#pragma unroll
+            for (int k = 0; k < 16; k++) y = sum[k] - a1 * y;
+            up = u2f(v[half][3].w);
         }
     }
     s.y = y;
@@ -586,10 +625,19 @@ __device__ __forceinline__ void st_iir_wave(const ChainLaunch &a, const StreamAr
                                             int ring, int lane)
 {
     uint8_t *ring_base = lds + ST_TABLE_BYTES + ring * (ST_RING_SLOTS * ST_SLOT_BYTES);
-    const uint32_t *full = sync + ring * 8;
-    uint32_t *consumed = sync + ring * 8 + 4;
     const StY2Ring y2r = st_y2_ring(lds, sync, ring, lane);
-    const uint32_t rd_off0 = (uint32_t)lane * 64u, rd_swz = ((uint32_t)lane >> 2) & 3u;
+    // the ring's sync words ([0 .. 3] `full`, [4] `consumed`, [5], [6] the y2 ring's): their LDS address lives in a vector register
+    // for the wave's whole life, and every look at one of them is that register plus a constant (lds_word_uniform)
+    uint32_t sync_a = (uint32_t)(uintptr_t)(sync + ring * 8);
+    asm volatile("" : "+v"(sync_a));
+    // the LDS byte addresses of the lane's four chunks of the ring's first slot (st_slot_off), in four vector registers for the wave's
+    // whole life: every ring read is one of them plus a constant
+    uint32_t rd_a[4];
+#pragma unroll
+    for (int gq = 0; gq < 4; gq++) {
+        rd_a[gq] = (uint32_t)(uintptr_t)ring_base + st_slot_off((uint32_t)lane, (uint32_t)gq);
+        asm volatile("" : "+v"(rd_a[gq]));
+    }
     const int n_pieces = (ST_HALO + (int)a.tile_len) >> 5;       // a multiple of 4
     if (ring >= (int)sa.rings) return;
     const uint32_t wg_segs = 64u * sa.rings;
@@ -649,13 +697,13 @@ __device__ __forceinline__ void st_iir_wave(const ChainLaunch &a, const StreamAr
         if (keeps_restart) q.sg.valid |= 2u;
         const int rec_pos_uniform = (int)a.tile_len - FORCED_BACK;
         if (fast) {
-            st_iir_lead_in(sa, ring_base, full, consumed, wg, s, rd_off0, rd_swz);
+            st_iir_lead_in(sa, rd_a, sync_a, wg, s);
             q.rec.y_in = s.y;                                    // the warmed-up state, checked against the predecessor's end
             for (int pq = ST_HALO / 32; pq < n_pieces; pq++)
-                st_iir_piece<true>(a, sa, ring_base, full, consumed, wg, y2r, yk, q, s, -ST_HALO + 32 * pq, rd_off0, rd_swz, lane, rec_pos_uniform);
+                st_iir_piece<true>(a, sa, rd_a, sync_a, wg, y2r, yk, q, s, -ST_HALO + 32 * pq, lane, rec_pos_uniform);
         } else {
             for (int pq = 0; pq < n_pieces; pq++)
-                st_iir_piece<false>(a, sa, ring_base, full, consumed, wg, y2r, yk, q, s, -ST_HALO + 32 * pq, rd_off0, rd_swz, lane, rec_pos_uniform);
+                st_iir_piece<false>(a, sa, rd_a, sync_a, wg, y2r, yk, q, s, -ST_HALO + 32 * pq, lane, rec_pos_uniform);
         }
         st_iir_marks(a, q, s, (int)a.tile_len, rec_pos_uniform);
         if (q.sg.valid) {
