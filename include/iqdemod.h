@@ -297,6 +297,56 @@ size_t iqd_resampler_out_count(const iqd_resampler_t *r, size_t n_in);
 int iqd_resampler_run(iqd_resampler_t *r, const void *in, size_t n_in, void *out);                 /* host pointers */
 int iqd_resampler_run_device(iqd_resampler_t *r, const void *in_dev, size_t n_in, void *out_dev);  /* queued on the engine's stream */
 
+/* The reference's four hot-path filter classes (layer L0) stand-alone, block-wise and for n_channels
+ * independent streams at once, with the caller's own coefficients.  A filter replaces, per channel, one object of
+ *   IQD_FILTER_DECIMATE_I16  Decimator_int16(filterLength, coefficients, decimationFactor), Filters/Int16/Decimator_int16.cc
+ *                            :176-238, :310-351: n counts samples since create / reset, an output when n = factor - 1
+ *                            (mod factor): acc = 1 << 14; for k = 0 .. L-1 in this order acc += hq[k] x[n-k], clamped to
+ *                            [-2^30, 2^30 - 1] after EVERY MAC; y = (int16)(acc >> 15).  1 <= factor <= 64, 1 <= L <= 1024;
+ *   IQD_FILTER_FIR_I16       FirFilter_int16(...), Filters/Int16/FirFilter_int16.cc:151-213: the same with an output for
+ *                            every input (factor must be 1);
+ *   IQD_FILTER_FIR_F32       FirFilter(...), Filters/FirFilter.cc:144-185: y = 0, then y = y + h[k] x[n-k] for k ascending,
+ *                            every product and sum rounded to float.  1 <= L <= 1024, factor 1;
+ *   IQD_FILTER_IIR_F32       IirFilter(...), Filters/IirFilter.cc:161-229: v = the FIR_F32 sum over num; r = 0, then
+ *                            r = r + den[k] y[n-1-k] for k ascending; y[n] = v - r.  den excludes the leading 1 (the DC
+ *                            blocker is num {1, -1}, den {-0.95}).  1 <= n_num <= 64, 1 <= n_den <= 64, factor 1,
+ * and a call with n_in samples per channel replaces n_in decimate() / filterData() calls.  x[n < 0] = 0.  The state carries
+ * over from call to call per channel: the FIR history, the decimator's commutator phase, the IIR's past inputs and
+ * outputs; iqd_filter_reset = resetFilterState().  The I16 kinds quantise num like the reference's constructors (round(32768
+ * h) cast to int16: a tap of 1.0 becomes -32768).  den / n_den are NULL / 0 for the three FIR kinds.
+ *
+ * Layouts: in [n_channels][n_in], out [n_channels][iqd_filter_out_count(f, n_in)]; int16 elements for the I16 kinds, float
+ * for the F32 kinds.  0 <= n_in <= 2^31 - 1; a decimator call may yield no output.  Device pointers need only the element's
+ * alignment (the kernels stage 16 bytes per lane where every row happens to be 16-byte aligned, with identical results).
+ * Results are bit for bit the reference's for finite inputs (for NaN / Inf the bit pattern is unspecified); float
+ * subnormals are kept, not flushed.
+ *
+ * Refusals, each IQD_EINVAL with a message naming the argument, before anything is allocated or queued: a NULL pointer, kind
+ * out of range, n_num / n_den / factor outside the ranges above (factor != 1 where it must be 1, den given to a FIR kind or
+ * missing for IIR_F32), n_channels = 0, n_in above 2^31 - 1.
+ *
+ * IIR_F32 is serial in time and exact (no scan, no warm-up overlap: both would change the rounding for arbitrary
+ * coefficients): one lane per channel, one wave per 64 channels.  Fewer than 64 x (number of CUs) channels therefore cannot
+ * fill the device.
+ *
+ * Host only, no GPU:
+ *   iqd_filter_tile_samples     the input samples (IIR: time steps) one workgroup stages per tile for these sizes, 0 for
+ *                               sizes out of range - where calls of T - 1, T and T + 1 samples take different paths;
+ *   iqd_filter_clamp_free_taps  the largest K0 <= n_taps with sum over k < K0 of |hq[k]| <= 32767: up to tap K0 no partial
+ *                               sum can leave [-2^30, 2^30 - 1] for any int16 input (2^14 + 32768 x 32767 < 2^30), so the
+ *                               kernel sums that prefix with packed dot products and clamps only from K0 on. */
+enum iqd_filter_kind { IQD_FILTER_DECIMATE_I16 = 0, IQD_FILTER_FIR_I16 = 1, IQD_FILTER_FIR_F32 = 2, IQD_FILTER_IIR_F32 = 3 };
+typedef struct iqd_filter iqd_filter_t;
+int iqd_filter_create(iqd_t *e, int kind, const float *num, uint32_t n_num, const float *den, uint32_t n_den, uint32_t factor,
+                      uint32_t n_channels, iqd_filter_t **out);
+void iqd_filter_destroy(iqd_filter_t *f);
+int iqd_filter_reset(iqd_filter_t *f);
+size_t iqd_filter_out_count(const iqd_filter_t *f, size_t n_in);
+int iqd_filter_run(iqd_filter_t *f, const void *in, size_t n_in, void *out);                 /* host pointers */
+int iqd_filter_run_device(iqd_filter_t *f, const void *in_dev, size_t n_in, void *out_dev);  /* queued on the engine's stream */
+uint32_t iqd_filter_tile_samples(int kind, uint32_t n_num, uint32_t n_den, uint32_t factor);
+uint32_t iqd_filter_clamp_free_taps(const float *taps, uint32_t n_taps);
+
 /* Wideband channelizer: many engine channels cut out of one capture (uint8 here; int8 and int16: "Signed captures" below) at M x 256 kS/s (an RTL-SDR at 2.048 MS/s is
  * M = 8).  The reference gets its one channel from the RTL2832U's own down-converter (Radio tunes the dongle, the chip
  * delivers 256 kS/s around that frequency); this is the same front for any number of channels of one receiver.  Every

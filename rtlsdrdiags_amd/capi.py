@@ -72,6 +72,8 @@ EXPORTS = [
     "iqd_channelizer_tuning", "iqd_accept_wideband_device", "iqd_channelizer_default_taps_q",
     "iqd_channelizer_set_survey", "iqd_channelizer_survey_device", "iqd_channelizer_survey", "iqd_magnitude_dbfs",
     "iqd_channelizer_window_outputs", "iqd_channelizer_follow_gain",
+    "iqd_filter_create", "iqd_filter_destroy", "iqd_filter_reset", "iqd_filter_out_count", "iqd_filter_run",
+    "iqd_filter_run_device", "iqd_filter_tile_samples", "iqd_filter_clamp_free_taps",
 ]
 
 _LIB = None
@@ -115,6 +117,18 @@ def _lib():
     L.iqd_resampler_out_count.restype = sz
     L.iqd_resampler_run.argtypes = [vp, vp, sz, vp]
     L.iqd_resampler_run_device.argtypes = [vp, vp, sz, vp]
+    L.iqd_filter_create.argtypes = [vp, C.c_int, vp, u32, vp, u32, u32, u32, C.POINTER(vp)]
+    L.iqd_filter_destroy.argtypes = [vp]
+    L.iqd_filter_destroy.restype = None
+    L.iqd_filter_reset.argtypes = [vp]
+    L.iqd_filter_out_count.argtypes = [vp, sz]
+    L.iqd_filter_out_count.restype = sz
+    L.iqd_filter_run.argtypes = [vp, vp, sz, vp]
+    L.iqd_filter_run_device.argtypes = [vp, vp, sz, vp]
+    L.iqd_filter_tile_samples.argtypes = [C.c_int, u32, u32, u32]
+    L.iqd_filter_tile_samples.restype = u32
+    L.iqd_filter_clamp_free_taps.argtypes = [vp, u32]
+    L.iqd_filter_clamp_free_taps.restype = u32
     L.iqd_front_end_device.argtypes = [vp, u32, u32, vp, sz, vp]
     L.iqd_convert_fs_over_4.argtypes = [vp, C.c_int, vp, sz]
     L.iqd_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -540,6 +554,61 @@ class Resampler:
             self._L.iqd_resampler_destroy(self._h)
             self._h = None
 
+class Filter:
+    """Block-wise Decimator_int16 / FirFilter_int16 / FirFilter / IirFilter for n_channels streams (include/iqdemod.h:
+    iqd_filter_*).  kind: "decimate_i16", "fir_i16", "fir_f32" or "iir_f32"; num: the taps (IIR: the numerator), den: the
+    IIR's denominator without its leading 1 (None for the FIR kinds)."""
+    KINDS = {"decimate_i16": 0, "fir_i16": 1, "fir_f32": 2, "iir_f32": 3}
+
+    def __init__(self, engine, kind, num, den=None, factor=1, n_channels=1):
+        self._e, self._L = engine, engine._L
+        self._h = None
+        self.kind, self.n_ch = self.KINDS.get(kind, kind), int(n_channels)
+        self.dtype = np.int16 if self.kind in (0, 1) else np.float32
+        num = None if num is None else np.ascontiguousarray(num, np.float32)
+        den = None if den is None else np.ascontiguousarray(den, np.float32)
+        h = C.c_void_p()
+        engine._check(self._L.iqd_filter_create(engine._h, int(self.kind), _np_ptr(num), 0 if num is None else len(num),
+                                                _np_ptr(den), 0 if den is None else len(den), int(factor), self.n_ch,
+                                                C.byref(h)))
+        self._h = h
+
+    def out_count(self, n_in):
+        return int(self._L.iqd_filter_out_count(self._h, int(n_in)))
+
+    def run(self, x):
+        """[n_channels, n_in] host array (or one row) -> [n_channels, out_count(n_in)]"""
+        x = np.ascontiguousarray(x, self.dtype).reshape(self.n_ch, -1)
+        out = np.zeros((self.n_ch, self.out_count(x.shape[1])), self.dtype)
+        guard = out if out.size else np.zeros(8, self.dtype)    # (a call without output gets a valid pointer all the same)
+        xin = x if x.size else np.zeros(8, self.dtype)
+        self._e._check(self._L.iqd_filter_run(self._h, _np_ptr(xin), x.shape[1], _np_ptr(guard)))
+        return out
+
+    def run_device(self, in_dev, n_in, out_dev):
+        """iqd_filter_run_device: device pointers (integers), queued on the engine's stream."""
+        self._e._check(self._L.iqd_filter_run_device(self._h, C.c_void_p(in_dev or None), int(n_in), C.c_void_p(out_dev or None)))
+
+    def reset(self):
+        self._e._check(self._L.iqd_filter_reset(self._h))
+
+    def close(self):
+        if self._h and self._e._h:
+            self._L.iqd_filter_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+
+def filter_tile_samples(kind, n_num, n_den=0, factor=1):
+    """iqd_filter_tile_samples (host only): the input samples (IIR: time steps) one workgroup stages per tile, 0 if out of range."""
+    return int(_lib().iqd_filter_tile_samples(int(Filter.KINDS.get(kind, kind)), int(n_num), int(n_den), int(factor)))
+
+
+def filter_clamp_free_taps(taps):
+    """iqd_filter_clamp_free_taps (host only): how many leading taps, once quantised to Q15, can never reach the per-MAC clamp."""
+    taps = np.ascontiguousarray(taps, np.float32)
+    return int(_lib().iqd_filter_clamp_free_taps(_np_ptr(taps), len(taps)))
 
 
 def channelizer_phasor_table():
