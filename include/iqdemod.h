@@ -571,6 +571,55 @@ int iqd_channelizer_survey(iqd_channelizer_t *z, const uint8_t *wide, size_t byt
                            uint32_t *magnitude);
 int32_t iqd_magnitude_dbfs(uint32_t magnitude);
 
+/* Band spectrum: an integer periodogram of the capture - every bin of the band at once, where the survey measures chosen
+ * points through a whole channel filter.  A bin is a channelizer channel's stage A with M = K = N: the window times the
+ * phasor table, summed over the frame's samples.  Every step is integer and fixed here, so results are exact:
+ *
+ *   sources   [n_sources][bytes_per_source], interleaved I/Q, one byte per rail.  IQD_WIDE_U8: x[n] = (I - 128) + j (Q - 128);
+ *             IQD_WIDE_S8: the bytes as they are.  IQD_WIDE_S16 is refused (IQD_EINVAL, the message naming the format).
+ *   frames    a frame is N consecutive samples; frames do not overlap.  No history, no state from call to call, no reset.
+ *   N         n_bins: 64, 128, 256, 512, 1024 or 2048.
+ *   window    w[0..N) int16, may be negative; |w[n]| <= 32639 and 256 sum |w| <= 2^31 - 256 (the channelizer's prototype
+ *             conditions).  window == NULL: iqd_spectrum_default_window(N).
+ *   phasor    P[i] = (Pc, Ps): iqd_channelizer_phasor_table, 4096 entries.
+ *   bin k'    0 <= k' < N, q = k' - N / 2: rows run from low to high frequency, the centre frequency is bin N / 2.
+ *             i(n) = ((q n) mod N) (4096 / N), the mod non-negative;
+ *             c[n] = (w[n] Pc[i] + 2^14) >> 15,  s[n] = (w[n] Ps[i] + 2^14) >> 15   (>> arithmetic throughout)
+ *             Ar = sum_n c[n] xr[n] + s[n] xi[n],  Ai = sum_n c[n] xi[n] - s[n] xr[n]      (exact in int32)
+ *             ar = (Ar + 2^15) >> 16, ai likewise;  p = ar^2 + ai^2.  No saturation: |A| <= 128 x 1.4143 x 2^23 < 2^31, so
+ *             |a| <= 23172 and p < 2^31.
+ *   blocks    a block is F = frames_per_block consecutive frames, 1 <= F <= 2^24; bytes_per_source is a non-zero multiple
+ *             of 2 N F; n_blocks = bytes_per_source / (2 N F).
+ *   output    power[n_sources][n_blocks][N] uint32 = floor((sum over the block's frames of p) / F), the sum in 64 bits.
+ *   default   iqd_spectrum_default_window(N): w[n] = (32767 - Pc[(2 n + 1) (2048 / N)]) >> sh, sh the smallest value >= 2
+ *             with 256 sum w <= 2^31 - 256 - a Hann window with a half-sample offset, symmetric, integer only (sh = 2 up
+ *             to N = 1024, 3 at N = 2048).
+ *   full scale iqd_spectrum_full_scale(window, N): with c0[n] = (32767 w[n] + 2^14) >> 15,
+ *             p_fs = ((127 sum_n c0[n] + 2^15) >> 16)^2: what bin N / 2 gives for the constant U8 input (255, 128).
+ *             dBFS = 10 log10(max(p, 1) / p_fs).
+ *   refusals  IQD_EINVAL with a message naming the argument, before anything is allocated or queued.  At create: a NULL
+ *             pointer, n_sources = 0, n_bins outside the set, sample_format S16 or above 2, a non-zero reserved word, a
+ *             window outside its bounds.  At run: frames_per_block 0 or above 2^24, bytes_per_source 0 or not a multiple
+ *             of 2 N F, a NULL or misaligned device pointer, more (block, 64 bins) pairs than one launch covers (2^31 - 1).
+ * A spectrum object is independent of channelizers: both may live on one engine and read the same device buffer.
+ * wide_dev and power_dev: device memory, both 16-byte aligned.  The _device form is queued on the engine's stream and
+ * returns once queued; the host form returns when done.  default_window and full_scale are host only, no GPU. */
+typedef struct iqd_spectrum_config {
+    uint32_t n_sources;     /* >= 1 */
+    uint32_t n_bins;        /* N */
+    const int16_t *window;  /* w[0..N); NULL -> iqd_spectrum_default_window(N) */
+    uint32_t sample_format; /* IQD_WIDE_U8 or IQD_WIDE_S8 */
+    uint32_t reserved[3];   /* 0 */
+} iqd_spectrum_config;
+typedef struct iqd_spectrum iqd_spectrum_t;
+int iqd_spectrum_create(iqd_t *e, const iqd_spectrum_config *cfg, iqd_spectrum_t **out);
+void iqd_spectrum_destroy(iqd_spectrum_t *s);   /* before its engine's iqd_destroy */
+int iqd_spectrum_run_device(iqd_spectrum_t *s, const void *wide_dev, size_t bytes_per_source, uint32_t frames_per_block,
+                            uint32_t *power_dev);
+int iqd_spectrum_run(iqd_spectrum_t *s, const void *wide, size_t bytes_per_source, uint32_t frames_per_block, uint32_t *power);
+int iqd_spectrum_default_window(uint32_t n_bins, int16_t *out);
+int iqd_spectrum_full_scale(const int16_t *window, uint32_t n_bins, uint32_t *p_fs);   /* window NULL = the default */
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

@@ -47,6 +47,11 @@ class ChannelizerConfig(C.Structure):
                 ("sample_format", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class SpectrumConfig(C.Structure):
+    _fields_ = [("n_sources", C.c_uint32), ("n_bins", C.c_uint32), ("window", C.c_void_p),
+                ("sample_format", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class IqdError(RuntimeError):
     def __init__(self, status, detail):
         super().__init__("libiqdemod: %s (%d): %s" % (_lib().iqd_strerror(status).decode(), status, detail))
@@ -74,6 +79,8 @@ EXPORTS = [
     "iqd_channelizer_window_outputs", "iqd_channelizer_follow_gain",
     "iqd_filter_create", "iqd_filter_destroy", "iqd_filter_reset", "iqd_filter_out_count", "iqd_filter_run",
     "iqd_filter_run_device", "iqd_filter_tile_samples", "iqd_filter_clamp_free_taps",
+    "iqd_spectrum_create", "iqd_spectrum_destroy", "iqd_spectrum_run_device", "iqd_spectrum_run",
+    "iqd_spectrum_default_window", "iqd_spectrum_full_scale",
 ]
 
 _LIB = None
@@ -182,6 +189,13 @@ def _lib():
     L.iqd_channelizer_window_outputs.restype = u32
     L.iqd_magnitude_dbfs.argtypes = [u32]
     L.iqd_magnitude_dbfs.restype = C.c_int32
+    L.iqd_spectrum_create.argtypes = [vp, C.POINTER(SpectrumConfig), C.POINTER(vp)]
+    L.iqd_spectrum_destroy.argtypes = [vp]
+    L.iqd_spectrum_destroy.restype = None
+    L.iqd_spectrum_run_device.argtypes = [vp, vp, sz, u32, vp]
+    L.iqd_spectrum_run.argtypes = [vp, vp, sz, u32, vp]
+    L.iqd_spectrum_default_window.argtypes = [u32, vp]
+    L.iqd_spectrum_full_scale.argtypes = [vp, u32, C.POINTER(u32)]
     _LIB = L
     return L
 
@@ -788,6 +802,92 @@ class Channelizer:
         """iqd_channelizer_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
         if self._h and self._e._h:
             self._L.iqd_channelizer_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+
+def spectrum_default_window(n_bins):
+    """iqd_spectrum_default_window (host only, no GPU): the integer Hann window of n_bins entries, int16."""
+    out = np.zeros(int(n_bins) if 0 < int(n_bins) <= 4096 else 1, np.int16)
+    rc = _lib().iqd_spectrum_default_window(int(n_bins) & 0xffffffff, _np_ptr(out))
+    if rc != 0:
+        raise IqdError(rc, "iqd_spectrum_default_window: n_bins %r" % (n_bins,))
+    return out
+
+
+def spectrum_full_scale(n_bins, window=None):
+    """iqd_spectrum_full_scale (host only, no GPU): the power of bin n_bins / 2 for the constant U8 input (255, 128)."""
+    w = None if window is None else np.ascontiguousarray(window, np.int16)
+    if w is not None and len(w) != int(n_bins):
+        raise ValueError("the window must have n_bins (%d) entries, not %d" % (int(n_bins), len(w)))
+    p = C.c_uint32()
+    rc = _lib().iqd_spectrum_full_scale(_np_ptr(w), int(n_bins) & 0xffffffff, C.byref(p))
+    if rc != 0:
+        raise IqdError(rc, "iqd_spectrum_full_scale: n_bins %r or the window out of range" % (n_bins,))
+    return p.value
+
+
+def spectrum_dbfs(power, p_fs):
+    """10 log10(max(power, 1) / p_fs): a power of Spectrum.run against spectrum_full_scale, in dBFS (float64)."""
+    return 10.0 * np.log10(np.maximum(np.asarray(power, np.float64), 1.0) / float(p_fs))
+
+
+class Spectrum:
+    """iqd_spectrum_*: the integer periodogram of n_sources wideband captures, n_bins bins (64 .. 2048, a power of two) from
+    low to high frequency, the centre frequency at bin n_bins / 2.  window: n_bins int16 values (None: the default Hann
+    window); sample_format "u8" or "s8"."""
+
+    def __init__(self, engine, n_bins, n_sources=1, window=None, sample_format="u8"):
+        self._e, self._L = engine, engine._L
+        self._h = None
+        if sample_format not in SAMPLE_FORMAT:
+            raise ValueError("sample_format must be one of %s" % ", ".join(SAMPLE_FORMAT))
+        self.sample_format = sample_format
+        self._code, self._dtype = SAMPLE_FORMAT[sample_format]
+        self.n_bins, self.n_sources = int(n_bins), int(n_sources)
+        self._window = None if window is None else np.ascontiguousarray(window, np.int16)
+        if self._window is not None and self._window.shape != (self.n_bins,):
+            raise ValueError("the window must have n_bins (%d) entries" % self.n_bins)
+        cfg = SpectrumConfig(self.n_sources & 0xffffffff, self.n_bins & 0xffffffff,
+                             None if self._window is None else self._window.ctypes.data, self._code)
+        h = C.c_void_p()
+        engine._check(self._L.iqd_spectrum_create(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        if not hasattr(engine, "_children"):
+            engine._children = weakref.WeakSet()
+        engine._children.add(self)
+
+    def _capture(self, wide):
+        """One call's capture as [n_sources, bytes_per_source] bytes; an array of the other format's dtype is a TypeError
+        (as Channelizer._capture)."""
+        dt = getattr(wide, "dtype", None)
+        if dt is not None and dt != self._dtype and (self._code != 0 or dt in (np.dtype(np.int8), np.dtype(np.int16))):
+            raise TypeError("a spectrum of sample_format %r takes %s arrays, not %s" % (self.sample_format, self._dtype, dt))
+        wide = np.ascontiguousarray(wide, dtype=self._dtype).reshape(self.n_sources, -1)
+        return wide.view(np.uint8)
+
+    def run(self, wide, frames_per_block):
+        """[n_sources, bytes_per_source] of the format's dtype -> [n_sources, n_blocks, n_bins] uint32 (host arrays),
+        n_blocks = bytes_per_source / (2 n_bins frames_per_block)."""
+        wide = self._capture(wide)
+        F = int(frames_per_block)
+        nb = wide.shape[1] // (2 * self.n_bins * F) if F > 0 else 0
+        out = np.zeros((self.n_sources, nb, self.n_bins), np.uint32)
+        guard = out if out.size else np.zeros(4, np.uint32)      # (a refused call gets a valid pointer all the same)
+        src = wide if wide.size else np.zeros(16, np.uint8)
+        self._e._check(self._L.iqd_spectrum_run(self._h, _np_ptr(src), wide.shape[1], F & 0xffffffff, _np_ptr(guard)))
+        return out
+
+    def run_device(self, wide_dev, bytes_per_source, frames_per_block, power_dev):
+        """iqd_spectrum_run_device: device pointers (integers), queued on the engine's stream."""
+        self._e._check(self._L.iqd_spectrum_run_device(self._h, C.c_void_p(wide_dev or None), int(bytes_per_source),
+                                                       int(frames_per_block) & 0xffffffff, C.c_void_p(power_dev or None)))
+
+    def close(self):
+        """iqd_spectrum_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
+        if self._h and self._e._h:
+            self._L.iqd_spectrum_destroy(self._h)
         self._h = None
 
     __del__ = close
