@@ -620,6 +620,67 @@ int iqd_spectrum_run(iqd_spectrum_t *s, const void *wide, size_t bytes_per_sourc
 int iqd_spectrum_default_window(uint32_t n_bins, int16_t *out);
 int iqd_spectrum_full_scale(const int16_t *window, uint32_t n_bins, uint32_t *p_fs);   /* window NULL = the default */
 
+/* Band activity: the occupied runs of a band spectrum - which stretches of the band stand above the noise floor, where each
+ * is centred and how wide it is: the list iqd_channelizer_set_channels wants.  Every quantity is an unsigned integer and
+ * every step is fixed here, so results are exact; there are no floats.
+ *
+ *   input     power[n_rows][N] uint32 in device memory: a row is what iqd_spectrum_run* wrote for one (source, block), but
+ *             any values up to 2^32 - 1 are legal.  N = n_bins: 64, 128, 256, 512, 1024 or 2048.  Rows are independent: no
+ *             state, no history, no reset.
+ *   config    floor_rank r, 0 <= r < N;  ratio_q8 Q, 256 <= Q <= 2^24;  dc_guard d, 0 <= d <= N / 4;  bridge g, 0 <= g <= 64;
+ *             min_width m, 1 <= m <= N;  max_detections K, 1 <= K <= N / 2;  reserved[0] = 0.
+ *   floor     f = the r-th smallest of the row's N values, counted from 0, duplicates counted (r = N / 2: the upper
+ *             median).  Guard bins are part of this count.
+ *   threshold T = min(2^32 - 1, (max(f, 1) Q) >> 8), the product in 64 bits.
+ *   hot       bin k is hot iff p[k] > T (strictly) and not (N / 2 - d < k < N / 2 + d): d = 0 guards nothing, d = 1 the centre
+ *             bin only (an RTL-SDR's DC spike).
+ *   runs      two hot bins i < j with no hot bin between them belong to one run iff j - i - 1 <= g; guard bins count as not
+ *             hot; runs do not wrap from bin N - 1 to bin 0.  first / last: the run's lowest / highest hot bin,
+ *             width = last - first + 1.  Runs of width < m are dropped and count nowhere.
+ *   per run   over its hot bins only (a bridged gap or a guarded spike inside a run adds nothing): n_hot their number,
+ *             peak_power the largest p, peak_bin the lowest bin that has it, sum_power = sum p (uint64),
+ *             centroid_q8 = floor(256 sum k p[k] / sum p[k]), k the absolute bin.  sum p >= 1 (hot is p > T >= 0),
+ *             sum k p < 2^54 and its 256-fold < 2^62: 64 bits hold them.
+ *   output    rows[n_rows]: floor, threshold, n_found (every kept run, those past K too), n_hot_bins (every hot bin of
+ *             the row, those of dropped runs too).  det[n_rows][K], ascending first_bin: the first min(n_found, K)
+ *             records are the runs, the rest of the row's K records are all-zero bytes - both arrays are defined in full
+ *             after a call.
+ *   offset    iqd_detect_offset_hz(N, rate, centroid_q8): hz = floor(((centroid_q8 - 128 N) rate + 128 N) / (256 N)), floor
+ *             also for negative numerators, in 64 bits: the offset from the capture's centre that iqd_channelizer_tuning
+ *             takes (station = centre + hz).  Host only, no GPU.  IQD_EINVAL: hz NULL, N outside the set, rate 0,
+ *             centroid_q8 >= 256 N.
+ *   refusals  IQD_EINVAL with a message naming the argument, before anything is allocated or queued: a NULL pointer, a
+ *             field outside its range, a non-zero reserved word; at run: n_rows 0 or above 2^31 - 1 (what one launch
+ *             covers), a NULL or misaligned device pointer.
+ * power_dev, rows_dev, det_dev: device memory, 16-byte aligned.  The _device form is queued on the engine's stream - straight
+ * behind the iqd_spectrum_run_device that writes power_dev, with no synchronisation between them - and returns once queued;
+ * the host form takes host pointers and returns when done. */
+typedef struct iqd_detect_config {
+    uint32_t n_bins;          /* N */
+    uint32_t floor_rank;      /* r */
+    uint32_t ratio_q8;        /* Q: the threshold over the floor, 256 = 1.0 */
+    uint32_t dc_guard;        /* d */
+    uint32_t bridge;          /* g */
+    uint32_t min_width;       /* m */
+    uint32_t max_detections;  /* K */
+    uint32_t reserved[1];     /* 0 */
+} iqd_detect_config;
+typedef struct iqd_detect_row {
+    uint32_t floor, threshold, n_found, n_hot_bins;
+} iqd_detect_row;
+typedef struct iqd_detection {
+    uint32_t first_bin, last_bin, peak_bin, peak_power;
+    uint64_t sum_power;
+    uint32_t centroid_q8, n_hot;
+} iqd_detection;
+typedef struct iqd_detect iqd_detect_t;
+int iqd_detect_create(iqd_t *e, const iqd_detect_config *cfg, iqd_detect_t **out);
+void iqd_detect_destroy(iqd_detect_t *d);   /* before its engine's iqd_destroy */
+int iqd_detect_run_device(iqd_detect_t *d, const uint32_t *power_dev, size_t n_rows, iqd_detect_row *rows_dev,
+                          iqd_detection *det_dev);
+int iqd_detect_run(iqd_detect_t *d, const uint32_t *power, size_t n_rows, iqd_detect_row *rows, iqd_detection *det);
+int iqd_detect_offset_hz(uint32_t n_bins, uint32_t rate_hz, uint32_t centroid_q8, int64_t *hz);
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

@@ -52,6 +52,17 @@ class SpectrumConfig(C.Structure):
                 ("sample_format", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class DetectConfig(C.Structure):
+    _fields_ = [("n_bins", C.c_uint32), ("floor_rank", C.c_uint32), ("ratio_q8", C.c_uint32), ("dc_guard", C.c_uint32),
+                ("bridge", C.c_uint32), ("min_width", C.c_uint32), ("max_detections", C.c_uint32), ("reserved", C.c_uint32 * 1)]
+
+
+# iqd_detect_row and iqd_detection (include/iqdemod.h: "Band activity") as numpy structured dtypes, 16 and 32 bytes
+DETECT_ROW = np.dtype([("floor", "<u4"), ("threshold", "<u4"), ("n_found", "<u4"), ("n_hot_bins", "<u4")])
+DETECTION = np.dtype([("first_bin", "<u4"), ("last_bin", "<u4"), ("peak_bin", "<u4"), ("peak_power", "<u4"),
+                      ("sum_power", "<u8"), ("centroid_q8", "<u4"), ("n_hot", "<u4")])
+
+
 class IqdError(RuntimeError):
     def __init__(self, status, detail):
         super().__init__("libiqdemod: %s (%d): %s" % (_lib().iqd_strerror(status).decode(), status, detail))
@@ -81,6 +92,7 @@ EXPORTS = [
     "iqd_filter_run_device", "iqd_filter_tile_samples", "iqd_filter_clamp_free_taps",
     "iqd_spectrum_create", "iqd_spectrum_destroy", "iqd_spectrum_run_device", "iqd_spectrum_run",
     "iqd_spectrum_default_window", "iqd_spectrum_full_scale",
+    "iqd_detect_create", "iqd_detect_destroy", "iqd_detect_run_device", "iqd_detect_run", "iqd_detect_offset_hz",
 ]
 
 _LIB = None
@@ -196,6 +208,12 @@ def _lib():
     L.iqd_spectrum_run.argtypes = [vp, vp, sz, u32, vp]
     L.iqd_spectrum_default_window.argtypes = [u32, vp]
     L.iqd_spectrum_full_scale.argtypes = [vp, u32, C.POINTER(u32)]
+    L.iqd_detect_create.argtypes = [vp, C.POINTER(DetectConfig), C.POINTER(vp)]
+    L.iqd_detect_destroy.argtypes = [vp]
+    L.iqd_detect_destroy.restype = None
+    L.iqd_detect_run_device.argtypes = [vp, vp, sz, vp, vp]
+    L.iqd_detect_run.argtypes = [vp, vp, sz, vp, vp]
+    L.iqd_detect_offset_hz.argtypes = [u32, u32, u32, C.POINTER(C.c_int64)]
     _LIB = L
     return L
 
@@ -888,6 +906,66 @@ class Spectrum:
         """iqd_spectrum_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
         if self._h and self._e._h:
             self._L.iqd_spectrum_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+
+def detect_offset_hz(n_bins, rate_hz, centroid_q8):
+    """iqd_detect_offset_hz (host only, no GPU): a detection's centroid as the offset in Hz from the capture's centre,
+    floor(((centroid_q8 - 128 N) rate + 128 N) / (256 N)) - what channelizer_tuning takes as station - centre."""
+    hz = C.c_int64()
+    args = [int(v) for v in (n_bins, rate_hz, centroid_q8)]
+    if any(v < 0 or v > 0xffffffff for v in args) or _lib().iqd_detect_offset_hz(*args, C.byref(hz)) != 0:
+        raise IqdError(-1, "iqd_detect_offset_hz: n_bins %r, rate_hz %r or centroid_q8 %r out of range" % (n_bins, rate_hz, centroid_q8))
+    return hz.value
+
+
+class Detector:
+    """iqd_detect_*: the occupied runs of band spectrum rows of n_bins bins (64 .. 2048, a power of two).  floor_rank: which
+    of the row's sorted values is the noise floor (None: n_bins / 2, the upper median); ratio_q8: the threshold over it
+    (256 = 1.0); dc_guard: bins N / 2 - d < k < N / 2 + d never count; bridge: the gap two hot bins of one run may have;
+    min_width: narrower runs are dropped; max_detections: records per row."""
+
+    def __init__(self, engine, n_bins, floor_rank=None, ratio_q8=2048, dc_guard=1, bridge=8, min_width=3, max_detections=16):
+        self._e, self._L = engine, engine._L
+        self._h = None
+        self.n_bins, self.max_detections = int(n_bins), int(max_detections)
+        rank = self.n_bins // 2 if floor_rank is None else int(floor_rank)
+        cfg = DetectConfig(*[int(v) & 0xffffffff for v in (n_bins, rank, ratio_q8, dc_guard, bridge, min_width, max_detections)])
+        h = C.c_void_p()
+        engine._check(self._L.iqd_detect_create(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        if not hasattr(engine, "_children"):
+            engine._children = weakref.WeakSet()
+        engine._children.add(self)
+
+    def run(self, power):
+        """[..., n_bins] uint32 (host array; a Spectrum.run result as it is) -> (rows [n_rows] DETECT_ROW,
+        det [n_rows, max_detections] DETECTION), n_rows the product of the leading dimensions."""
+        if getattr(power, "dtype", None) != np.uint32:
+            raise TypeError("the power rows are uint32, not %s" % getattr(power, "dtype", type(power)))
+        power = np.ascontiguousarray(power).reshape(-1, self.n_bins)
+        rows = np.zeros(len(power), DETECT_ROW)
+        det = np.zeros((len(power), self.max_detections), DETECTION)
+        src = power if power.size else np.zeros(4, np.uint32)     # (a refused call gets valid pointers all the same)
+        self._e._check(self._L.iqd_detect_run(self._h, _np_ptr(src), len(power), _np_ptr(rows if len(power) else np.zeros(1, DETECT_ROW)),
+                                              _np_ptr(det if len(power) else np.zeros(1, DETECTION))))
+        return rows, det
+
+    def run_device(self, power_dev, n_rows, rows_dev, det_dev):
+        """iqd_detect_run_device: device pointers (integers), queued on the engine's stream."""
+        self._e._check(self._L.iqd_detect_run_device(self._h, C.c_void_p(power_dev or None), int(n_rows),
+                                                     C.c_void_p(rows_dev or None), C.c_void_p(det_dev or None)))
+
+    def offset_hz(self, rate_hz, centroid_q8):
+        """detect_offset_hz for this detector's n_bins"""
+        return detect_offset_hz(self.n_bins, rate_hz, centroid_q8)
+
+    def close(self):
+        """iqd_detect_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
+        if self._h and self._e._h:
+            self._L.iqd_detect_destroy(self._h)
         self._h = None
 
     __del__ = close

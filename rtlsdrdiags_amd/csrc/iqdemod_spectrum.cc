@@ -2,6 +2,7 @@
 // iqd_spectrum_*): what a user looks at before placing survey points or channels.
 //
 //   iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] out=power.u32 [log=spectrum.txt]
+//                    [detect=runs.txt [rank=512] [ratio_q8=2048] [guard=1] [bridge=8] [minwidth=3] [maxdet=16]]
 //
 //   in       interleaved I/Q, one byte per rail
 //   rate     the capture's sample rate in Hz (for the log's offsets only)
@@ -11,6 +12,12 @@
 //   window   a text file of N int16 values separated by white space or commas; left out: the library's default window
 //   out      the API's array, block after block: N little-endian uint32 per block
 //   log      one line per block and bin: block, offset in Hz ((k' - N / 2) rate / N), power, dBFS
+//   detect   the occupied runs of every block (include/iqdemod.h: "Band activity"), one line per detection: block, the
+//            offsets in Hz of its first bin, its last bin and its centroid (iqd_detect_offset_hz), the peak in dBFS,
+//            sum_power.  The detector runs on the device straight behind the spectrum, on the same stream.  rate must be
+//            a whole number of Hz then.
+//   rank ratio_q8 guard bridge minwidth maxdet   iqd_detect_config's floor_rank (left out: bins / 2), ratio_q8, dc_guard,
+//            bridge, min_width, max_detections; runs past maxdet per block are counted on stderr
 // A capture that ends inside a block ends with its last whole block; the rest is dropped and counted on stderr.
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
 #include <math.h>
@@ -48,9 +55,16 @@ bool readWindow(const std::string &path, std::vector<int16_t> &v)
 
 int main(int argc, char **argv)
 {
-  std::string in, out, log, windowPath, format = "u8";
+  std::string in, out, log, windowPath, detectPath, format = "u8";
   double rate = 0.0;
   uint32_t bins = 0, frames = 0;
+  iqd_detect_config dc{};
+  dc.ratio_q8 = 2048;
+  dc.dc_guard = 1;
+  dc.bridge = 8;
+  dc.min_width = 3;
+  dc.max_detections = 16;
+  bool rankGiven = false;
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
     if (!strncmp(a, "in=", 3)) in = a + 3;
@@ -61,6 +75,13 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "rate=", 5)) rate = strtod(a + 5, nullptr);
     else if (!strncmp(a, "bins=", 5)) bins = (uint32_t)strtoul(a + 5, nullptr, 10);
     else if (!strncmp(a, "frames=", 7)) frames = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "detect=", 7)) detectPath = a + 7;
+    else if (!strncmp(a, "rank=", 5)) { dc.floor_rank = (uint32_t)strtoul(a + 5, nullptr, 10); rankGiven = true; }
+    else if (!strncmp(a, "ratio_q8=", 9)) dc.ratio_q8 = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "guard=", 6)) dc.dc_guard = (uint32_t)strtoul(a + 6, nullptr, 10);
+    else if (!strncmp(a, "bridge=", 7)) dc.bridge = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "minwidth=", 9)) dc.min_width = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "maxdet=", 7)) dc.max_detections = (uint32_t)strtoul(a + 7, nullptr, 10);
     else {
       fprintf(stderr, "iqdemod_spectrum: unknown argument %s\n", a);
       return 1;
@@ -69,7 +90,12 @@ int main(int argc, char **argv)
   const bool u8 = format == "u8";
   if (in.empty() || out.empty() || bins == 0 || frames == 0 || frames > (1u << 24) || !(rate > 0.0) || (!u8 && format != "s8")) {
     fprintf(stderr, "usage: iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] "
-                    "out=power.u32 [log=spectrum.txt]\n");
+                    "out=power.u32 [log=spectrum.txt] [detect=runs.txt [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=]]\n");
+    return 1;
+  }
+  const bool detect = !detectPath.empty();
+  if (detect && (rate != floor(rate) || rate > 4294967295.0)) {
+    fprintf(stderr, "iqdemod_spectrum: detect= needs rate as a whole number of Hz below 2^32\n");
     return 1;
   }
   std::vector<int16_t> window;
@@ -80,7 +106,8 @@ int main(int argc, char **argv)
   FILE *fin = fopen(in.c_str(), "rb");
   FILE *fout = fin ? fopen(out.c_str(), "wb") : nullptr;
   FILE *flog = fout && !log.empty() ? fopen(log.c_str(), "w") : nullptr;
-  if (!fin || !fout || (!log.empty() && !flog)) {
+  FILE *fdet = fout && detect ? fopen(detectPath.c_str(), "w") : nullptr;
+  if (!fin || !fout || (!log.empty() && !flog) || (detect && !fdet)) {
     fprintf(stderr, "iqdemod_spectrum: cannot open the files\n");
     return 1;
   }
@@ -110,22 +137,62 @@ int main(int argc, char **argv)
     return 1;
   }
 
+  iqd_detect_t *d = nullptr;
+  if (detect) {
+    dc.n_bins = bins;
+    if (!rankGiven) dc.floor_rank = bins / 2;
+    rc = iqd_detect_create(e, &dc, &d);
+    if (rc != IQD_OK) {
+      fprintf(stderr, "iqdemod_spectrum: iqd_detect_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      iqd_spectrum_destroy(s);
+      iqd_destroy(e);
+      return 1;
+    }
+  }
+
   // whole blocks, up to about 16 MiB of capture per call
   const size_t blockBytes = (size_t)2 * bins * frames;
   const size_t perCall = blockBytes >= (16u << 20) ? 1 : (16u << 20) / blockBytes;
   std::vector<uint8_t> buf(perCall * blockBytes);
   std::vector<uint32_t> power(perCall * bins);
   int status = 0;
-  uint64_t block = 0;
+  uint64_t block = 0, pastMax = 0;
   size_t dropped = 0;
+  // detect=: the capture, the power rows and the detector's two arrays stay on the device from one call to the next
+  std::vector<iqd_detect_row> rows(detect ? perCall : 0);
+  std::vector<iqd_detection> dets(detect ? perCall * dc.max_detections : 0);
+  void *wideDev = nullptr, *powerDev = nullptr, *rowsDev = nullptr, *detDev = nullptr;
+  if (detect) {
+    rc = iqd_dev_alloc(e, buf.size(), &wideDev);
+    if (rc == IQD_OK) rc = iqd_dev_alloc(e, power.size() * sizeof(uint32_t), &powerDev);
+    if (rc == IQD_OK) rc = iqd_dev_alloc(e, rows.size() * sizeof(iqd_detect_row), &rowsDev);
+    if (rc == IQD_OK) rc = iqd_dev_alloc(e, dets.size() * sizeof(iqd_detection), &detDev);
+    if (rc != IQD_OK) {
+      fprintf(stderr, "iqdemod_spectrum: iqd_dev_alloc: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      iqd_detect_destroy(d);
+      iqd_spectrum_destroy(s);
+      iqd_destroy(e);
+      return 1;
+    }
+  }
   for (;;) {
     const size_t got = fread(buf.data(), 1, buf.size(), fin);
     const size_t nb = got / blockBytes;
     dropped = got - nb * blockBytes;
     if (nb) {
-      rc = iqd_spectrum_run(s, buf.data(), nb * blockBytes, frames, power.data());
+      if (!detect) {
+        rc = iqd_spectrum_run(s, buf.data(), nb * blockBytes, frames, power.data());
+      } else {
+        // spectrum and detector queued back to back on the engine's stream; the host sees the results after both
+        rc = iqd_dev_upload(e, wideDev, buf.data(), nb * blockBytes);
+        if (rc == IQD_OK) rc = iqd_spectrum_run_device(s, wideDev, nb * blockBytes, frames, (uint32_t *)powerDev);
+        if (rc == IQD_OK) rc = iqd_detect_run_device(d, (const uint32_t *)powerDev, nb, (iqd_detect_row *)rowsDev, (iqd_detection *)detDev);
+        if (rc == IQD_OK) rc = iqd_dev_download(e, power.data(), powerDev, nb * bins * sizeof(uint32_t));
+        if (rc == IQD_OK) rc = iqd_dev_download(e, rows.data(), rowsDev, nb * sizeof(iqd_detect_row));
+        if (rc == IQD_OK) rc = iqd_dev_download(e, dets.data(), detDev, nb * dc.max_detections * sizeof(iqd_detection));
+      }
       if (rc != IQD_OK) {
-        fprintf(stderr, "iqdemod_spectrum: iqd_spectrum_run: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", detect ? "spectrum and detector" : "iqd_spectrum_run", iqd_strerror(rc), iqd_last_error(e));
         status = 3;
         break;
       }
@@ -140,15 +207,32 @@ int main(int argc, char **argv)
           fprintf(flog, "%llu %.3f %u %.2f\n", (unsigned long long)(block + b), ((double)k - bins / 2) * rate / bins, p,
                   10.0 * log10((double)(p ? p : 1) / (double)(pfs ? pfs : 1)));
         }
+      for (size_t b = 0; detect && b < nb; b++) {
+        const uint32_t found = rows[b].n_found, shown = found < dc.max_detections ? found : dc.max_detections;
+        pastMax += found - shown;
+        for (uint32_t i = 0; i < shown; i++) {
+          const iqd_detection &r = dets[b * dc.max_detections + i];
+          int64_t hz = 0;
+          iqd_detect_offset_hz(bins, (uint32_t)rate, r.centroid_q8, &hz);
+          fprintf(fdet, "%llu %.3f %.3f %lld %.2f %llu\n", (unsigned long long)(block + b), ((double)r.first_bin - bins / 2) * rate / bins,
+                  ((double)r.last_bin - bins / 2) * rate / bins, (long long)hz,
+                  10.0 * log10((double)(r.peak_power ? r.peak_power : 1) / (double)(pfs ? pfs : 1)), (unsigned long long)r.sum_power);
+        }
+      }
       block += nb;
     }
     if (got < buf.size()) break;
   }
   if (dropped) fprintf(stderr, "iqdemod_spectrum: %zu bytes after the last whole block dropped\n", dropped);
+  if (pastMax) fprintf(stderr, "iqdemod_spectrum: %llu runs past maxdet not written\n", (unsigned long long)pastMax);
+  for (void *p : {wideDev, powerDev, rowsDev, detDev})
+    if (p) iqd_dev_free(e, p);
+  iqd_detect_destroy(d);
   iqd_spectrum_destroy(s);
   iqd_destroy(e);
   fclose(fin);
   if (fclose(fout) != 0) status = status ? status : 1;
   if (flog && fclose(flog) != 0) status = status ? status : 1;
+  if (fdet && fclose(fdet) != 0) status = status ? status : 1;
   return status;
 }
