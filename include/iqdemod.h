@@ -681,6 +681,101 @@ int iqd_detect_run_device(iqd_detect_t *d, const uint32_t *power_dev, size_t n_r
 int iqd_detect_run(iqd_detect_t *d, const uint32_t *power, size_t n_rows, iqd_detect_row *rows, iqd_detection *det);
 int iqd_detect_offset_hz(uint32_t n_bins, uint32_t rate_hz, uint32_t centroid_q8, int64_t *hz);
 
+/* Band tracks: the detector's runs followed from block to block - a stateful object behind iqd_detect_run_device on the same
+ * stream.  For every (source, block) it writes S fixed slots, each a track with an identity that persists from block to
+ * block and from call to call, hysteresis (a track opens after H hits and is held over B misses), a smoothed centre, the
+ * exact channelizer phase_inc of that centre and a width class.  Slot s of source j is meant to be channelizer channel
+ * j S + s: the host reads one block's slots and hands their phase_inc column to iqd_channelizer_set_channels.  Every quantity
+ * is an integer and every step is fixed here, so results are exact; there are no floats.
+ *
+ *   input     the detector's two arrays for n_sources x n_blocks rows, in the spectrum's row order: rows_dev[n_sources][n_blocks]
+ *             and det_dev[n_sources][n_blocks][K].  Of a row only n_found and the first D = min(n_found, K) records are read
+ *             (of a record: first_bin, last_bin, peak_power, centroid_q8, which must be what the detector writes:
+ *             first_bin <= last_bin < N, centroid_q8 < 256 N); the bytes past them may be anything.
+ *   state     per source: the S slots as they stand after the last block, and next_id.  It persists across calls until
+ *             iqd_track_reset (all slots all-zero bytes, next_id 0).  Sources are independent; the blocks of a source are
+ *             processed in order.  One call of b1 + b2 blocks gives what a call of b1 blocks followed by one of b2 blocks gives.
+ *   a block   G = gate_q8, H = open_hits, B = hold_blocks, A = alpha_q8; a slot is live iff state != 0, free iff state == 0.
+ *     0 clear     every slot's flags become 0; a slot whose state is 0 (one that closed in the previous block) becomes
+ *                 all-zero bytes.
+ *     1 match     for detection i = 0 .. D - 1 in that order, c = det[i].centroid_q8: among the slots that are live, not yet
+ *                 matched in this block and have |centre_q8 - c| <= G - centre_q8 as it stood when the block began - the one
+ *                 with the least distance, on a tie the lowest slot index, is matched to detection i.  If there is none,
+ *                 detection i is unmatched.
+ *     2 update    every matched slot, from its detection: centre_q8 += ((c - centre_q8) A) >> 8, >> arithmetic (the floor
+ *                 also for negative differences; |c - centre_q8| A < 2^27, and the result lies between the old centre and c,
+ *                 so in [0, 256 N)); first_bin, last_bin, peak_power are the detection's;
+ *                 max_width = max(max_width, last_bin - first_bin + 1); hits = min(hits + 1, 255); misses = 0; flag matched;
+ *                 if state is 1 and hits >= H: state 2, flag opened.
+ *     3 age       every slot that was live when the block began: age_blocks += 1 (mod 2^32).  If it was not matched:
+ *                 misses += 1; a tentative slot (state 1) then becomes all-zero bytes at once; an active slot (state 2) with
+ *                 misses > B gets state 0 and flag closed and keeps its other fields for this block's record only
+ *                 (misses is stored mod 2^16: B = 65535 closes at a stored 0).
+ *     4 allocate  the unmatched detections, in ascending i, take the lowest-index slots that were free when the block began
+ *                 (after step 0); a slot freed or closed in this block is not available until the next block.
+ *                 track_id = ++next_id (per source, mod 2^32); state 1 - or 2 with flag opened when H = 1; flags new and
+ *                 matched; hits 1, misses 0, centre_q8 = c, age_blocks 0; first_bin, last_bin, peak_power the detection's,
+ *                 max_width = last_bin - first_bin + 1.  A detection that finds no slot left counts in the block's n_unplaced.
+ *     5 derive    every slot with track_id != 0:
+ *                 phase_inc = (uint32)((centre_q8 - 128 N) 2^(24 - log2 N)) + inc_bias (mod 2^32): as a signed fraction of
+ *                 2^32 exactly (centre_q8 / 256 - N / 2) / N of the wide rate, whatever the rate - what
+ *                 iqd_channelizer_set_channels takes; |centre_q8 - 128 N| <= 2^18 at N = 2048 times 2^13, and so for every N
+ *                 the product lies in [-2^31, 2^31).  width_class = the number of j with max_width >= class_edge[j].
+ *   output    slots_dev[n_sources][n_blocks][S]: every slot as it stands after the block; blocks_dev[n_sources][n_blocks]:
+ *             n_active and n_tentative after the block, the slots with flag opened | those with flag closed << 16, and the
+ *             block's unplaced detections.  Both arrays are defined in full after a call.
+ *   state, flags   state 0 free, 1 tentative, 2 active.  flags bit 0 matched this block, bit 1 new this block, bit 2 opened
+ *             this block (became active), bit 3 closed this block.
+ *   phase_inc iqd_track_phase_inc(N, centroid_q8, inc_bias): step 5's rule on the host, no GPU.  IQD_EINVAL: inc NULL, N outside
+ *             the set, centroid_q8 >= 256 N.
+ *   refusals  IQD_EINVAL with a message naming the argument, before anything is allocated or queued: a NULL pointer, a field
+ *             outside its range, a non-zero reserved word; at run: n_blocks 0, n_sources n_blocks above 2^31 - 1, a NULL or
+ *             misaligned device pointer; get_state: source >= n_sources.
+ * rows_dev, det_dev, slots_dev, blocks_dev: device memory, 16-byte aligned.  The _device form is queued on the engine's stream
+ * - straight behind the iqd_detect_run_device that writes its input - and returns once queued; the host form takes host
+ * pointers and returns when done; iqd_track_get_state synchronises; iqd_track_reset is queued. */
+typedef struct iqd_track_config {
+    uint32_t n_sources;       /* >= 1 */
+    uint32_t n_bins;          /* N: 64 ... 2048, the detector's */
+    uint32_t max_detections;  /* K: 1 ... N / 2, the detector's */
+    uint32_t n_slots;         /* S: 1 ... 64 */
+    uint32_t gate_q8;         /* G: 0 ... 256 N - 1 */
+    uint32_t open_hits;       /* H: 1 ... 255 */
+    uint32_t hold_blocks;     /* B: 0 ... 65535 */
+    uint32_t alpha_q8;        /* A: 1 ... 256 (256: the centre follows the detection) */
+    uint32_t inc_bias;        /* added to every phase_inc mod 2^32 (e.g. the +64 kHz of "station + Fs/4") */
+    uint32_t class_edge[3];   /* 1 <= e0 <= e1 <= e2 <= N + 1 (N + 1 is never reached) */
+    uint32_t reserved[4];     /* 0 */
+} iqd_track_config;
+typedef struct iqd_track_slot {     /* 32 bytes */
+    uint32_t track_id;              /* 0: free.  Per source, counted from 1 in order of allocation, mod 2^32 */
+    uint8_t  state, flags, hits, width_class;
+    uint16_t misses, max_width;
+    uint32_t centre_q8, phase_inc;
+    uint16_t first_bin, last_bin;
+    uint32_t peak_power, age_blocks;
+} iqd_track_slot;
+typedef struct iqd_track_block {
+    uint32_t n_active, n_tentative, n_opened_closed /* opened | closed << 16 */, n_unplaced;
+} iqd_track_block;
+#define IQD_TRACK_FREE 0
+#define IQD_TRACK_TENTATIVE 1
+#define IQD_TRACK_ACTIVE 2
+#define IQD_TRACK_F_MATCHED 1
+#define IQD_TRACK_F_NEW 2
+#define IQD_TRACK_F_OPENED 4
+#define IQD_TRACK_F_CLOSED 8
+typedef struct iqd_track iqd_track_t;
+int iqd_track_create(iqd_t *e, const iqd_track_config *cfg, iqd_track_t **out);
+void iqd_track_destroy(iqd_track_t *t);   /* before its engine's iqd_destroy */
+int iqd_track_reset(iqd_track_t *t);
+int iqd_track_run_device(iqd_track_t *t, const iqd_detect_row *rows_dev, const iqd_detection *det_dev, size_t n_blocks,
+                         iqd_track_slot *slots_dev, iqd_track_block *blocks_dev);
+int iqd_track_run(iqd_track_t *t, const iqd_detect_row *rows, const iqd_detection *det, size_t n_blocks, iqd_track_slot *slots,
+                  iqd_track_block *blocks);
+int iqd_track_get_state(iqd_track_t *t, uint32_t source, iqd_track_slot *out /* [S] */);
+int iqd_track_phase_inc(uint32_t n_bins, uint32_t centroid_q8, uint32_t inc_bias, uint32_t *inc);
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

@@ -57,10 +57,23 @@ class DetectConfig(C.Structure):
                 ("bridge", C.c_uint32), ("min_width", C.c_uint32), ("max_detections", C.c_uint32), ("reserved", C.c_uint32 * 1)]
 
 
+class TrackConfig(C.Structure):
+    _fields_ = [("n_sources", C.c_uint32), ("n_bins", C.c_uint32), ("max_detections", C.c_uint32), ("n_slots", C.c_uint32),
+                ("gate_q8", C.c_uint32), ("open_hits", C.c_uint32), ("hold_blocks", C.c_uint32), ("alpha_q8", C.c_uint32),
+                ("inc_bias", C.c_uint32), ("class_edge", C.c_uint32 * 3), ("reserved", C.c_uint32 * 4)]
+
+
 # iqd_detect_row and iqd_detection (include/iqdemod.h: "Band activity") as numpy structured dtypes, 16 and 32 bytes
 DETECT_ROW = np.dtype([("floor", "<u4"), ("threshold", "<u4"), ("n_found", "<u4"), ("n_hot_bins", "<u4")])
 DETECTION = np.dtype([("first_bin", "<u4"), ("last_bin", "<u4"), ("peak_bin", "<u4"), ("peak_power", "<u4"),
                       ("sum_power", "<u8"), ("centroid_q8", "<u4"), ("n_hot", "<u4")])
+
+
+# iqd_track_slot and iqd_track_block (include/iqdemod.h: "Band tracks"), 32 and 16 bytes
+TRACK_SLOT = np.dtype([("track_id", "<u4"), ("state", "u1"), ("flags", "u1"), ("hits", "u1"), ("width_class", "u1"),
+                       ("misses", "<u2"), ("max_width", "<u2"), ("centre_q8", "<u4"), ("phase_inc", "<u4"),
+                       ("first_bin", "<u2"), ("last_bin", "<u2"), ("peak_power", "<u4"), ("age_blocks", "<u4")])
+TRACK_BLOCK = np.dtype([("n_active", "<u4"), ("n_tentative", "<u4"), ("n_opened_closed", "<u4"), ("n_unplaced", "<u4")])
 
 
 class IqdError(RuntimeError):
@@ -93,6 +106,8 @@ EXPORTS = [
     "iqd_spectrum_create", "iqd_spectrum_destroy", "iqd_spectrum_run_device", "iqd_spectrum_run",
     "iqd_spectrum_default_window", "iqd_spectrum_full_scale",
     "iqd_detect_create", "iqd_detect_destroy", "iqd_detect_run_device", "iqd_detect_run", "iqd_detect_offset_hz",
+    "iqd_track_create", "iqd_track_destroy", "iqd_track_reset", "iqd_track_run_device", "iqd_track_run", "iqd_track_get_state",
+    "iqd_track_phase_inc",
 ]
 
 _LIB = None
@@ -214,6 +229,14 @@ def _lib():
     L.iqd_detect_run_device.argtypes = [vp, vp, sz, vp, vp]
     L.iqd_detect_run.argtypes = [vp, vp, sz, vp, vp]
     L.iqd_detect_offset_hz.argtypes = [u32, u32, u32, C.POINTER(C.c_int64)]
+    L.iqd_track_create.argtypes = [vp, C.POINTER(TrackConfig), C.POINTER(vp)]
+    L.iqd_track_destroy.argtypes = [vp]
+    L.iqd_track_destroy.restype = None
+    L.iqd_track_reset.argtypes = [vp]
+    L.iqd_track_run_device.argtypes = [vp, vp, vp, sz, vp, vp]
+    L.iqd_track_run.argtypes = [vp, vp, vp, sz, vp, vp]
+    L.iqd_track_get_state.argtypes = [vp, u32, vp]
+    L.iqd_track_phase_inc.argtypes = [u32, u32, u32, C.POINTER(u32)]
     _LIB = L
     return L
 
@@ -966,6 +989,89 @@ class Detector:
         """iqd_detect_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
         if self._h and self._e._h:
             self._L.iqd_detect_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+
+def track_phase_inc(n_bins, centroid_q8, inc_bias=0):
+    """iqd_track_phase_inc (host only, no GPU): the channelizer phase_inc of a centre in 1/256 bins,
+    (uint32)((centroid_q8 - 128 N) 2^(24 - log2 N)) + inc_bias mod 2^32 - what Channelizer.set_channels takes."""
+    inc = C.c_uint32()
+    args = [int(v) for v in (n_bins, centroid_q8, inc_bias)]
+    if any(v < 0 or v > 0xffffffff for v in args) or _lib().iqd_track_phase_inc(*args, C.byref(inc)) != 0:
+        raise IqdError(-1, "iqd_track_phase_inc: n_bins %r or centroid_q8 %r out of range" % (n_bins, centroid_q8))
+    return inc.value
+
+
+def track_default_edges(n_bins):
+    """the width classes used where none are given: runs of at least 1/64, 1/16 and 1/4 of the band (and of 2 bins)"""
+    n = int(n_bins)
+    return (max(n // 64, 1) + 1, max(n // 16, 2), max(n // 4, 2))
+
+
+class Tracker:
+    """iqd_track_*: the detector's runs followed from block to block - n_slots fixed slots per source, each a track with a
+    persistent id, hysteresis (open after open_hits hits, held over hold_blocks misses), a centre smoothed by alpha_q8 / 256,
+    its exact phase_inc (plus inc_bias) and a width class (class_edge: three widths in bins).  n_bins and max_detections
+    are the Detector's.  State is carried from call to call until reset()."""
+
+    def __init__(self, engine, n_bins, n_sources=1, max_detections=16, n_slots=8, gate_q8=512, open_hits=3, hold_blocks=2,
+                 alpha_q8=64, inc_bias=0, class_edge=None):
+        self._e, self._L = engine, engine._L
+        self._h = None
+        self.n_bins, self.n_sources, self.max_detections, self.n_slots = int(n_bins), int(n_sources), int(max_detections), int(n_slots)
+        edges = track_default_edges(n_bins) if class_edge is None else tuple(int(v) for v in class_edge)
+        if len(edges) != 3:
+            raise ValueError("class_edge must have three entries")
+        cfg = TrackConfig(*[int(v) & 0xffffffff for v in (n_sources, n_bins, max_detections, n_slots, gate_q8, open_hits, hold_blocks,
+                                                          alpha_q8, inc_bias)])
+        for i in range(3):
+            cfg.class_edge[i] = edges[i] & 0xffffffff
+        h = C.c_void_p()
+        engine._check(self._L.iqd_track_create(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        if not hasattr(engine, "_children"):
+            engine._children = weakref.WeakSet()
+        engine._children.add(self)
+
+    def run(self, rows, det):
+        """rows [n_sources, n_blocks] DETECT_ROW and det [n_sources, n_blocks, max_detections] DETECTION (host arrays; a
+        Detector.run result reshaped) -> (slots [n_sources, n_blocks, n_slots] TRACK_SLOT, blocks [n_sources, n_blocks]
+        TRACK_BLOCK)."""
+        if getattr(rows, "dtype", None) != DETECT_ROW or getattr(det, "dtype", None) != DETECTION:
+            raise TypeError("rows are DETECT_ROW and det DETECTION arrays")
+        rows = np.ascontiguousarray(rows).reshape(self.n_sources, -1)
+        nb = rows.shape[1]
+        det = np.ascontiguousarray(det).reshape(self.n_sources, nb, self.max_detections)
+        slots = np.zeros((self.n_sources, nb, self.n_slots), TRACK_SLOT)
+        blocks = np.zeros((self.n_sources, nb), TRACK_BLOCK)
+        one = np.zeros(64, np.uint8)                              # (a refused call gets valid pointers all the same)
+        self._e._check(self._L.iqd_track_run(self._h, _np_ptr(rows if nb else one), _np_ptr(det if nb else one), nb,
+                                             _np_ptr(slots if nb else one), _np_ptr(blocks if nb else one)))
+        return slots, blocks
+
+    def run_device(self, rows_dev, det_dev, n_blocks, slots_dev, blocks_dev):
+        """iqd_track_run_device: device pointers (integers), queued on the engine's stream."""
+        self._e._check(self._L.iqd_track_run_device(self._h, C.c_void_p(rows_dev or None), C.c_void_p(det_dev or None), int(n_blocks),
+                                                    C.c_void_p(slots_dev or None), C.c_void_p(blocks_dev or None)))
+
+    def reset(self):
+        """iqd_track_reset: every slot free, ids count from 1 again."""
+        self._e._check(self._L.iqd_track_reset(self._h))
+
+    def state(self, source=0):
+        """iqd_track_get_state: the source's n_slots slots as they stand after the last block (synchronises)."""
+        out = np.zeros(self.n_slots, TRACK_SLOT)
+        if not 0 <= int(source) <= 0xffffffff:
+            raise IqdError(-1, "iqd_track_get_state: source %r out of range" % (source,))
+        self._e._check(self._L.iqd_track_get_state(self._h, int(source), _np_ptr(out)))
+        return out
+
+    def close(self):
+        """iqd_track_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
+        if self._h and self._e._h:
+            self._L.iqd_track_destroy(self._h)
         self._h = None
 
     __del__ = close

@@ -2,7 +2,8 @@
 // iqd_spectrum_*): what a user looks at before placing survey points or channels.
 //
 //   iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] out=power.u32 [log=spectrum.txt]
-//                    [detect=runs.txt [rank=512] [ratio_q8=2048] [guard=1] [bridge=8] [minwidth=3] [maxdet=16]]
+//                    [detect=runs.txt [rank=512] [ratio_q8=2048] [guard=1] [bridge=8] [minwidth=3] [maxdet=16]
+//                     [track=tracks.txt [slots=8] [gate_q8=512] [open=3] [hold=2] [alpha_q8=64] [bias=0] [edges=a,b,c]]]
 //
 //   in       interleaved I/Q, one byte per rail
 //   rate     the capture's sample rate in Hz (for the log's offsets only)
@@ -18,6 +19,12 @@
 //            a whole number of Hz then.
 //   rank ratio_q8 guard bridge minwidth maxdet   iqd_detect_config's floor_rank (left out: bins / 2), ratio_q8, dc_guard,
 //            bridge, min_width, max_detections; runs past maxdet per block are counted on stderr
+//   track    needs detect=.  The tracker (include/iqdemod.h: "Band tracks") runs on the device behind the detector, on the
+//            same stream, with its state carried from one read of the file to the next.  One line per slot record that is
+//            live or closing: block, slot, id, state, flags, the centre's offset in Hz (iqd_detect_offset_hz), phase_inc as
+//            0x%08x, the offsets in Hz of its first and last bin, class.  Unplaced detections are counted on stderr.
+//   slots gate_q8 open hold alpha_q8 bias edges   iqd_track_config's n_slots, gate_q8, open_hits, hold_blocks, alpha_q8,
+//            inc_bias, class_edge (left out: bins / 64 + 1, bins / 16, bins / 4 bins)
 // A capture that ends inside a block ends with its last whole block; the rest is dropped and counted on stderr.
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
 #include <math.h>
@@ -55,7 +62,15 @@ bool readWindow(const std::string &path, std::vector<int16_t> &v)
 
 int main(int argc, char **argv)
 {
-  std::string in, out, log, windowPath, detectPath, format = "u8";
+  std::string in, out, log, windowPath, detectPath, trackPath, format = "u8";
+  iqd_track_config tc{};
+  tc.n_sources = 1;
+  tc.n_slots = 8;
+  tc.gate_q8 = 512;
+  tc.open_hits = 3;
+  tc.hold_blocks = 2;
+  tc.alpha_q8 = 64;
+  bool edgesGiven = false;
   double rate = 0.0;
   uint32_t bins = 0, frames = 0;
   iqd_detect_config dc{};
@@ -82,6 +97,20 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "bridge=", 7)) dc.bridge = (uint32_t)strtoul(a + 7, nullptr, 10);
     else if (!strncmp(a, "minwidth=", 9)) dc.min_width = (uint32_t)strtoul(a + 9, nullptr, 10);
     else if (!strncmp(a, "maxdet=", 7)) dc.max_detections = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "track=", 6)) trackPath = a + 6;
+    else if (!strncmp(a, "slots=", 6)) tc.n_slots = (uint32_t)strtoul(a + 6, nullptr, 10);
+    else if (!strncmp(a, "gate_q8=", 8)) tc.gate_q8 = (uint32_t)strtoul(a + 8, nullptr, 10);
+    else if (!strncmp(a, "open=", 5)) tc.open_hits = (uint32_t)strtoul(a + 5, nullptr, 10);
+    else if (!strncmp(a, "hold=", 5)) tc.hold_blocks = (uint32_t)strtoul(a + 5, nullptr, 10);
+    else if (!strncmp(a, "alpha_q8=", 9)) tc.alpha_q8 = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "bias=", 5)) tc.inc_bias = (uint32_t)strtoul(a + 5, nullptr, 0);
+    else if (!strncmp(a, "edges=", 6)) {
+      edgesGiven = sscanf(a + 6, "%u,%u,%u", &tc.class_edge[0], &tc.class_edge[1], &tc.class_edge[2]) == 3;
+      if (!edgesGiven) {
+        fprintf(stderr, "iqdemod_spectrum: edges= takes three widths in bins, a,b,c\n");
+        return 1;
+      }
+    }
     else {
       fprintf(stderr, "iqdemod_spectrum: unknown argument %s\n", a);
       return 1;
@@ -90,10 +119,15 @@ int main(int argc, char **argv)
   const bool u8 = format == "u8";
   if (in.empty() || out.empty() || bins == 0 || frames == 0 || frames > (1u << 24) || !(rate > 0.0) || (!u8 && format != "s8")) {
     fprintf(stderr, "usage: iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] "
-                    "out=power.u32 [log=spectrum.txt] [detect=runs.txt [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=]]\n");
+                    "out=power.u32 [log=spectrum.txt] [detect=runs.txt [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=] "
+                    "[track=tracks.txt [slots=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c]]]\n");
     return 1;
   }
-  const bool detect = !detectPath.empty();
+  const bool detect = !detectPath.empty(), track = !trackPath.empty();
+  if (track && !detect) {
+    fprintf(stderr, "iqdemod_spectrum: track= needs detect=\n");
+    return 1;
+  }
   if (detect && (rate != floor(rate) || rate > 4294967295.0)) {
     fprintf(stderr, "iqdemod_spectrum: detect= needs rate as a whole number of Hz below 2^32\n");
     return 1;
@@ -107,7 +141,8 @@ int main(int argc, char **argv)
   FILE *fout = fin ? fopen(out.c_str(), "wb") : nullptr;
   FILE *flog = fout && !log.empty() ? fopen(log.c_str(), "w") : nullptr;
   FILE *fdet = fout && detect ? fopen(detectPath.c_str(), "w") : nullptr;
-  if (!fin || !fout || (!log.empty() && !flog) || (detect && !fdet)) {
+  FILE *ftrk = fout && track ? fopen(trackPath.c_str(), "w") : nullptr;
+  if (!fin || !fout || (!log.empty() && !flog) || (detect && !fdet) || (track && !ftrk)) {
     fprintf(stderr, "iqdemod_spectrum: cannot open the files\n");
     return 1;
   }
@@ -150,6 +185,25 @@ int main(int argc, char **argv)
     }
   }
 
+  iqd_track_t *t = nullptr;
+  if (track) {
+    tc.n_bins = bins;
+    tc.max_detections = dc.max_detections;
+    if (!edgesGiven) {
+      tc.class_edge[0] = bins / 64 + 1;
+      tc.class_edge[1] = bins / 16;
+      tc.class_edge[2] = bins / 4;
+    }
+    rc = iqd_track_create(e, &tc, &t);
+    if (rc != IQD_OK) {
+      fprintf(stderr, "iqdemod_spectrum: iqd_track_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      iqd_detect_destroy(d);
+      iqd_spectrum_destroy(s);
+      iqd_destroy(e);
+      return 1;
+    }
+  }
+
   // whole blocks, up to about 16 MiB of capture per call
   const size_t blockBytes = (size_t)2 * bins * frames;
   const size_t perCall = blockBytes >= (16u << 20) ? 1 : (16u << 20) / blockBytes;
@@ -161,14 +215,20 @@ int main(int argc, char **argv)
   // detect=: the capture, the power rows and the detector's two arrays stay on the device from one call to the next
   std::vector<iqd_detect_row> rows(detect ? perCall : 0);
   std::vector<iqd_detection> dets(detect ? perCall * dc.max_detections : 0);
-  void *wideDev = nullptr, *powerDev = nullptr, *rowsDev = nullptr, *detDev = nullptr;
+  std::vector<iqd_track_slot> slots(track ? perCall * tc.n_slots : 0);
+  std::vector<iqd_track_block> tblocks(track ? perCall : 0);
+  uint64_t unplaced = 0;
+  void *wideDev = nullptr, *powerDev = nullptr, *rowsDev = nullptr, *detDev = nullptr, *slotsDev = nullptr, *tblocksDev = nullptr;
   if (detect) {
     rc = iqd_dev_alloc(e, buf.size(), &wideDev);
     if (rc == IQD_OK) rc = iqd_dev_alloc(e, power.size() * sizeof(uint32_t), &powerDev);
     if (rc == IQD_OK) rc = iqd_dev_alloc(e, rows.size() * sizeof(iqd_detect_row), &rowsDev);
     if (rc == IQD_OK) rc = iqd_dev_alloc(e, dets.size() * sizeof(iqd_detection), &detDev);
+    if (rc == IQD_OK && track) rc = iqd_dev_alloc(e, slots.size() * sizeof(iqd_track_slot), &slotsDev);
+    if (rc == IQD_OK && track) rc = iqd_dev_alloc(e, tblocks.size() * sizeof(iqd_track_block), &tblocksDev);
     if (rc != IQD_OK) {
       fprintf(stderr, "iqdemod_spectrum: iqd_dev_alloc: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      iqd_track_destroy(t);
       iqd_detect_destroy(d);
       iqd_spectrum_destroy(s);
       iqd_destroy(e);
@@ -187,12 +247,17 @@ int main(int argc, char **argv)
         rc = iqd_dev_upload(e, wideDev, buf.data(), nb * blockBytes);
         if (rc == IQD_OK) rc = iqd_spectrum_run_device(s, wideDev, nb * blockBytes, frames, (uint32_t *)powerDev);
         if (rc == IQD_OK) rc = iqd_detect_run_device(d, (const uint32_t *)powerDev, nb, (iqd_detect_row *)rowsDev, (iqd_detection *)detDev);
+        if (rc == IQD_OK && track)
+          rc = iqd_track_run_device(t, (const iqd_detect_row *)rowsDev, (const iqd_detection *)detDev, nb, (iqd_track_slot *)slotsDev,
+                                    (iqd_track_block *)tblocksDev);
         if (rc == IQD_OK) rc = iqd_dev_download(e, power.data(), powerDev, nb * bins * sizeof(uint32_t));
         if (rc == IQD_OK) rc = iqd_dev_download(e, rows.data(), rowsDev, nb * sizeof(iqd_detect_row));
         if (rc == IQD_OK) rc = iqd_dev_download(e, dets.data(), detDev, nb * dc.max_detections * sizeof(iqd_detection));
+        if (rc == IQD_OK && track) rc = iqd_dev_download(e, slots.data(), slotsDev, nb * tc.n_slots * sizeof(iqd_track_slot));
+        if (rc == IQD_OK && track) rc = iqd_dev_download(e, tblocks.data(), tblocksDev, nb * sizeof(iqd_track_block));
       }
       if (rc != IQD_OK) {
-        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", detect ? "spectrum and detector" : "iqd_spectrum_run", iqd_strerror(rc), iqd_last_error(e));
+        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", track ? "spectrum, detector and tracker" : detect ? "spectrum and detector" : "iqd_spectrum_run", iqd_strerror(rc), iqd_last_error(e));
         status = 3;
         break;
       }
@@ -219,14 +284,28 @@ int main(int argc, char **argv)
                   10.0 * log10((double)(r.peak_power ? r.peak_power : 1) / (double)(pfs ? pfs : 1)), (unsigned long long)r.sum_power);
         }
       }
+      for (size_t b = 0; track && b < nb; b++) {
+        unplaced += tblocks[b].n_unplaced;
+        for (uint32_t k = 0; k < tc.n_slots; k++) {
+          const iqd_track_slot &r = slots[b * tc.n_slots + k];
+          if (r.track_id == 0) continue;
+          int64_t hz = 0;
+          iqd_detect_offset_hz(bins, (uint32_t)rate, r.centre_q8, &hz);
+          fprintf(ftrk, "%llu %u %u %u %u %lld 0x%08x %.3f %.3f %u\n", (unsigned long long)(block + b), k, r.track_id, r.state, r.flags,
+                  (long long)hz, r.phase_inc, ((double)r.first_bin - bins / 2) * rate / bins, ((double)r.last_bin - bins / 2) * rate / bins,
+                  r.width_class);
+        }
+      }
       block += nb;
     }
     if (got < buf.size()) break;
   }
   if (dropped) fprintf(stderr, "iqdemod_spectrum: %zu bytes after the last whole block dropped\n", dropped);
   if (pastMax) fprintf(stderr, "iqdemod_spectrum: %llu runs past maxdet not written\n", (unsigned long long)pastMax);
-  for (void *p : {wideDev, powerDev, rowsDev, detDev})
+  if (unplaced) fprintf(stderr, "iqdemod_spectrum: %llu detections found no free slot\n", (unsigned long long)unplaced);
+  for (void *p : {wideDev, powerDev, rowsDev, detDev, slotsDev, tblocksDev})
     if (p) iqd_dev_free(e, p);
+  iqd_track_destroy(t);
   iqd_detect_destroy(d);
   iqd_spectrum_destroy(s);
   iqd_destroy(e);
@@ -234,5 +313,6 @@ int main(int argc, char **argv)
   if (fclose(fout) != 0) status = status ? status : 1;
   if (flog && fclose(flog) != 0) status = status ? status : 1;
   if (fdet && fclose(fdet) != 0) status = status ? status : 1;
+  if (ftrk && fclose(ftrk) != 0) status = status ? status : 1;
   return status;
 }
