@@ -776,6 +776,61 @@ int iqd_track_run(iqd_track_t *t, const iqd_detect_row *rows, const iqd_detectio
 int iqd_track_get_state(iqd_track_t *t, uint32_t source, iqd_track_slot *out /* [S] */);
 int iqd_track_phase_inc(uint32_t n_bins, uint32_t centroid_q8, uint32_t inc_bias, uint32_t *inc);
 
+/* Track-following channels: a channelizer channel may FOLLOW A SLOT of a track table - the slots array that
+ * iqd_track_run_device writes, or any array of that layout - and is then cut, block by block, at the slot's phase_inc.  The
+ * table is complete before the channelizer runs, so the retune stays on the device: iqd_track_run_device followed by the
+ * channelizer call on the engine's stream needs no synchronise in between.  Anything not named here is the integer
+ * channelizer's spec above.
+ *
+ *   blocks    a following channel's row of one call is n_blocks blocks of block_bytes bytes (block_bytes / 2 outputs, or
+ *             block_bytes M wide bytes per source).  A spectrum block of 2 N F wide bytes is block_bytes = 2 N F / M; the
+ *             caller chooses N, F and M so that this is a multiple of 64.
+ *   length    a call with at least one follower needs bytes_per_source / M == n_blocks * block_bytes, whatever the engine's
+ *             own block_bytes: the accept behind the channelizer sees ordinary rows.
+ *   entry     channel c with source j (its set_channels source) and slot s reads, for block b, the table entry
+ *             t = slots_dev[j][b - lag][s] - of it only state and phase_inc.  lag 1, block 0: the carry (below).
+ *   cut       t.state >= min_state: the block is live and cut by exactly the integer spec with d_b = t.phase_inc - taps from
+ *             d_b, the rotation P[(n d_b mod 2^32) >> 20] with absolute n, the channel's gain shift, the wide history as
+ *             always.  Otherwise every byte of the block is 0x80: free slots, tentative ones under min_state 2, and a slot in
+ *             its closing block (state 0 although track_id != 0).
+ *   carry     per following channel, on the device: (live, d).  Every call with followers leaves it at the decision of its
+ *             LAST table block, entry n_blocks - 1 of the channel's source and slot, whatever lag is.  With lag 1, block 0
+ *             uses the carry, so one call of b1 + b2 blocks gives the bytes of a call of b1 followed by one of b2 with the
+ *             table halves handed in by two set_track_table calls.  The carry is not live after create, after
+ *             iqd_channelizer_reset, and for a channel that has just started to follow (or moved to another slot).
+ *   settings  while a channel follows, its set_channels increment is kept but ignored (source and gain shift still apply);
+ *             it is back in force at the next call after the channel stops.  reset keeps the flags and the table.  Several
+ *             channels may follow one slot.  The table's memory is read when the kernel runs, in stream order; the table
+ *             stays in force until it is replaced (NULL: no table).
+ *   calls     track followers need no engine channel: they run under iqd_channelizer_run / _run_device and
+ *             iqd_accept_wideband / _device, beside fixed channels; under the accept forms also beside scanner- and
+ *             gain-following channels (which the run forms go on refusing).
+ *   launches  one kernel launch per call whatever n_blocks for K <= 256; for longer prototypes two per run of blocks, the
+ *             runs cut so that the per-(block, tile) operand scratch stays within 64 MiB (or one block's, where that is more).
+ *   refusals  IQD_EINVAL before anything is queued, the message naming the reason, the stream intact afterwards.
+ *             set_track_table: a non-zero reserved word; n_slots outside 1..64; n_blocks 0; block_bytes 0 or no multiple of
+ *             64; lag > 1; min_state not 1 or 2; slots_dev NULL or not 16-byte aligned.  follow_tracks: a slot < -1 or > 63;
+ *             a bad channel range; a slot >= 0 on a fractional channelizer or on signed captures, or on a channel that follows
+ *             its scanner or its gain - and follow_scanner / follow_gain(..., 1) on a track follower.  A call with followers:
+ *             no table set; a follower's slot >= the table's n_slots; the length rule violated.  iqd_channelizer_survey*
+ *             while any channel follows tracks.
+ * iqd_channelizer_follow_tracks: slot[i] >= 0: channel first + i follows that slot of ITS source's table row; -1, or
+ *             slot == NULL: it stops following.
+ * iqd_channelizer_track_window_outputs (host only, no GPU): iqd_channelizer_window_outputs for a track follower's window,
+ *             which shares its LDS with the prototype: t with 2 (t M + Kp) <= 32768 - 2048, cut to a multiple of 64 and to 1024. */
+typedef struct iqd_track_follow {
+    const iqd_track_slot *slots_dev;  /* [n_sources][n_blocks][n_slots], as iqd_track_run_device writes it; 16-byte aligned */
+    uint32_t n_slots;                 /* S of the table, 1 ... 64 */
+    uint32_t n_blocks;                /* table blocks per source, >= 1 */
+    uint32_t block_bytes;             /* row bytes (output bytes of one channel) that one table block covers: a multiple of 64 */
+    uint32_t lag;                     /* 0: block b is cut at table block b; 1: at table block b - 1 (block 0: the carry) */
+    uint32_t min_state;               /* IQD_TRACK_TENTATIVE (1) or IQD_TRACK_ACTIVE (2) */
+    uint32_t reserved[3];             /* 0 */
+} iqd_track_follow;
+int iqd_channelizer_set_track_table(iqd_channelizer_t *z, const iqd_track_follow *t);   /* NULL: no table */
+int iqd_channelizer_follow_tracks(iqd_channelizer_t *z, uint32_t first, uint32_t n, const int32_t *slot);
+uint32_t iqd_channelizer_track_window_outputs(uint32_t decimation, uint32_t n_taps);
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

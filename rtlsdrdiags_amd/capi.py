@@ -76,6 +76,12 @@ TRACK_SLOT = np.dtype([("track_id", "<u4"), ("state", "u1"), ("flags", "u1"), ("
 TRACK_BLOCK = np.dtype([("n_active", "<u4"), ("n_tentative", "<u4"), ("n_opened_closed", "<u4"), ("n_unplaced", "<u4")])
 
 
+class TrackFollow(C.Structure):
+    """iqd_track_follow (include/iqdemod.h: "Track-following channels")"""
+    _fields_ = [("slots_dev", C.c_void_p), ("n_slots", C.c_uint32), ("n_blocks", C.c_uint32), ("block_bytes", C.c_uint32),
+                ("lag", C.c_uint32), ("min_state", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class IqdError(RuntimeError):
     def __init__(self, status, detail):
         super().__init__("libiqdemod: %s (%d): %s" % (_lib().iqd_strerror(status).decode(), status, detail))
@@ -108,6 +114,7 @@ EXPORTS = [
     "iqd_detect_create", "iqd_detect_destroy", "iqd_detect_run_device", "iqd_detect_run", "iqd_detect_offset_hz",
     "iqd_track_create", "iqd_track_destroy", "iqd_track_reset", "iqd_track_run_device", "iqd_track_run", "iqd_track_get_state",
     "iqd_track_phase_inc",
+    "iqd_channelizer_set_track_table", "iqd_channelizer_follow_tracks", "iqd_channelizer_track_window_outputs",
 ]
 
 _LIB = None
@@ -237,6 +244,10 @@ def _lib():
     L.iqd_track_run.argtypes = [vp, vp, vp, sz, vp, vp]
     L.iqd_track_get_state.argtypes = [vp, u32, vp]
     L.iqd_track_phase_inc.argtypes = [u32, u32, u32, C.POINTER(u32)]
+    L.iqd_channelizer_set_track_table.argtypes = [vp, C.POINTER(TrackFollow)]
+    L.iqd_channelizer_follow_tracks.argtypes = [vp, u32, u32, vp]
+    L.iqd_channelizer_track_window_outputs.argtypes = [u32, u32]
+    L.iqd_channelizer_track_window_outputs.restype = u32
     _LIB = L
     return L
 
@@ -729,6 +740,11 @@ def channelizer_window_outputs(decimation, n_taps, sample_format="u8"):
     return int(_lib().iqd_channelizer_window_outputs(int(decimation), int(n_taps), SAMPLE_FORMAT[sample_format][0]))
 
 
+def channelizer_track_window_outputs(decimation, n_taps):
+    """iqd_channelizer_track_window_outputs (host only): the most outputs of one window of a track follower's block."""
+    return int(_lib().iqd_channelizer_track_window_outputs(int(decimation), int(n_taps)))
+
+
 class Channelizer:
     """iqd_channelizer_*: n_channels channels cut out of n_sources wideband captures at decimation / decimation_den x
     256 kS/s (decimation_den 1, 2, 4 or 8; 2.4 MS/s is 75 / 8).  sample_format: what the captures hold - "u8" (offset
@@ -838,6 +854,29 @@ class Channelizer:
         in dB and per engine block, in place of the channel's gain shift."""
         n = self.n_channels - int(first) if n is None else int(n)
         self._e._check(self._L.iqd_channelizer_follow_gain(self._h, int(first), n, 1 if follow else 0))
+
+    def follow_tracks(self, slot, first=0, n=None):
+        """Channels [first, first + n) follow slot[i] of their source's track table row (one value: all the same slot);
+        -1 or None: they stop following."""
+        if slot is None:
+            n = self.n_channels - int(first) if n is None else int(n)
+            self._e._check(self._L.iqd_channelizer_follow_tracks(self._h, int(first), n, None))
+            return
+        s = np.atleast_1d(np.asarray(slot, dtype=np.int64))
+        if n is None:
+            n = len(s) if np.ndim(slot) else self.n_channels - int(first)
+        s = np.ascontiguousarray(np.clip(np.broadcast_to(s, int(n)), -2 ** 31, 2 ** 31 - 1), np.int32)
+        self._e._check(self._L.iqd_channelizer_follow_tracks(self._h, int(first), int(n), _np_ptr(s)))
+
+    def set_track_table(self, slots_dev, n_slots=0, n_blocks=0, block_bytes=0, lag=0, min_state=2, reserved=(0, 0, 0)):
+        """The track table the followers read: slots_dev a device pointer (integer) to [n_sources][n_blocks][n_slots]
+        iqd_track_slot, as Tracker.run_device writes it; block_bytes the row bytes one table block covers.  None clears."""
+        if slots_dev is None:
+            self._e._check(self._L.iqd_channelizer_set_track_table(self._h, None))
+            return
+        t = TrackFollow(int(slots_dev) or None, int(n_slots), int(n_blocks), int(block_bytes), int(lag), int(min_state),
+                        (C.c_uint32 * 3)(*[int(r) for r in reserved]))
+        self._e._check(self._L.iqd_channelizer_set_track_table(self._h, C.byref(t)))
 
     def close(self):
         """iqd_channelizer_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""

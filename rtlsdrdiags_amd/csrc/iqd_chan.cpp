@@ -4,7 +4,8 @@
 // into tiles of 8 (padding slots have zero taps and store nothing), packs the tiles' taps as MFMA A operands
 // (iqd_chan.h) and queues the kernel of iqd_chan.hip on the engine's stream.  Only the channels a set_channels call
 // names get new taps; the packing is redone at the next run.  Channels that follow their engine channel's IF gain
-// (iqd_channelizer_follow_gain) get tiles and workgroups of their own and go to chz_gain_kernel (iqd_chan_gain.hip).  Captures of a signed sample format (IQD_WIDE_S8, IQD_WIDE_S16)
+// (iqd_channelizer_follow_gain) get tiles and workgroups of their own and go to chz_gain_kernel (iqd_chan_gain.hip); so do
+// channels that follow a slot of a track table (iqd_channelizer_follow_tracks; chz_track_kernel, iqd_chan_track.hip).  Captures of a signed sample format (IQD_WIDE_S8, IQD_WIDE_S16)
 // go to chz_fmt_kernel (iqd_chan_fmt.hip) with the same tiles and A operands; S16 adds the rows' coefficient sums.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -62,8 +63,8 @@ struct Staging {
     }
 };
 
-// the three kinds of channel: each has tiles and workgroups of its own and its kernel
-enum { CHZ_FIXED, CHZ_GAIN, CHZ_SCAN, CHZ_KINDS };
+// the four kinds of channel: each has tiles and workgroups of its own and its kernel
+enum { CHZ_FIXED, CHZ_GAIN, CHZ_SCAN, CHZ_TRACK, CHZ_KINDS };
 struct WgSet {
     std::vector<ChzWg> wgs;
     DevBufExact dev;
@@ -98,6 +99,14 @@ struct iqd_channelizer {
     std::vector<uint8_t> follow_gain;             // [n_ch]: the channel follows its engine channel's IF gain
     std::vector<unsigned long long> centre;       // [n_src]: source centre frequencies
     uint32_t n_follow = 0, n_gain = 0;
+    std::vector<int32_t> trk;                     // [n_ch]: the table slot the channel follows, -1: none
+    std::vector<uint8_t> trk_fresh;               // [n_ch]: it has started to follow since the last call (its carry does not count)
+    uint32_t n_track = 0;
+    bool any_fresh = false;
+    iqd_track_follow table{};                     // the track table in force (slots_dev NULL: none)
+    DevBufExact d_carry[2], d_track_amat;         // the followers' carries (live, d) [n_ch], by call parity; large K: the scratch
+    int carry_cur = 0;
+    bool track_ran = false;                       // the last queued call had track followers (wideband_queue's step back)
     bool centre_dirty = true;
     uint32_t n_cus = 256;
     std::vector<int16_t> gr, gi;                  // [n_ch][q branches][kb], zero from a branch's length on
@@ -106,9 +115,10 @@ struct iqd_channelizer {
     bool any_dirty = true;
     uint64_t m_abs = 0;                           // outputs per channel since create / reset
     std::vector<ChzTile> tiles;
-    WgSet wg[CHZ_KINDS];                          // chz_kernel's workgroups (fixed channels), the gain walker's, the scan walker's
+    WgSet wg[CHZ_KINDS];                          // chz_kernel's workgroups (fixed channels), the gain walker's, the scan walker's, chz_track_kernel's
+    uint32_t first_track_tile = 0;                // tiles [first_track_tile, tiles.size()) hold track followers
     uint32_t n_fixed_tiles = 0;                   // tiles [0, n_fixed_tiles) hold fixed channels,
-    uint32_t n_packed_tiles = 0;                  // [n_fixed_tiles, n_packed_tiles) gain-following ones, the rest scanner-following
+    uint32_t n_packed_tiles = 0;                  // [n_fixed_tiles, n_packed_tiles) gain-following ones, then scanner-, then track-following
     std::vector<uint32_t> slot_of;                // [n_ch]: tile * 8 + slot
     std::vector<uint8_t> amat;                    // [n_tiles][q residues][nq][2][64][16]
     std::vector<ChzFmtTile> gsum;                 // [n_tiles]: the rows' coefficient sums (IQD_WIDE_S16 only)
@@ -179,8 +189,8 @@ static void chz_new_taps(iqd_channelizer *z, uint32_t c)
     z->any_dirty = true;
 }
 
-// channels sorted by source, 8 per tile, up to CHZ_WAVES tiles of one source per workgroup row; fixed, gain-following and
-// scanner-following channels never share a tile.  A walker's workgroups take `waves` tiles each: as few as keep every CU
+// channels sorted by source, 8 per tile, up to CHZ_WAVES tiles of one source per workgroup row; fixed, gain-following,
+// scanner-following and track-following channels never share a tile.  A walker's workgroups take `waves` tiles each: as few as keep every CU
 // busy; the rest of the workgroup's 8 waves share the tiles' outputs (wpt waves per tile).
 static void chz_walker_wgs(const iqd_channelizer *z, const std::vector<ChzWg> &runs, WgSet &w)
 {
@@ -202,9 +212,10 @@ static void chz_group(iqd_channelizer *z)
     std::vector<std::vector<uint32_t>> by_src[CHZ_KINDS];
     for (auto &b : by_src) b.resize(z->n_src);
     for (uint32_t c = 0; c < z->n_ch; c++)
-        by_src[z->follow[c] ? CHZ_SCAN : z->follow_gain[c] ? CHZ_GAIN : CHZ_FIXED][z->src[c]].push_back(c);
+        by_src[z->follow[c] ? CHZ_SCAN : z->follow_gain[c] ? CHZ_GAIN : z->trk[c] >= 0 ? CHZ_TRACK : CHZ_FIXED][z->src[c]].push_back(c);
     std::vector<ChzWg> runs[CHZ_KINDS];           // following tiles per source
     for (int f = 0; f < CHZ_KINDS; f++) {
+        if (f == CHZ_TRACK) z->first_track_tile = (uint32_t)z->tiles.size();
         for (uint32_t s = 0; s < z->n_src; s++) {
             const auto &list = by_src[f][s];
             const uint32_t first_tile = (uint32_t)z->tiles.size();
@@ -217,7 +228,7 @@ static void chz_group(iqd_channelizer *z)
                 z->tiles.push_back(t);
             }
             const uint32_t n_tiles = (uint32_t)z->tiles.size() - first_tile;
-            if (f == CHZ_FIXED)
+            if (f == CHZ_FIXED || f == CHZ_TRACK)   // chz_kernel's geometry: rows of up to CHZ_WAVES tiles
                 for (uint32_t t = 0; t < n_tiles; t += CHZ_WAVES)
                     z->wg[f].wgs.push_back(ChzWg{s, first_tile + t, std::min(CHZ_WAVES, n_tiles - t), 0});
             else if (n_tiles)
@@ -269,7 +280,9 @@ static void chz_pack_slot(iqd_channelizer *z, uint32_t tile, uint32_t l)
     const uint32_t c = t.ch[l];
     t.inc[l] = c == CHZ_NONE ? 0 : z->inc[c];
     t.shift[l] = c == CHZ_NONE ? 0 : z->shift[c];
-    if (tile >= z->n_packed_tiles) return;   // a scanner-following channel: the walker builds its operands itself, per block
+    if (tile >= z->first_track_tile)         // a track follower: the slot it follows in the increment's place (iqd_chan.h)
+        t.inc[l] = c == CHZ_NONE ? 0 : (uint32_t)z->trk[c] | (z->trk_fresh[c] ? CHZ_TRACK_FRESH : 0u);
+    if (tile >= z->n_packed_tiles) return;   // a following channel whose kernel builds its operands itself, per block
     const size_t taps = c == CHZ_NONE ? 0 : (size_t)c * z->q * z->kb;
     chz_pack_rows(z, z->amat.data(), tile, l, c == CHZ_NONE ? nullptr : &z->gr[taps], c == CHZ_NONE ? nullptr : &z->gi[taps]);
     if (z->fmt == IQD_WIDE_S16) {   // the sums of rows 2 l (gr on I, -gi on Q) and 2 l + 1 (gi on I, gr on Q); |sum| < 2^25
@@ -330,6 +343,7 @@ static int chz_upload(iqd_channelizer *z)
 static int chz_fill_history(iqd_channelizer *z)   // zero history: offset-binary 0x80; a signed format's raw bytes: 0
 {
     CHZ_TRY(z, hipMemsetAsync(z->d_hist[z->cur].p, z->fmt == IQD_WIDE_U8 ? 0x80 : 0, (size_t)z->n_src * 2 * z->kp * z->rail, z->stream));
+    CHZ_TRY(z, hipMemsetAsync(z->d_carry[z->carry_cur].p, 0, (size_t)z->n_ch * sizeof(uint2), z->stream));   // no carry is live
     z->m_abs = 0;
     return IQD_OK;
 }
@@ -458,6 +472,8 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
     z->shift.assign(z->n_ch, 0);
     z->follow.assign(z->n_ch, 0);
     z->follow_gain.assign(z->n_ch, 0);
+    z->trk.assign(z->n_ch, -1);
+    z->trk_fresh.assign(z->n_ch, 0);
     z->centre.assign(z->n_src, 0);
     {
         int cus = 0;
@@ -473,7 +489,8 @@ int iqd_channelizer_create(iqd_t *e, const iqd_channelizer_config *cfg, iqd_chan
         packed[i] = (uint16_t)z->phasor[2 * i] | ((uint32_t)(uint16_t)z->phasor[2 * i + 1] << 16);
     const size_t hb = (size_t)z->n_src * 2 * z->kp * z->rail;
     bool ok = z->d_phasor.ensure(CHZ_PHASOR * 4) == hipSuccess && z->d_hist[0].ensure(hb) == hipSuccess &&
-              z->d_hist[1].ensure(hb) == hipSuccess;
+              z->d_hist[1].ensure(hb) == hipSuccess && z->d_carry[0].ensure((size_t)z->n_ch * sizeof(uint2)) == hipSuccess &&
+              z->d_carry[1].ensure((size_t)z->n_ch * sizeof(uint2)) == hipSuccess;
     ok = ok && hipMemcpy(z->d_phasor.p, packed.data(), CHZ_PHASOR * 4, hipMemcpyHostToDevice) == hipSuccess;
     std::vector<int16_t> proto(z->kp, 0);
     if (z->q == 1) std::copy(z->h.begin(), z->h.end(), proto.begin());   // (the walker's; it does not run at q > 1)
@@ -535,6 +552,20 @@ static int chz_check_len(iqd_channelizer *z, size_t bytes_per_source)
         return z->fail(IQD_EINVAL, "channelizer: bytes_per_source must be a positive multiple of 64 * decimation");
     if (bytes_per_source / z->m * z->q > 0x7fffffffull) return z->fail(IQD_EINVAL, "channelizer: bytes_per_source too large");
     if (bytes_per_source > 0x7fffffffull) return z->fail(IQD_EINVAL, "channelizer: bytes_per_source too large");
+    return IQD_OK;
+}
+
+// every refusal of a call with track followers: no table, a slot the table does not have, the length rule
+static int chz_check_tracks(iqd_channelizer *z, size_t bytes_per_source)
+{
+    if (!z->n_track) return IQD_OK;
+    const iqd_track_follow &t = z->table;
+    if (!t.slots_dev) return z->fail(IQD_EINVAL, "channelizer: a channel follows a track slot and no track table is set");
+    for (uint32_t c = 0; c < z->n_ch; c++)
+        if (z->trk[c] >= 0 && (uint32_t)z->trk[c] >= t.n_slots)
+            return z->fail(IQD_EINVAL, "channelizer: a channel follows a slot the track table does not have (slot >= n_slots)");
+    if (z->row_bytes(bytes_per_source) != (size_t)t.n_blocks * t.block_bytes)
+        return z->fail(IQD_EINVAL, "channelizer: with track followers bytes_per_source / decimation must be the table's n_blocks * block_bytes");
     return IQD_OK;
 }
 
@@ -611,6 +642,44 @@ static int chz_queue(iqd_channelizer *z, const void *wide_dev, size_t bytes_per_
             scan->waves = sw.waves;
             scan->wpt = sw.wpt;
         }
+        const WgSet &tw = z->wg[CHZ_TRACK];
+        z->track_ran = !tw.wgs.empty();
+        if (z->track_ran) {   // (checked by chz_check_tracks: the table is there and fits the call)
+            ChzTrackLaunch t{};
+            t.slots = z->table.slots_dev;
+            t.carry = z->d_carry[z->carry_cur].as<uint2>();
+            t.carry_next = z->d_carry[z->carry_cur ^ 1].as<uint2>();
+            t.proto = z->d_proto.as<int16_t>();
+            t.n_slots = z->table.n_slots;
+            t.n_blocks = z->table.n_blocks;
+            t.block_out = z->table.block_bytes / 2;
+            t.lag = z->table.lag;
+            t.min_state = z->table.min_state;
+            t.first_tile = z->first_track_tile;
+            t.n_tiles = (uint32_t)z->tiles.size() - z->first_track_tile;
+            ChzLaunch b = a;
+            b.wgs = tw.dev.as<ChzWg>();
+            b.t_blk = std::min(t.block_out, chz_track_window_outputs(z->m, z->kp));
+            t.wins = (t.block_out + b.t_blk - 1) / b.t_blk;
+            uint32_t run_blocks = t.n_blocks;
+            if (z->nq > CHZ_NQ_REG) {   // the scratch: CHZ_TRACK_SCRATCH bytes at most, or one block's operands
+                const size_t per_block = (size_t)t.n_tiles * z->nq * 2 * 64 * 16;
+                run_blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>(t.n_blocks, CHZ_TRACK_SCRATCH / per_block));
+                CHZ_TRY(z, z->d_track_amat.ensure(run_blocks * per_block));
+                t.amat = z->d_track_amat.as<uint4>();
+            }
+            CHZ_TRY(z, launch_channelizer_track(b, (uint32_t)tw.wgs.size(), t, run_blocks, z->stream));
+            z->carry_cur ^= 1;
+            if (z->any_fresh) {   // the carries count from the next call on: those tiles are packed again
+                for (uint32_t c = 0; c < z->n_ch; c++)
+                    if (z->trk_fresh[c]) {
+                        z->trk_fresh[c] = 0;
+                        z->ch_dirty[c] = 1;
+                    }
+                z->any_fresh = false;
+                z->any_dirty = true;
+            }
+        }
         CHZ_TRY(z, launch_channelizer(a, n_fixed, sw.dev.as<ChzWg>(), scan ? (uint32_t)sw.wgs.size() : 0u, scan, z->stream));
     }
     z->cur ^= 1;
@@ -626,6 +695,7 @@ int iqd_channelizer_run_device(iqd_channelizer_t *z, const void *wide_dev, size_
     if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: a channel follows its scanner; use iqd_accept_wideband*");
     if (z->n_gain) return z->fail(IQD_EINVAL, "channelizer: a channel follows its gain; use iqd_accept_wideband*");
     int rc = chz_check_len(z, bytes_per_source);
+    if (rc == IQD_OK) rc = chz_check_tracks(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     return chz_queue(z, wide_dev, bytes_per_source, out_dev, nullptr);
 }
@@ -637,6 +707,7 @@ int iqd_channelizer_run(iqd_channelizer_t *z, const uint8_t *wide, size_t bytes_
     if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: a channel follows its scanner; use iqd_accept_wideband*");
     if (z->n_gain) return z->fail(IQD_EINVAL, "channelizer: a channel follows its gain; use iqd_accept_wideband*");
     int rc = chz_check_len(z, bytes_per_source);
+    if (rc == IQD_OK) rc = chz_check_tracks(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(z->device);
     const size_t ib = (size_t)z->n_src * bytes_per_source, ob = (size_t)z->n_ch * z->row_bytes(bytes_per_source);
@@ -702,6 +773,7 @@ static int chz_survey_check(iqd_channelizer *z, size_t bytes_per_source, uint32_
     if (z->sv_inc.empty()) return z->fail(IQD_EINVAL, "channelizer: no survey points set");
     if (z->n_follow) return z->fail(IQD_EINVAL, "channelizer: no survey while a channel follows its scanner");
     if (z->n_gain) return z->fail(IQD_EINVAL, "channelizer: no survey while a channel follows its gain");
+    if (z->n_track) return z->fail(IQD_EINVAL, "channelizer: no survey while a channel follows a track slot");
     int rc = chz_check_len(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     const uint32_t unit = z->q > 1 ? 256 : 64;
@@ -787,6 +859,7 @@ static int wideband_queue(iqd_t *e, iqd_channelizer *z, uint32_t first_ch, const
     if (!wide_dev || !rows_dev || !pcm_dev) return z->fail(IQD_EINVAL, "accept_wideband: NULL buffer");
     if ((((uintptr_t)wide_dev) | ((uintptr_t)rows_dev)) & 15) return z->fail(IQD_EINVAL, "accept_wideband: wide and rows buffers must be 16-byte aligned");
     int rc = chz_check_len(z, bytes_per_source);
+    if (rc == IQD_OK) rc = chz_check_tracks(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     uint32_t e_nch = 0, bb = 0, flags = 0;
     engine_geometry(e, &e_nch, &bb, &flags);
@@ -815,6 +888,7 @@ static int wideband_queue(iqd_t *e, iqd_channelizer *z, uint32_t first_ch, const
         // still, the channelizer steps back as well: the call's history went to the other buffer, so the stream stands
         // where it stood before the call, like the engine's.
         z->cur ^= 1;
+        if (z->track_ran) z->carry_cur ^= 1;
         z->m_abs -= z->row_bytes(bytes_per_source) / 2;
         return rc;
     }
@@ -828,6 +902,7 @@ int iqd_accept_wideband(iqd_t *e, iqd_channelizer_t *z, uint32_t first_ch, const
     if (!z || z->e != e) return engine_fail(e, IQD_EINVAL, "accept_wideband: the channelizer belongs to another engine");
     if (!wide || !pcm) return z->fail(IQD_EINVAL, "accept_wideband: NULL buffer");
     int rc = chz_check_len(z, bytes_per_source);
+    if (rc == IQD_OK) rc = chz_check_tracks(z, bytes_per_source);
     if (rc != IQD_OK) return rc;
     uint32_t e_nch = 0, bb = 0, flags = 0;
     engine_geometry(e, &e_nch, &bb, &flags);
@@ -879,8 +954,11 @@ static int chz_follow(iqd_channelizer *z, uint32_t first, uint32_t n, int follow
     if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
     if (follow && z->fmt != IQD_WIDE_U8) return z->fail(IQD_EINVAL, msg[z->fmt == IQD_WIDE_S16 ? 0 : 1]);
     if (follow && z->q > 1) return z->fail(IQD_EINVAL, msg[2]);
-    for (uint32_t i = 0; follow && i < n; i++)
+    for (uint32_t i = 0; follow && i < n; i++) {
         if (other[first + i]) return z->fail(IQD_EINVAL, msg[3]);
+        if (z->trk[first + i] >= 0)
+            return z->fail(IQD_EINVAL, "channelizer: a channel that follows a track slot cannot follow its scanner or its gain as well (not built yet)");
+    }
     for (uint32_t i = 0; i < n; i++) {
         uint8_t &f = flags[first + i];
         if (f == (follow ? 1 : 0)) continue;
@@ -909,6 +987,66 @@ int iqd_channelizer_follow_gain(iqd_channelizer_t *z, uint32_t first, uint32_t n
         "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow their gain yet",
         "channelizer: a channel that follows its scanner cannot follow its gain as well (not built yet)"};
     return z ? chz_follow(z, first, n, follow, z->follow_gain, z->follow, z->n_gain, msg) : IQD_EINVAL;
+}
+
+int iqd_channelizer_set_track_table(iqd_channelizer_t *z, const iqd_track_follow *t)
+{
+    if (!z) return IQD_EINVAL;
+    if (!t) {
+        z->table = iqd_track_follow{};
+        return IQD_OK;
+    }
+    for (uint32_t r : t->reserved)
+        if (r) return z->fail(IQD_EINVAL, "channelizer: a track table's reserved fields must be 0");
+    if (t->n_slots < 1 || t->n_slots > 64) return z->fail(IQD_EINVAL, "channelizer: a track table's n_slots must be 1..64");
+    if (t->n_blocks < 1) return z->fail(IQD_EINVAL, "channelizer: a track table's n_blocks must be >= 1");
+    if (t->block_bytes == 0 || t->block_bytes % 64 != 0)
+        return z->fail(IQD_EINVAL, "channelizer: a track table's block_bytes must be a positive multiple of 64");
+    if (t->lag > 1) return z->fail(IQD_EINVAL, "channelizer: a track table's lag must be 0 or 1");
+    if (t->min_state != IQD_TRACK_TENTATIVE && t->min_state != IQD_TRACK_ACTIVE)
+        return z->fail(IQD_EINVAL, "channelizer: a track table's min_state must be IQD_TRACK_TENTATIVE (1) or IQD_TRACK_ACTIVE (2)");
+    if (!t->slots_dev) return z->fail(IQD_EINVAL, "channelizer: a track table's slots_dev is NULL");
+    if (((uintptr_t)t->slots_dev) & 15) return z->fail(IQD_EINVAL, "channelizer: a track table's slots_dev must be 16-byte aligned");
+    z->table = *t;
+    return IQD_OK;
+}
+
+int iqd_channelizer_follow_tracks(iqd_channelizer_t *z, uint32_t first, uint32_t n, const int32_t *slot)
+{
+    if (!z) return IQD_EINVAL;
+    if (n < 1 || first >= z->n_ch || n > z->n_ch - first) return z->fail(IQD_EINVAL, "channelizer: bad channel range");
+    for (uint32_t i = 0; slot && i < n; i++) {
+        if (slot[i] < -1 || slot[i] > 63) return z->fail(IQD_EINVAL, "channelizer: a track slot must be -1 or 0..63");
+        if (slot[i] < 0) continue;
+        if (z->fmt != IQD_WIDE_U8)
+            return z->fail(IQD_EINVAL, z->fmt == IQD_WIDE_S16 ? "channelizer: channels on IQD_WIDE_S16 captures cannot follow tracks yet"
+                                                              : "channelizer: channels on IQD_WIDE_S8 captures cannot follow tracks yet");
+        if (z->q > 1) return z->fail(IQD_EINVAL, "channelizer: channels of a fractional channelizer (decimation_den > 1) cannot follow tracks yet");
+        if (z->follow[first + i]) return z->fail(IQD_EINVAL, "channelizer: a channel that follows its scanner cannot follow a track slot as well (not built yet)");
+        if (z->follow_gain[first + i]) return z->fail(IQD_EINVAL, "channelizer: a channel that follows its gain cannot follow a track slot as well (not built yet)");
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t c = first + i;
+        const int32_t s = slot ? slot[i] : -1;
+        if (s == z->trk[c]) continue;
+        if ((s >= 0) != (z->trk[c] >= 0)) {
+            z->n_track += s >= 0 ? 1 : -1;
+            z->layout_dirty = true;
+        }
+        z->trk[c] = s;
+        z->trk_fresh[c] = s >= 0;   // a channel that starts to follow, or moves to another slot: its carry does not count
+        z->any_fresh = z->any_fresh || s >= 0;
+        z->ch_dirty[c] = 1;
+        z->any_dirty = true;
+    }
+    return IQD_OK;
+}
+
+// chz_track_window_outputs as a host-only function
+uint32_t iqd_channelizer_track_window_outputs(uint32_t decimation, uint32_t n_taps)
+{
+    if (decimation < 2 || decimation > 64 || n_taps < 1 || n_taps > 1024) return 0;
+    return chz_track_window_outputs(decimation, (n_taps + 31) / 32 * 32);
 }
 
 // chz_t_max as a host-only function (the window's fit in LDS is checked on it for every M)

@@ -90,6 +90,26 @@ struct ChzGainShadow { AgcConfig cfg; AgcState st; };
 constexpr uint32_t CHZ_GAIN_SHADOW = CHZ_WAVES * CHZ_TILE_CH * (uint32_t)sizeof(ChzGainShadow);   // the walker's shadows in LDS
 struct ChzGainLaunch : ChzWalkLaunch {};
 
+// Track-following channels (chz_track_kernel, iqd_chan_track.hip) beside ChzLaunch: a.wgs are the track tiles' workgroup
+// rows, a.t_blk the outputs of one window of a block.  ChzTile::inc of a track tile is not an increment: it holds the table
+// slot its channel follows, and CHZ_TRACK_FRESH while the channel's carry does not count (it has just started to follow).
+constexpr uint32_t CHZ_TRACK_FRESH = 0x80000000u;
+constexpr size_t CHZ_TRACK_SCRATCH = (size_t)64 << 20;   // large K: the most bytes of per-(block, tile) A operands of one run of
+                                                         // blocks (one block's, where that alone is more)
+struct ChzTrackLaunch {
+    const iqd_track_slot *slots;           // [n_sources][n_blocks][n_slots], read when the kernel runs
+    const uint2 *carry;                    // [n_ch]: (live, d) the previous call left (block 0 at lag 1)
+    uint2 *carry_next;                     // the same after this call: the decision of table block n_blocks - 1
+    const int16_t *proto;                  // [kp] prototype, zero from K on
+    uint4 *amat;                           // nq > CHZ_NQ_REG: [blocks of a run][n_tiles][nq][2 planes][64 lanes]
+    uint32_t n_slots, n_blocks;            // S and the blocks per source of the table
+    uint32_t block_out;                    // outputs per table block, a multiple of 32
+    uint32_t wins;                         // windows per block, ceil(block_out / a.t_blk)
+    uint32_t lag, min_state;
+    uint32_t b0;                           // first table block of this launch (a run of the large-K path; else 0)
+    uint32_t first_tile, n_tiles;          // the track tiles are [first_tile, first_tile + n_tiles) of a.tiles
+};
+
 // The band survey (chz_survey_kernel, iqd_chan_survey.hip) beside ChzLaunch: a.tiles / a.amat are the survey's point tiles
 // (ChzTile::ch is the point index), shared by all sources; a.wgs and a.out are unused.  Workgroup x of the grid is
 // (source, window, row of CHZ_WAVES point tiles) = (x / (n_win rows), x / rows % n_win, x % rows).
@@ -123,6 +143,14 @@ constexpr uint32_t chz_window_outputs(uint32_t m, uint32_t kp, uint32_t q, uint3
     return (uint32_t)(t < 1024 ? t : 1024) / group * group;
 }
 
+// The same for a track follower's window, which shares the LDS with the prototype (2 CHZ_PROTO_MAX bytes):
+// 2 (t m + kp) <= CHZ_WIN_MAX - 2 CHZ_PROTO_MAX.  (iqd_channelizer_track_window_outputs exports it.)
+constexpr uint32_t chz_track_window_outputs(uint32_t m, uint32_t kp)
+{
+    const uint32_t t = ((CHZ_WIN_MAX - 2 * CHZ_PROTO_MAX) / 2 - kp) / m;
+    return (t < 1024 ? t : 1024) / CHZ_GROUP * CHZ_GROUP;
+}
+
 // iqd_channelizer_tuning: the increment of a channel whose station is `station` Hz (centre station + 64000 r) cut from a
 // source centred on `centre` Hz at Fs = 256000 M; false when out of band.  Host and device share this one statement.
 __host__ __device__ inline bool chz_tuning(uint32_t m, unsigned long long centre, unsigned long long station, int32_t r,
@@ -153,6 +181,10 @@ hipError_t launch_channelizer_fmt(const ChzFmtLaunch &f, uint32_t n_wgs, hipStre
 
 // chz_gain_kernel alone: n_wgs workgroups a.wgs of gain-following tiles, one launch whatever g.n_blocks (iqd_chan_gain.hip)
 hipError_t launch_channelizer_gain(const ChzLaunch &a, uint32_t n_wgs, const ChzGainLaunch &g, hipStream_t st);
+
+// chz_track_kernel alone: n_wgs workgroup rows a.wgs of track tiles.  nq <= CHZ_NQ_REG: one launch whatever t.n_blocks; else
+// per run of run_blocks table blocks chz_track_build_kernel and chz_track_kernel<0> (iqd_chan_track.hip)
+hipError_t launch_channelizer_track(const ChzLaunch &a, uint32_t n_wgs, const ChzTrackLaunch &t, uint32_t run_blocks, hipStream_t st);
 
 // host-only spec pieces (iqd_chan.cpp)
 void chz_phasor_table(int16_t *out /* [8192] (c, s) pairs */);

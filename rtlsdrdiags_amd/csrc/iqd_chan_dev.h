@@ -1,6 +1,6 @@
 // Device pieces of the wideband channelizer, each written once for chz_kernel / chz_scan_kernel (iqd_chan.hip),
-// chz_frac_kernel (iqd_chan_frac.hip), chz_survey_kernel (iqd_chan_survey.hip), chz_fmt_kernel (iqd_chan_fmt.hip) and
-// chz_gain_kernel (iqd_chan_gain.hip): the B operand read, the epilogue of one output, the window staging, the prologue
+// chz_frac_kernel (iqd_chan_frac.hip), chz_survey_kernel (iqd_chan_survey.hip), chz_fmt_kernel (iqd_chan_fmt.hip),
+// chz_gain_kernel (iqd_chan_gain.hip) and chz_track_kernel (iqd_chan_track.hip): the B operand read, the epilogue of one output, the window staging, the prologue
 // (phasor table, a lane's tile parameters and A operands), the accumulate step, the group walk with its Finish and Sink
 // policies, the walkers' block close.
 #pragma once

@@ -9,6 +9,9 @@
 //                [squelch=<dBFS>[,<dBFS>...]] [freqlog=<file>]
 //                [survey=<first_offset_Hz>,<step_Hz>,<count> [surveyshift=<L>] surveylog=<file>] [format=u8|s8|s16]
 //                [agc=off|lowpass|harris[,...]] [rxgain=<dB>[,<dB>...]] [gainlog=<file>]
+//   iqdemod_wide in=cap.iq rate=2048000 tracks=<S> bins=<N> frames=<F> modes=<m>[,...] [gains=<L>[,...]] out=pcm_%d.s16
+//                [blocks=K] [lag=0|1] [minstate=1|2] [tracklog=<file>] [squelch=<dBFS>[,...]]
+//                [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c]
 //
 //   format     what the capture holds: u8 offset binary (an RTL-SDR; the default), s8 signed int8 (hackrf_transfer), s16
 //              little-endian signed int16 (SDRplay, Airspy, USRP, SDR++ / SDR# / SDRangel basebands).  s8 and s16 are for
@@ -44,6 +47,19 @@
 //              point's offset in Hz, the block magnitude, its level in dBFS (iqd_magnitude_dbfs; no gain applied).
 //              surveyshift: the gain shift L of every point (default 0).  With survey=, offsets= (and modes=, out=) may
 //              be left out: then nothing is demodulated and no PCM files are written.  Not together with scan=.
+//   tracks     S channels that follow the band's tracks (include/iqdemod.h: "Track-following channels") in place of
+//              offsets=: per call of K table blocks (blocks=, default 4; a table block is bins x frames samples) the band
+//              spectrum, the activity detector, the tracker and the channelizer's accept are queued on one stream, and
+//              channel s is cut at slot s of the tracker's table, block by block.  bins, frames and the detector's and
+//              tracker's keys are iqdemod_spectrum's, with its defaults (tracks= stands for slots=); bias= is the tracker's
+//              inc_bias and the engine channels' rotation is 0 (the tracker's centre is the station itself).  lag, minstate:
+//              iqd_track_follow's (defaults 0 and 2).  2 bins frames / decimation, the row bytes of a table block, must be a
+//              multiple of 256 and at most 32768 (it is the engine's block), or K of them together.  A capture that ends
+//              inside a call ends with its whole table blocks as one shorter call; a trailing part that does not fill a
+//              table block is dropped and counted on stderr.  Not together with scan=, agc= / rxgain=, a fractional rate or
+//              format=s8|s16.
+//   tracklog   one line per table block and channel: block (from 0, over the whole capture), channel, 1 if the block was
+//              cut (live) else 0, the phase_inc it was cut with as 0x%08x, and that increment as an offset in Hz
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
 #include <math.h>
 #include <stdint.h>
@@ -82,10 +98,207 @@ std::vector<uint64_t> u64List(const char *s)
   return v;
 }
 
+struct TrackArgs {
+  std::string in, out, tracklog;
+  uint32_t m = 0, S = 0, bins = 0, frames = 0, blocks = 4, lag = 0, minstate = 2;
+  double rate = 0;
+  std::vector<double> modes, gains, squelch;
+  iqd_detect_config dc{};
+  iqd_track_config tc{};
+  bool rankGiven = false, edgesGiven = false;
+};
+
+// tracks=: spectrum -> detector -> tracker -> accept_wideband on one stream per call, one synchronise (the downloads)
+int runTracks(const TrackArgs &a)
+{
+  const uint32_t n = a.S, N = a.bins, F = a.frames, M = a.m;
+  const size_t wide_block = (size_t)2 * N * F;             // capture bytes of one table block
+  const size_t bb = wide_block / M;                        // its row bytes
+  if (wide_block % M != 0 || bb % 64 != 0) {
+    fprintf(stderr, "iqdemod_wide: tracks= needs 2 bins frames / decimation to be a multiple of 64\n");
+    return 1;
+  }
+  uint32_t engine_bb = 0;
+  if (bb % 256 == 0 && bb <= 32768) engine_bb = (uint32_t)bb;
+  else if (a.blocks * bb % 256 == 0 && a.blocks * bb <= 32768) engine_bb = (uint32_t)(a.blocks * bb);
+  if (!engine_bb) {
+    fprintf(stderr, "iqdemod_wide: tracks= needs 2 bins frames / decimation (or blocks= of them) to be a multiple of 256, at most 32768\n");
+    return 1;
+  }
+  FILE *f = fopen(a.in.c_str(), "rb");
+  if (!f) {
+    fprintf(stderr, "iqdemod_wide: cannot open %s\n", a.in.c_str());
+    return 1;
+  }
+  std::vector<FILE *> sinks(n);
+  for (uint32_t c = 0; c < n; c++) {
+    char name[4096];
+    snprintf(name, sizeof(name), a.out.c_str(), (int)c);
+    if (!(sinks[c] = fopen(name, "wb"))) {
+      fprintf(stderr, "iqdemod_wide: cannot create %s\n", name);
+      return 1;
+    }
+  }
+  FILE *tlog = nullptr;
+  if (!a.tracklog.empty() && !(tlog = fopen(a.tracklog.c_str(), "w"))) {
+    fprintf(stderr, "iqdemod_wide: cannot create %s\n", a.tracklog.c_str());
+    return 1;
+  }
+  iqd_config cfg{};
+  cfg.abi_version = IQD_ABI_VERSION;
+  cfg.n_channels = n;
+  cfg.block_bytes = engine_bb;
+  cfg.device = -1;
+  iqd_t *e = nullptr;
+  int rc = iqd_create(&cfg, &e);
+  if (rc != IQD_OK) {
+    fprintf(stderr, "iqdemod_wide: iqd_create: %s\n", iqd_strerror(rc));
+    return 1;
+  }
+  iqd_spectrum_config sc{};
+  sc.n_sources = 1;
+  sc.n_bins = N;
+  iqd_detect_config dc = a.dc;
+  dc.n_bins = N;
+  if (!a.rankGiven) dc.floor_rank = N / 2;
+  iqd_track_config tc = a.tc;
+  tc.n_sources = 1;
+  tc.n_bins = N;
+  tc.n_slots = n;
+  tc.max_detections = dc.max_detections;
+  if (!a.edgesGiven) {
+    tc.class_edge[0] = N / 64 + 1;
+    tc.class_edge[1] = N / 16;
+    tc.class_edge[2] = N / 4;
+  }
+  iqd_channelizer_config zc{};
+  zc.n_sources = 1;
+  zc.n_channels = n;
+  zc.decimation = M;
+  iqd_spectrum_t *s = nullptr;
+  iqd_detect_t *d = nullptr;
+  iqd_track_t *t = nullptr;
+  iqd_channelizer_t *z = nullptr;
+  rc = iqd_spectrum_create(e, &sc, &s);
+  if (rc == IQD_OK) rc = iqd_detect_create(e, &dc, &d);
+  if (rc == IQD_OK) rc = iqd_track_create(e, &tc, &t);
+  if (rc == IQD_OK) rc = iqd_channelizer_create(e, &zc, &z);
+  std::vector<uint32_t> source(n, 0), inc(n, 0);
+  std::vector<uint8_t> shift(n);
+  std::vector<int32_t> slot(n);
+  for (uint32_t c = 0; c < n; c++) {
+    shift[c] = (uint8_t)a.gains[c % a.gains.size()];
+    slot[c] = (int32_t)c;
+  }
+  if (rc == IQD_OK) rc = iqd_channelizer_set_channels(z, 0, n, source.data(), inc.data(), shift.data());
+  if (rc == IQD_OK) rc = iqd_channelizer_follow_tracks(z, 0, n, slot.data());
+  for (uint32_t c = 0; c < n && rc == IQD_OK; c++) rc = iqd_set_mode(e, c, 1, (int)a.modes[c % a.modes.size()]);
+  if (rc == IQD_OK) rc = iqd_set_rotation(e, 0, n, 0);
+  for (uint32_t c = 0; c < n && rc == IQD_OK && !a.squelch.empty(); c++)
+    rc = iqd_set_squelch(e, c, 1, (int32_t)a.squelch[c % a.squelch.size()]);
+  const uint32_t K = a.blocks, D = dc.max_detections;
+  const size_t call = K * wide_block, row = K * bb;
+  void *d_wide = nullptr, *d_pow = nullptr, *d_rows = nullptr, *d_det = nullptr, *d_slots = nullptr, *d_blocks = nullptr;
+  void *d_out = nullptr, *d_pcm = nullptr, *d_cnt = nullptr;
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, call, &d_wide);
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)K * N * 4, &d_pow);
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)K * sizeof(iqd_detect_row), &d_rows);
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)K * D * sizeof(iqd_detection), &d_det);
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)K * n * sizeof(iqd_track_slot), &d_slots);
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)K * sizeof(iqd_track_block), &d_blocks);
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)n * row, &d_out);
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)n * (row / 64) * 2, &d_pcm);
+  if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)n * 4, &d_cnt);
+  if (rc != IQD_OK) {
+    fprintf(stderr, "iqdemod_wide: setup: %s (%s)\n", iqd_strerror(rc), iqd_last_error(e));
+    return 1;
+  }
+  std::vector<uint8_t> wide(call);
+  std::vector<int16_t> pcm((size_t)n * (row / 64));
+  std::vector<uint32_t> count(n);
+  std::vector<iqd_track_slot> slots((size_t)K * n);
+  std::vector<uint32_t> carry_live(n, 0), carry_inc(n, 0);   // the tool's copy of the followers' carries, for the log
+  uint64_t block_no = 0;
+  size_t dropped = 0;
+  int status = 0;
+  for (;;) {
+    const size_t got = fread(wide.data(), 1, call, f);
+    const uint32_t nb = (uint32_t)(got / wide_block);
+    dropped += got - nb * wide_block;
+    if (nb == 0) break;
+    const size_t bytes = nb * wide_block, r_bytes = nb * bb;
+    iqd_track_follow tf{};
+    tf.slots_dev = (const iqd_track_slot *)d_slots;
+    tf.n_slots = n;
+    tf.n_blocks = nb;
+    tf.block_bytes = (uint32_t)bb;
+    tf.lag = a.lag;
+    tf.min_state = a.minstate;
+    int r = iqd_dev_upload(e, d_wide, wide.data(), bytes);
+    if (r == IQD_OK) r = iqd_spectrum_run_device(s, d_wide, bytes, F, (uint32_t *)d_pow);
+    if (r == IQD_OK) r = iqd_detect_run_device(d, (const uint32_t *)d_pow, nb, (iqd_detect_row *)d_rows, (iqd_detection *)d_det);
+    if (r == IQD_OK) r = iqd_track_run_device(t, (const iqd_detect_row *)d_rows, (const iqd_detection *)d_det, nb,
+                                              (iqd_track_slot *)d_slots, (iqd_track_block *)d_blocks);
+    if (r == IQD_OK) r = iqd_channelizer_set_track_table(z, &tf);
+    if (r == IQD_OK) r = iqd_accept_wideband_device(e, z, 0, d_wide, bytes, d_out, d_pcm, d_cnt, nullptr, nullptr);
+    if (r == IQD_OK) r = iqd_synchronize(e);
+    if (r == IQD_OK) r = iqd_dev_download(e, pcm.data(), d_pcm, (size_t)n * (r_bytes / 64) * 2);
+    if (r == IQD_OK) r = iqd_dev_download(e, count.data(), d_cnt, (size_t)n * 4);
+    if (r == IQD_OK && tlog) r = iqd_dev_download(e, slots.data(), d_slots, (size_t)nb * n * sizeof(iqd_track_slot));
+    if (r != IQD_OK) {
+      fprintf(stderr, "iqdemod_wide: tracks: %s (%s)\n", iqd_strerror(r), iqd_last_error(e));
+      status = 3;
+      break;
+    }
+    for (uint32_t c = 0; c < n; c++)
+      if (fwrite(&pcm[(size_t)c * (r_bytes / 64)], 2, count[c], sinks[c]) != count[c]) {
+        fprintf(stderr, "iqdemod_wide: write failed\n");
+        status = 1;
+      }
+    if (tlog) {
+      auto decide = [&](uint32_t b, uint32_t c, uint32_t &live, uint32_t &d_inc) {
+        const iqd_track_slot &q = slots[(size_t)b * n + c];
+        live = q.state >= a.minstate ? 1u : 0u;
+        d_inc = live ? q.phase_inc : 0u;
+      };
+      for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t c = 0; c < n; c++) {
+          uint32_t live = carry_live[c], d_inc = carry_inc[c];
+          if (b >= a.lag) decide(b - a.lag, c, live, d_inc);
+          fprintf(tlog, "%llu %u %u 0x%08x %lld\n", (unsigned long long)(block_no + b), c, live, d_inc,
+                  (long long)llround((double)(int32_t)d_inc / 4294967296.0 * a.rate));
+        }
+      for (uint32_t c = 0; c < n; c++) decide(nb - 1, c, carry_live[c], carry_inc[c]);
+    }
+    block_no += nb;
+    if (got < call) break;
+  }
+  if (dropped) fprintf(stderr, "iqdemod_wide: %zu trailing bytes do not fill a table block: dropped\n", dropped);
+  fclose(f);
+  if (tlog) fclose(tlog);
+  for (FILE *q : sinks) fclose(q);
+  iqd_channelizer_destroy(z);
+  iqd_track_destroy(t);
+  iqd_detect_destroy(d);
+  iqd_spectrum_destroy(s);
+  iqd_destroy(e);
+  return status;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
+  TrackArgs ta;
+  ta.dc.ratio_q8 = 2048;
+  ta.dc.dc_guard = 1;
+  ta.dc.bridge = 8;
+  ta.dc.min_width = 3;
+  ta.dc.max_detections = 16;
+  ta.tc.gate_q8 = 512;
+  ta.tc.open_hits = 3;
+  ta.tc.hold_blocks = 2;
+  ta.tc.alpha_q8 = 64;
   std::string in, out, freqlog, surveylog, gainlog;
   uint32_t m = 0, den = 1, blocks = 4;
   bool m_given = false;
@@ -124,6 +337,30 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "format=", 7)) format = a + 7;
     else if (!strncmp(a, "rxgain=", 7)) rxgain = numList(a + 7);
     else if (!strncmp(a, "gainlog=", 8)) gainlog = a + 8;
+    else if (!strncmp(a, "tracks=", 7)) ta.S = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "bins=", 5)) ta.bins = (uint32_t)strtoul(a + 5, nullptr, 10);
+    else if (!strncmp(a, "frames=", 7)) ta.frames = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "lag=", 4)) ta.lag = (uint32_t)strtoul(a + 4, nullptr, 10);
+    else if (!strncmp(a, "minstate=", 9)) ta.minstate = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "tracklog=", 9)) ta.tracklog = a + 9;
+    else if (!strncmp(a, "rank=", 5)) { ta.dc.floor_rank = (uint32_t)strtoul(a + 5, nullptr, 10); ta.rankGiven = true; }
+    else if (!strncmp(a, "ratio_q8=", 9)) ta.dc.ratio_q8 = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "guard=", 6)) ta.dc.dc_guard = (uint32_t)strtoul(a + 6, nullptr, 10);
+    else if (!strncmp(a, "bridge=", 7)) ta.dc.bridge = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "minwidth=", 9)) ta.dc.min_width = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "maxdet=", 7)) ta.dc.max_detections = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "gate_q8=", 8)) ta.tc.gate_q8 = (uint32_t)strtoul(a + 8, nullptr, 10);
+    else if (!strncmp(a, "open=", 5)) ta.tc.open_hits = (uint32_t)strtoul(a + 5, nullptr, 10);
+    else if (!strncmp(a, "hold=", 5)) ta.tc.hold_blocks = (uint32_t)strtoul(a + 5, nullptr, 10);
+    else if (!strncmp(a, "alpha_q8=", 9)) ta.tc.alpha_q8 = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "bias=", 5)) ta.tc.inc_bias = (uint32_t)strtoul(a + 5, nullptr, 0);
+    else if (!strncmp(a, "edges=", 6)) {
+      ta.edgesGiven = sscanf(a + 6, "%u,%u,%u", &ta.tc.class_edge[0], &ta.tc.class_edge[1], &ta.tc.class_edge[2]) == 3;
+      if (!ta.edgesGiven) {
+        fprintf(stderr, "iqdemod_wide: edges= takes three widths in bins, a,b,c\n");
+        return 1;
+      }
+    }
     else if (!strncmp(a, "agc=", 4)) {
       for (const char *q = a + 4;;) {
         const char *c = strchr(q, ',');
@@ -173,6 +410,31 @@ int main(int argc, char **argv)
     fprintf(stderr, "iqdemod_wide: agc= / rxgain= cannot be combined with %s: channels that follow their gain are not built for it yet\n",
             !scan.empty() ? "scan=" : den > 1 ? "a fractional rate" : "format=s8|s16");
     return 1;
+  }
+  if (ta.S) {
+    if (!scan.empty() || gain_following || den > 1 || sample_format != IQD_WIDE_U8) {
+      fprintf(stderr, "iqdemod_wide: tracks= cannot be combined with %s: channels that follow tracks are not built for it yet\n",
+              !scan.empty() ? "scan=" : gain_following ? "agc= / rxgain=" : den > 1 ? "a fractional rate" : "format=s8|s16");
+      return 1;
+    }
+    if (in.empty() || out.empty() || modes.empty() || gains.empty() || m < 2 || rate <= 0 || !blocks || ta.S > 64 || !ta.bins ||
+        !ta.frames || ta.lag > 1 || ta.minstate < 1 || ta.minstate > 2 || !offsets.empty() || !survey.empty()) {
+      fprintf(stderr, "usage: iqdemod_wide in=cap.iq rate=2048000 tracks=S(1..64) bins=N frames=F modes=<m,...> [gains=<L,...>] "
+                      "out=pcm_%%d.s16 [blocks=K] [lag=0|1] [minstate=1|2] [tracklog=file] [squelch=dBFS,...] [rank=] [ratio_q8=] "
+                      "[guard=] [bridge=] [minwidth=] [maxdet=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c]\n"
+                      "  (not with offsets=, survey=, scan=, agc=, rxgain=, a fractional rate or format=s8|s16; the capture's whole table\n"
+                      "  blocks of bins x frames samples are run, a trailing part that does not fill one is dropped and counted)\n");
+      return 1;
+    }
+    ta.in = in;
+    ta.out = out;
+    ta.m = m;
+    ta.rate = rate;
+    ta.blocks = blocks;
+    ta.modes = modes;
+    ta.gains = gains;
+    ta.squelch = squelch;
+    return runTracks(ta);
   }
   const bool surveying = !survey.empty();
   const bool survey_ok = !surveying || (survey.size() == 3 && survey[2] >= 1 && survey[2] <= 4096 && surveyshift <= 8 && !surveylog.empty());

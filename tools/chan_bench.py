@@ -8,6 +8,7 @@ per channel and call, M = 8, default taps.  Prints one JSON line:
     python tools/chan_bench.py --scan [--steps K]      (scanner-driven channels, written to profiles/ as well)
     python tools/chan_bench.py --survey [--decimation 75 --den 8]   (the band survey against rows of real channels)
     python tools/chan_bench.py --gain [--steps K]      (channels that follow their AGC's IF gain)
+    python tools/chan_bench.py --tracks [--steps K]    (channels that follow the slots of a track table)
 
   chan_ms            per call, host clock around iqd_channelizer_run_device + synchronize (median of K steps, after
                      about --settle-ms of the same call untimed, like bench.py's clock settle)
@@ -26,6 +27,14 @@ iqd_channelizer_run + iqd_accept_iq with iqd_scanner_get + iqd_channelizer_tunin
 --gain: every channel follows its gain (iqd_channelizer_follow_gain), FM with a running Harris AGC; each call is 4 blocks
 (block_bytes 32768), the same size as --scan's.  gain_call_ms: iqd_accept_wideband_device + synchronize; fixed_call_ms:
 the same call with the channels fixed (chz_kernel, AGC running open loop); rows_accept_ms and walker_ms as for --scan.
+
+--tracks: every channel follows a slot of a track table (iqd_channelizer_follow_tracks): a synthetic table, S = 64, every
+slot active, the increments new in every block, channel c on slot c mod 64 of its source; each call is 4 table blocks
+(block_bytes 32768).  tracks_ms: iqd_channelizer_run_device + synchronize (chz_track_kernel and the history kernel: to hold
+against --chan-only's chan_ms); tracks_fm_ms: iqd_accept_wideband_device + synchronize with the FM accept behind (against
+chan_fm_ms).  host_loop_ms_16: the host-driven loop for 16 followers of one source - per block a slot download,
+set_channels with their phase_inc, iqd_channelizer_run of one block, 0x80 over the rows not live, iqd_accept_iq - and
+tracks_fm_ms_16, the same 16 channels through the table.
 
 --survey: 16 sources, 2^16 outputs each, a 12.5 kHz grid of 163 points per source (2608 virtual channels), block_bytes
 32768.  survey_ms: iqd_channelizer_survey_device + synchronize; grid_run_ms: iqd_channelizer_run_device for 2608 real
@@ -65,6 +74,7 @@ def main():
     ap.add_argument("--chan-only", action="store_true", help="only the channelizer calls (counter runs)")
     ap.add_argument("--scan", action="store_true", help="scanner-driven channels (see above)")
     ap.add_argument("--gain", action="store_true", help="gain-following channels (see above)")
+    ap.add_argument("--tracks", action="store_true", help="track-following channels (see above)")
     ap.add_argument("--survey", action="store_true", help="the band survey against run_device on the same grid (see above)")
     ap.add_argument("--grid-only", action="store_true", help="with --survey: only grid_run_ms (a build without the survey)")
     ap.add_argument("--decimation", type=int, default=8, help="M, or P of a fractional decimation P / Q")
@@ -78,6 +88,8 @@ def main():
         return survey_bench(capi, args)
     if args.gain:
         return gain_bench(capi, args)
+    if args.tracks:
+        return tracks_bench(capi, args)
 
     M, Q, n_src, n_ch, n_out = args.decimation, args.den, 16, 4096, 1 << 16
     B = 2 if args.format == "s16" else 1               # bytes per rail (white bytes are full-scale in every format)
@@ -259,6 +271,62 @@ def gain_bench(capi, args):
     z.close(); eng.close()
     line.update(gain_call_ms=round(gain_ms, 4), rows_accept_ms=round(rows_ms, 4), walker_ms=round(gain_ms - rows_ms, 4),
                 fixed_call_ms=round(fixed_ms, 4))
+    print(json.dumps(line))
+
+
+def _tracks_setup(capi, n_ch, n_src, M, n_out, nblk=4, S=64):
+    from rtlsdrdiags_amd import synth
+    bps = n_out * 2 * M
+    row = bps // M
+    eng = capi.Engine(n_ch)
+    eng.set_mode("fm")
+    rng = np.random.default_rng(1)
+    z = capi.Channelizer(eng, M, n_ch, n_src)
+    z.set_channels(0, source=np.arange(n_ch) % n_src, gain_shift=np.full(n_ch, 3))
+    table = np.zeros((n_src, nblk, S), capi.TRACK_SLOT)     # the kernel cannot tell it from a tracker's output
+    table["track_id"] = np.arange(1, S + 1)
+    table["state"] = 2
+    table["phase_inc"] = rng.integers(0, 2 ** 32, table.shape, dtype=np.uint64)
+    d_tab = eng.dev_alloc(table.nbytes)
+    eng.dev_upload(d_tab, table.view(np.uint8).reshape(-1))
+    z.follow_tracks(np.arange(n_ch) % S)
+    z.set_track_table(d_tab, S, nblk, row // nblk, 0, 2)
+    d_in, d_rows = eng.dev_alloc(n_src * bps), eng.dev_alloc(n_ch * row)
+    d_pcm, d_cnt = eng.dev_alloc(n_ch * row // 64 * 2), eng.dev_alloc(n_ch * 4)
+    eng.dev_upload(d_in, np.concatenate([synth.white_u8(bps // 2, seed=s) for s in range(n_src)]))
+    run = lambda: z.run_device(d_in, bps, d_rows)
+    call = lambda: eng.accept_wideband_device(z, d_in, bps, d_rows, d_pcm, d_cnt)
+    return eng, z, run, call, (table, d_tab)
+
+
+def tracks_bench(capi, args):
+    from rtlsdrdiags_amd import synth
+    M, n_out, nblk = 8, 1 << 16, 4
+    line = {"workload": "track-following channelizer, 4096 ch / 16 sources / M=8 / default taps / 2^16 outputs (4 table blocks) "
+                        "per call / S=64, every slot active"}
+    eng, z, run, call, _ = _tracks_setup(capi, 4096, 16, M, n_out)
+    t, f = [], []
+    for _ in range(3):
+        t.append(round(timed(run, eng.synchronize, args.steps, args.settle_ms)[0], 4))
+        f.append(round(timed(call, eng.synchronize, args.steps, args.settle_ms)[0], 4))
+    z.close(); eng.close()
+    line.update(tracks_ms=t, tracks_fm_ms=f)
+    # 16 followers of one source: through the table, and the host-driven loop of one-block calls
+    eng, z, run, call, (table, d_tab) = _tracks_setup(capi, 16, 1, M, n_out)
+    line["tracks_fm_ms_16"] = round(timed(call, eng.synchronize, args.steps, args.settle_ms)[0], 4)
+    z.follow_tracks(None)
+    wide = synth.white_u8(n_out * M, seed=0).reshape(1, -1)
+    blk_bytes = wide.shape[1] // nblk
+
+    def loop():
+        for b in range(nblk):
+            slots = eng.dev_download(d_tab, table.nbytes).view(capi.TRACK_SLOT).reshape(table.shape)[0, b, :16]
+            z.set_channels(0, phase_inc=slots["phase_inc"])
+            r = z.run(wide[:, b * blk_bytes:(b + 1) * blk_bytes])
+            r[slots["state"] < 2] = 0x80
+            eng.accept(r)
+    line["host_loop_ms_16"] = round(timed(loop, eng.synchronize, max(5, args.steps // 5), args.settle_ms)[0], 4)
+    z.close(); eng.close()
     print(json.dumps(line))
 
 

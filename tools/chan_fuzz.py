@@ -18,6 +18,9 @@ Gain cases (channels that follow their engine channel's IF gain, iqd_channelizer
 tests/chan_gain_model.py on oracle chains) are drawn only when asked: FUZZ_GAIN=1 makes every case one, and nothing else
 draws them, so that a seed without it is the cases it always was.
 
+Track cases (channels that follow the slots of a track table, iqd_channelizer_follow_tracks, against
+tests/chan_track_model.py) are drawn only when asked as well: FUZZ_TRACK=1 makes every case one.
+
 Format cases (signed captures: sample_format "s8" / "s16", chz_fmt_kernel, against tests/chan_fmt_model.py) are drawn only
 when asked as well: FUZZ_FMT=1 makes every case one.  Such a case is drawn without a GPU (draw_fmt) and then run (run_fmt):
 M, taps, sources, channels, calls and the operator's steps as in a plain case, the long calls sized by
@@ -44,6 +47,8 @@ from tests import chan_model as cm                     # noqa: E402
 from tests import chan_mutants as mu                   # noqa: E402
 from tests import chan_scan_model as sm                # noqa: E402
 from tests import chan_survey_model as svm             # noqa: E402
+from tests import chan_track_cases as tkc              # noqa: E402
+from tests import chan_track_model as tkm              # noqa: E402
 
 K_EDGES = (1, 31, 32, 33, 255, 256, 257, 1023, 1024)
 INC_EDGES = (0, 1, 2 ** 31, 2 ** 31 - 1, 2 ** 32 - 1)
@@ -51,7 +56,8 @@ BOUND_SUM = (2 ** 31 - 256) // 256
 SLICES = {"plain": ((9101, 150), (9102, 150)), "scan": (9103, 40),   # (seed, cases): tests/test_gpu_chan_fuzz.py's
           "survey": (9104, 40),                                       # tests/test_gpu_chan_survey_fuzz.py's
           "gain": (9105, 24),                                         # tests/test_gpu_chan_gain_fuzz.py's
-          "fmt": (9106, 36)}                                          # tests/test_gpu_chan_fmt_fuzz.py's
+          "fmt": (9106, 36),                                          # tests/test_gpu_chan_fmt_fuzz.py's
+          "track": (9107, 24)}                                        # tests/test_gpu_chan_track_fuzz.py's
 MODEL_BUDGET = 4e7        # tap x wideband-sample products the model may spend per case (chan_model convolves at the
 #                           wide rate: K M outputs per channel); fewer channels are compared when a case is past it
 
@@ -650,6 +656,148 @@ def scan_case(rng, ctx):
     return run_scan(ctx, M, taps, h, n_src, n_ch, bb, calls, rng, check=check)
 
 
+# ------------------------------------------------------------------------------------------------------ track cases
+def track_case(rng, ctx):
+    """Track-following and fixed channels of one channelizer against chan_track_model.Follower (fixed ones against
+    chan_model): M, taps (K up to 1024: both kernel forms), sources, channels, S, block_bytes (64 ... 4096, no multiple of the
+    window among them), blocks per call, lag, min_state and the call form drawn; a new synthetic table per call; between calls
+    followers stop, start or move to another slot, and now and then the channelizer is reset.  Rows in the three forms that
+    return them, PCM, magnitudes and flags against oracle chains in the two accept forms.  None, or what differed."""
+    P = ctx.P
+    M = int(rng.choice([2, 3, 7, 8, 16, 64])) if rng.random() < 0.7 else int(rng.integers(2, 65))
+    taps, h = draw_taps(rng, M)
+    K = len(h)
+    n_src = int(rng.integers(1, 4))
+    n_ch = min(draw_count(rng), 130)
+    S = int(rng.choice([1, 2, 8, 64])) if rng.random() < 0.6 else int(rng.integers(1, 65))
+    bb = 64 * int(rng.choice([1, 1, 2, 3, 4, 8, 16, 40, 64]))
+    nblk = int(rng.integers(1, 7))
+    while nblk * bb > 16384:
+        nblk -= 1
+    n_calls = int(rng.integers(2, 5))
+    lag, min_state = int(rng.integers(0, 2)), int(rng.integers(1, 3))
+    form = ("run", "run_device", "accept", "accept_device")[int(rng.integers(0, 4))]
+    row = nblk * bb
+    engine_bb = 256 if row % 256 == 0 else 32768               # whole engine blocks, or one short block
+    src = rng.integers(0, n_src, n_ch).astype(np.uint32)
+    inc = np.array([draw_inc(rng) for _ in range(n_ch)], np.uint64)
+    shift = rng.integers(0, 9, n_ch).astype(np.uint8)
+    slot = np.where(rng.random(n_ch) < 0.7, rng.integers(0, S, n_ch), -1).astype(np.int32)
+    if not (slot >= 0).any():
+        slot[0] = 0
+    n_samp = n_calls * row // 2 * M
+    wide = np.stack([draw_input(rng, M, n_samp)[1] for _ in range(n_src)])
+    per = max(1, K * row // 2 * M * n_calls)
+    check = sorted(rng.choice(n_ch, min(n_ch, max(2, int(MODEL_BUDGET // per))), replace=False).tolist())
+    window = min(capi.channelizer_window_outputs(M, K), capi.channelizer_track_window_outputs(M, K))
+    ctx.count("track cases")
+    ctx.count("large K cases", K > 256)
+    ctx.count("two-window cases", bb // 2 > window)
+    eng = capi.Engine(n_ch, block_bytes=engine_bb)
+    eng.set_mode("fm")
+    eng.set_squelch(-45)
+    z = capi.Channelizer(eng, M, n_ch, n_src, taps=taps)
+    z.set_channels(0, source=src, phase_inc=inc, gain_shift=shift)
+    z.follow_tracks(slot)
+    fol = {c: tkm.Follower(h, M, P, src[c], shift[c], max(int(slot[c]), 0), channel=c, window=window) for c in check}
+    chains = {}
+    if form.startswith("accept"):
+        for c in check:
+            chains[c] = ctx.oracle.chain()
+            chains[c].set_mode("fm")
+            chains[c].set_squelch(-45)
+    log, pos, bad, keep = [], 0, None, []
+    span = row * M
+    for i in range(n_calls):
+        if i and rng.random() < 0.6:                           # between calls: stop, start or move a follower; or a reset
+            if rng.random() < 0.25:
+                z.reset()
+                for f in fol.values():
+                    f.reset()
+                pos = 0
+                log.append((i, "reset"))
+                ctx.count("track resets")
+            else:
+                c = int(rng.integers(0, n_ch))
+                new = -1 if slot[c] >= 0 and rng.random() < 0.5 else int(rng.integers(0, S))
+                if new != slot[c]:
+                    z.follow_tracks([new], first=c)
+                    slot[c] = new
+                    if c in fol and new >= 0:
+                        fol[c].start(new)
+                    log.append((i, c, "slot", new))
+                    ctx.count("track toggles")
+        table = tkc.synthetic_table(rng, n_src, nblk, S, nblk)
+        d_t = eng.dev_alloc(table.nbytes)
+        keep.append(d_t)
+        eng.dev_upload(d_t, table.view(np.uint8).reshape(-1))
+        if not (slot >= 0).any():                              # (every follower stopped: the call needs no table)
+            z.set_track_table(None)
+        else:
+            z.set_track_table(d_t, S, nblk, bb, lag, min_state)
+        piece = np.ascontiguousarray(wide[:, pos * span:(pos + 1) * span])
+        rows = acc = None
+        if form == "run":
+            rows = z.run(piece)
+        elif form == "accept":
+            acc = eng.accept_wideband(z, piece)
+        else:
+            d_w, d_r = eng.dev_alloc(piece.nbytes), eng.dev_alloc(n_ch * row)
+            eng.dev_upload(d_w, piece)
+            if form == "run_device":
+                z.run_device(d_w, span, d_r)
+                eng.synchronize()
+            else:
+                nb_e = max(1, row // engine_bb)
+                d_p, d_c, d_m, d_a = eng.dev_alloc(n_ch * row // 64 * 2), eng.dev_alloc(4 * n_ch), eng.dev_alloc(4 * n_ch * nb_e), eng.dev_alloc(n_ch * nb_e)
+                eng.accept_wideband_device(z, d_w, span, d_r, d_p, d_c, d_m, d_a)
+                eng.synchronize()
+                acc = (eng.dev_download(d_p, n_ch * row // 64 * 2, np.int16).reshape(n_ch, -1), eng.dev_download(d_c, 4 * n_ch, np.uint32),
+                       eng.dev_download(d_m, 4 * n_ch * nb_e, np.uint32).reshape(n_ch, nb_e), eng.dev_download(d_a, n_ch * nb_e).reshape(n_ch, nb_e))
+                for d in (d_p, d_c, d_m, d_a):
+                    eng.dev_free(d)
+            rows = eng.dev_download(d_r, n_ch * row).reshape(n_ch, row)
+            eng.dev_free(d_w)
+            eng.dev_free(d_r)
+        for c in check:
+            wide_row = wide[src[c], :(pos + 1) * span]
+            if slot[c] >= 0:
+                want = fol[c].call(wide_row, table, bb, lag, min_state)
+                live = (want.reshape(nblk, bb) != 0x80).any(axis=1)
+                ctx.count("track blocks", nblk)
+                ctx.count("live blocks", live.sum())
+            else:
+                m0 = pos * row // 2
+                want = cm.channel(wide_row, h, M, int(inc[c]), int(shift[c]), P, m_range=(m0, m0 + row // 2))
+                fol[c].skip(row // 2)
+            what = None
+            if rows is not None and not np.array_equal(rows[c], want):
+                what = "rows (first at byte %d)" % int(np.nonzero(rows[c] != want)[0][0])
+            if what is None and acc is not None:
+                p_, mg, al = chains[c].accept_stream(want, block_bytes=min(engine_bb, len(want)))
+                pcm, cnt, mag, alw = acc
+                if cnt[c] != len(p_) or not np.array_equal(pcm[c, :cnt[c]], p_):
+                    what = "pcm"
+                elif not np.array_equal(mag[c], mg) or not np.array_equal(alw[c], al):
+                    what = "magnitude / flags"
+            if what is not None:
+                bad = ("track case: M=%d K=%d (%s) sources=%d channels=%d S=%d block_bytes=%d blocks=%d lag=%d min_state=%d form=%s: "
+                       "call %d, channel %d (source %d, slot %d, L %d) differs in %s; ops %r" % (
+                           M, K, "default taps" if taps is None else "drawn taps", n_src, n_ch, S, bb, nblk, lag, min_state, form, i, c,
+                           int(src[c]), int(slot[c]), int(shift[c]), what, log))
+                break
+        pos += 1
+        if bad is not None:
+            break
+    for ch in chains.values():
+        ch.close()
+    z.close()
+    for d in keep:
+        eng.dev_free(d)
+    eng.close()
+    return bad
+
+
 # ------------------------------------------------------------------------------------------------------ gain cases
 def gain_case(rng, ctx):
     """Gain-following and fixed channels of one channelizer through iqd_accept_wideband_device, against
@@ -1021,12 +1169,15 @@ def main():
     mode, fmode, smode = os.environ.get("FUZZ_SCAN"), os.environ.get("FUZZ_FRAC"), os.environ.get("FUZZ_SURVEY")
     gmode = os.environ.get("FUZZ_GAIN") == "1"
     tmode = os.environ.get("FUZZ_FMT") == "1"
+    kmode = os.environ.get("FUZZ_TRACK") == "1"
 
     def one():
         if gmode:                                          # (asked for: no draw decides it, the other kinds draw as ever)
             return False, gain_case(rng, ctx)
         if tmode:                                          # (asked for as well)
             return False, fmt_case(rng, ctx)
+        if kmode:
+            return False, track_case(rng, ctx)
         r = rng.random() if mode is None else 1.0
         scan = mode == "1" or (mode is None and r < 0.125)
         if scan:
