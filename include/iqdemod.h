@@ -831,6 +831,80 @@ int iqd_channelizer_set_track_table(iqd_channelizer_t *z, const iqd_track_follow
 int iqd_channelizer_follow_tracks(iqd_channelizer_t *z, uint32_t first, uint32_t n, const int32_t *slot);
 uint32_t iqd_channelizer_track_window_outputs(uint32_t decimation, uint32_t n_taps);
 
+/* Band track measurements: what a track IS - for every (source, block, slot) the power over the noise floor, the occupied
+ * bandwidth in the ITU sense (the band that holds all but beta of the power at each end), the share of the power that sits
+ * in the carrier, and from those a mode hint.  A stateless object queued on the engine's stream straight behind
+ * iqd_track_run_device; it reads the spectrum's power rows again, which the tracker never does.  Every quantity is an unsigned
+ * integer and every step is fixed here, so results are exact; there are no floats.
+ *
+ *   input     power_dev[n_sources][n_blocks][N] uint32 (iqd_spectrum_run_device's, any values up to 2^32 - 1 are legal);
+ *             rows_dev[n_sources][n_blocks] (iqd_detect_run_device's; only floor is read);
+ *             slots_dev[n_sources][n_blocks][S] (iqd_track_run_device's; only track_id, state, first_bin and last_bin are
+ *             read, and they must be what the tracker writes: first_bin <= last_bin < N).
+ *   config    N = n_bins 64 ... 2048, a power of two; S = n_slots 1 ... 64; d = dc_guard 0 ... N / 4 (the detector's meaning);
+ *             m = margin 0 ... 64; beta = obw_tail_q16 0 ... 32767; c = carrier_half 0 ... 8; min_sum any; carrier_min_q8
+ *             0 ... 256; wide_bins 1 ... N + 1; n_sources >= 1; reserved 0.
+ *   entry     (j, b, s): t = slots[j][b][s], p = power[j][b], f = rows[j][b].floor.
+ *   measured  iff t.state != 0.  A free slot, and a slot in its closing block (state 0 with track_id still set), gives 32
+ *             zero bytes.
+ *   excess    e[k] = p[k] > f ? p[k] - f : 0, and e[k] = 0 for the guard bins N / 2 - d < k < N / 2 + d.
+ *   window    lo = max(first_bin - m, 0), hi = min(last_bin + m, N - 1); everything below is over lo .. hi.
+ *   sums      sum_excess E = sum e (uint64; below 2^32 x 2^11 = 2^43); n_over = the number of bins with e > 0;
+ *             peak_excess = max e; peak_bin = the lowest bin that has it.
+ *   empty     E = 0: flags = IQD_MEASURE_F_EMPTY, track_id stays, every other field is 0.
+ *   weak      E < min_sum: flag IQD_MEASURE_F_WEAK; the fields are computed all the same; hint = IQD_HINT_NONE.
+ *   centroid  centroid_q8 = floor(256 sum k e[k] / E), k the absolute bin: sum k e < 2^11 x 2^43 = 2^54, its 256-fold < 2^62.
+ *   obw       L(k) = sum over lo .. k of e, R(k) = sum over k .. hi of e.  obw_lo = the least k with 65536 L(k) > beta E,
+ *             obw_hi = the greatest k with 65536 R(k) > beta E; both products are below 2^16 x 2^43 = 2^59.  obw_lo <= obw_hi
+ *             always: with a = obw_lo, L(a - 1) <= beta E / 65536 (or a = lo and L(a - 1) = 0), so
+ *             65536 R(a) = 65536 (E - L(a - 1)) >= (65536 - beta) E > beta E for beta <= 32767 and E > 0: a passes obw_hi's test.
+ *   carrier   C = sum e over max(lo, peak_bin - c) .. min(hi, peak_bin + c); carrier_q8 = floor(256 C / E), 0 ... 256.
+ *   hint      of a measured entry that is neither weak nor empty: IQD_HINT_WIDE if obw_hi - obw_lo + 1 >= wide_bins, otherwise
+ *             IQD_HINT_CARRIER if carrier_q8 >= carrier_min_q8, otherwise IQD_HINT_NARROW.
+ *   limits    the hint is a hint; the measurements are the product.  It sees one block's power and nothing else: an
+ *             unmodulated FM carrier (a pause in speech) looks like CARRIER; a sideband signal has no carrier at all and looks
+ *             like NARROW; a strong neighbour inside the margin is measured with the track.  Nothing is smoothed across
+ *             blocks; the host decides what to do with a block's hints.
+ *   output    meas_dev[n_sources][n_blocks][S], defined in full after every call.
+ *   refusals  IQD_EINVAL with a message naming the argument, before anything is allocated or queued, the stream intact: a
+ *             NULL pointer, a field outside its range, a non-zero reserved word; at run: n_blocks 0, n_sources n_blocks above
+ *             2^31 - 1, a device pointer that is NULL or not 16-byte aligned.
+ * The _device form is queued and returns once queued; the host form takes host pointers and returns when done. */
+typedef struct iqd_measure_config {
+    uint32_t n_sources;       /* >= 1 */
+    uint32_t n_bins;          /* N: 64 ... 2048, a power of two */
+    uint32_t n_slots;         /* S: 1 ... 64, the tracker's */
+    uint32_t dc_guard;        /* d: 0 ... N / 4, the detector's */
+    uint32_t margin;          /* m: 0 ... 64 bins added on each side of the track's run */
+    uint32_t obw_tail_q16;    /* beta: 0 ... 32767, the share of the power left outside at EACH end (328: 0.5 %) */
+    uint32_t carrier_half;    /* c: 0 ... 8 bins on each side of the peak that count as carrier */
+    uint32_t min_sum;         /* below this sum of excess power a track is weak and gets no hint */
+    uint32_t carrier_min_q8;  /* 0 ... 256 */
+    uint32_t wide_bins;       /* 1 ... N + 1 (N + 1 is never reached) */
+    uint32_t reserved[2];     /* 0 */
+} iqd_measure_config;
+typedef struct iqd_track_measure {   /* 32 bytes */
+    uint32_t track_id;
+    uint16_t obw_lo, obw_hi, peak_bin;
+    uint8_t  flags, hint;
+    uint32_t peak_excess, centroid_q8;
+    uint16_t carrier_q8, n_over;
+    uint64_t sum_excess;
+} iqd_track_measure;
+#define IQD_MEASURE_F_EMPTY 1
+#define IQD_MEASURE_F_WEAK 2
+#define IQD_HINT_NONE 0
+#define IQD_HINT_CARRIER 1
+#define IQD_HINT_NARROW 2
+#define IQD_HINT_WIDE 3
+typedef struct iqd_measure iqd_measure_t;
+int iqd_measure_create(iqd_t *e, const iqd_measure_config *cfg, iqd_measure_t **out);
+void iqd_measure_destroy(iqd_measure_t *m);   /* before its engine's iqd_destroy */
+int iqd_measure_run_device(iqd_measure_t *m, const uint32_t *power_dev, const iqd_detect_row *rows_dev, const iqd_track_slot *slots_dev,
+                           size_t n_blocks, iqd_track_measure *meas_dev);
+int iqd_measure_run(iqd_measure_t *m, const uint32_t *power, const iqd_detect_row *rows, const iqd_track_slot *slots, size_t n_blocks,
+                    iqd_track_measure *meas);
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

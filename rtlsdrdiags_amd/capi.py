@@ -76,6 +76,22 @@ TRACK_SLOT = np.dtype([("track_id", "<u4"), ("state", "u1"), ("flags", "u1"), ("
 TRACK_BLOCK = np.dtype([("n_active", "<u4"), ("n_tentative", "<u4"), ("n_opened_closed", "<u4"), ("n_unplaced", "<u4")])
 
 
+class MeasureConfig(C.Structure):
+    """iqd_measure_config (include/iqdemod.h: "Band track measurements")"""
+    _fields_ = [("n_sources", C.c_uint32), ("n_bins", C.c_uint32), ("n_slots", C.c_uint32), ("dc_guard", C.c_uint32),
+                ("margin", C.c_uint32), ("obw_tail_q16", C.c_uint32), ("carrier_half", C.c_uint32), ("min_sum", C.c_uint32),
+                ("carrier_min_q8", C.c_uint32), ("wide_bins", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# iqd_track_measure (include/iqdemod.h: "Band track measurements"), 32 bytes
+TRACK_MEASURE = np.dtype([("track_id", "<u4"), ("obw_lo", "<u2"), ("obw_hi", "<u2"), ("peak_bin", "<u2"), ("flags", "u1"),
+                          ("hint", "u1"), ("peak_excess", "<u4"), ("centroid_q8", "<u4"), ("carrier_q8", "<u2"),
+                          ("n_over", "<u2"), ("sum_excess", "<u8")])
+MEASURE_F_EMPTY, MEASURE_F_WEAK = 1, 2
+HINT_NONE, HINT_CARRIER, HINT_NARROW, HINT_WIDE = 0, 1, 2, 3
+HINT_MODE = {HINT_NONE: "fm", HINT_CARRIER: "am", HINT_NARROW: "fm", HINT_WIDE: "wbfm"}   # what iqdemod_wide modes=auto sets
+
+
 class TrackFollow(C.Structure):
     """iqd_track_follow (include/iqdemod.h: "Track-following channels")"""
     _fields_ = [("slots_dev", C.c_void_p), ("n_slots", C.c_uint32), ("n_blocks", C.c_uint32), ("block_bytes", C.c_uint32),
@@ -114,6 +130,7 @@ EXPORTS = [
     "iqd_detect_create", "iqd_detect_destroy", "iqd_detect_run_device", "iqd_detect_run", "iqd_detect_offset_hz",
     "iqd_track_create", "iqd_track_destroy", "iqd_track_reset", "iqd_track_run_device", "iqd_track_run", "iqd_track_get_state",
     "iqd_track_phase_inc",
+    "iqd_measure_create", "iqd_measure_destroy", "iqd_measure_run_device", "iqd_measure_run",
     "iqd_channelizer_set_track_table", "iqd_channelizer_follow_tracks", "iqd_channelizer_track_window_outputs",
 ]
 
@@ -244,6 +261,11 @@ def _lib():
     L.iqd_track_run.argtypes = [vp, vp, vp, sz, vp, vp]
     L.iqd_track_get_state.argtypes = [vp, u32, vp]
     L.iqd_track_phase_inc.argtypes = [u32, u32, u32, C.POINTER(u32)]
+    L.iqd_measure_create.argtypes = [vp, C.POINTER(MeasureConfig), C.POINTER(vp)]
+    L.iqd_measure_destroy.argtypes = [vp]
+    L.iqd_measure_destroy.restype = None
+    L.iqd_measure_run_device.argtypes = [vp, vp, vp, vp, sz, vp]
+    L.iqd_measure_run.argtypes = [vp, vp, vp, vp, sz, vp]
     L.iqd_channelizer_set_track_table.argtypes = [vp, C.POINTER(TrackFollow)]
     L.iqd_channelizer_follow_tracks.argtypes = [vp, u32, u32, vp]
     L.iqd_channelizer_track_window_outputs.argtypes = [u32, u32]
@@ -1111,6 +1133,69 @@ class Tracker:
         """iqd_track_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
         if self._h and self._e._h:
             self._L.iqd_track_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+
+def measure_defaults(n_bins):
+    """the thresholds used where none are given (DESIGN 4.15 has the measurements they were chosen from): a margin of
+    N / 256 bins, 0.5 % of the power left outside at each end, a carrier of the peak bin and one on each side, no hint under
+    a sum of 4096, CARRIER from 160 / 256 of the power in the carrier, WIDE from an occupied band of N / 32 bins"""
+    n = int(n_bins)
+    return dict(margin=max(n // 256, 1), obw_tail_q16=328, carrier_half=1, min_sum=4096, carrier_min_q8=160, wide_bins=max(n // 32, 2))
+
+
+class Measure:
+    """iqd_measure_*: what every track of a Tracker's table is in a block - the excess power over the Detector's floor in the
+    track's run widened by `margin` bins, the occupied bandwidth that leaves obw_tail_q16 / 65536 of it outside at each end,
+    the share of it within carrier_half bins of the peak, and a mode hint (HINT_*) from wide_bins and carrier_min_q8.
+    n_bins and dc_guard are the Detector's, n_slots the Tracker's.  Stateless."""
+
+    def __init__(self, engine, n_bins, n_sources=1, n_slots=8, dc_guard=1, margin=None, obw_tail_q16=None, carrier_half=None,
+                 min_sum=None, carrier_min_q8=None, wide_bins=None, reserved=(0, 0)):
+        self._e, self._L = engine, engine._L
+        self._h = None
+        self.n_bins, self.n_sources, self.n_slots = int(n_bins), int(n_sources), int(n_slots)
+        given = dict(margin=margin, obw_tail_q16=obw_tail_q16, carrier_half=carrier_half, min_sum=min_sum,
+                     carrier_min_q8=carrier_min_q8, wide_bins=wide_bins)
+        v = dict(measure_defaults(n_bins), **{k: x for k, x in given.items() if x is not None})
+        cfg = MeasureConfig(*[int(x) & 0xffffffff for x in (n_sources, n_bins, n_slots, dc_guard, v["margin"], v["obw_tail_q16"],
+                                                            v["carrier_half"], v["min_sum"], v["carrier_min_q8"], v["wide_bins"])])
+        for i in range(2):
+            cfg.reserved[i] = int(reserved[i]) & 0xffffffff
+        h = C.c_void_p()
+        engine._check(self._L.iqd_measure_create(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        if not hasattr(engine, "_children"):
+            engine._children = weakref.WeakSet()
+        engine._children.add(self)
+
+    def run(self, power, rows, slots):
+        """power [n_sources, n_blocks, n_bins] uint32, rows [n_sources, n_blocks] DETECT_ROW, slots [n_sources, n_blocks,
+        n_slots] TRACK_SLOT (host arrays: Spectrum.run's, Detector.run's and Tracker.run's) -> [n_sources, n_blocks, n_slots]
+        TRACK_MEASURE."""
+        if getattr(power, "dtype", None) != np.uint32 or getattr(rows, "dtype", None) != DETECT_ROW or getattr(slots, "dtype", None) != TRACK_SLOT:
+            raise TypeError("power is uint32, rows are DETECT_ROW and slots TRACK_SLOT arrays")
+        rows = np.ascontiguousarray(rows).reshape(self.n_sources, -1)
+        nb = rows.shape[1]
+        power = np.ascontiguousarray(power).reshape(self.n_sources, nb, self.n_bins)
+        slots = np.ascontiguousarray(slots).reshape(self.n_sources, nb, self.n_slots)
+        meas = np.zeros((self.n_sources, nb, self.n_slots), TRACK_MEASURE)
+        one = np.zeros(64, np.uint8)                              # (a refused call gets valid pointers all the same)
+        self._e._check(self._L.iqd_measure_run(self._h, _np_ptr(power if nb else one), _np_ptr(rows if nb else one),
+                                               _np_ptr(slots if nb else one), nb, _np_ptr(meas if nb else one)))
+        return meas
+
+    def run_device(self, power_dev, rows_dev, slots_dev, n_blocks, meas_dev):
+        """iqd_measure_run_device: device pointers (integers), queued on the engine's stream."""
+        self._e._check(self._L.iqd_measure_run_device(self._h, C.c_void_p(power_dev or None), C.c_void_p(rows_dev or None),
+                                                      C.c_void_p(slots_dev or None), int(n_blocks), C.c_void_p(meas_dev or None)))
+
+    def close(self):
+        """iqd_measure_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
+        if self._h and self._e._h:
+            self._L.iqd_measure_destroy(self._h)
         self._h = None
 
     __del__ = close

@@ -3,7 +3,8 @@
 //
 //   iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] out=power.u32 [log=spectrum.txt]
 //                    [detect=runs.txt [rank=512] [ratio_q8=2048] [guard=1] [bridge=8] [minwidth=3] [maxdet=16]
-//                     [track=tracks.txt [slots=8] [gate_q8=512] [open=3] [hold=2] [alpha_q8=64] [bias=0] [edges=a,b,c]]]
+//                     [track=tracks.txt [slots=8] [gate_q8=512] [open=3] [hold=2] [alpha_q8=64] [bias=0] [edges=a,b,c]
+//                      [measure=meas.txt [margin=] [beta_q16=328] [carrier=1] [minsum=4096] [carrier_q8=160] [wide=]]]]
 //
 //   in       interleaved I/Q, one byte per rail
 //   rate     the capture's sample rate in Hz (for the log's offsets only)
@@ -25,6 +26,12 @@
 //            0x%08x, the offsets in Hz of its first and last bin, class.  Unplaced detections are counted on stderr.
 //   slots gate_q8 open hold alpha_q8 bias edges   iqd_track_config's n_slots, gate_q8, open_hits, hold_blocks, alpha_q8,
 //            inc_bias, class_edge (left out: bins / 64 + 1, bins / 16, bins / 4 bins)
+//   measure  needs track=.  The track measurements (include/iqdemod.h: "Band track measurements") run on the device behind the
+//            tracker, on the same stream.  One line per measured record (a live slot): block, slot, id, the offsets in Hz of
+//            obw_lo, obw_hi and the peak bin (iqd_detect_offset_hz of the bin's middle, 256 k + 128) and of the centroid,
+//            carrier_q8, sum_excess, flags, hint (0 none, 1 carrier, 2 narrow, 3 wide).
+//   margin beta_q16 carrier minsum carrier_q8 wide   iqd_measure_config's margin (left out: bins / 256, at least 1),
+//            obw_tail_q16, carrier_half, min_sum, carrier_min_q8, wide_bins (left out: bins / 32); dc_guard is guard=
 // A capture that ends inside a block ends with its last whole block; the rest is dropped and counted on stderr.
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
 #include <math.h>
@@ -62,7 +69,14 @@ bool readWindow(const std::string &path, std::vector<int16_t> &v)
 
 int main(int argc, char **argv)
 {
-  std::string in, out, log, windowPath, detectPath, trackPath, format = "u8";
+  std::string in, out, log, windowPath, detectPath, trackPath, measurePath, format = "u8";
+  iqd_measure_config mc{};
+  mc.n_sources = 1;
+  mc.obw_tail_q16 = 328;
+  mc.carrier_half = 1;
+  mc.min_sum = 4096;
+  mc.carrier_min_q8 = 160;
+  bool marginGiven = false, wideGiven = false;
   iqd_track_config tc{};
   tc.n_sources = 1;
   tc.n_slots = 8;
@@ -104,6 +118,13 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "hold=", 5)) tc.hold_blocks = (uint32_t)strtoul(a + 5, nullptr, 10);
     else if (!strncmp(a, "alpha_q8=", 9)) tc.alpha_q8 = (uint32_t)strtoul(a + 9, nullptr, 10);
     else if (!strncmp(a, "bias=", 5)) tc.inc_bias = (uint32_t)strtoul(a + 5, nullptr, 0);
+    else if (!strncmp(a, "measure=", 8)) measurePath = a + 8;
+    else if (!strncmp(a, "margin=", 7)) { mc.margin = (uint32_t)strtoul(a + 7, nullptr, 10); marginGiven = true; }
+    else if (!strncmp(a, "beta_q16=", 9)) mc.obw_tail_q16 = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "carrier=", 8)) mc.carrier_half = (uint32_t)strtoul(a + 8, nullptr, 10);
+    else if (!strncmp(a, "minsum=", 7)) mc.min_sum = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "carrier_q8=", 11)) mc.carrier_min_q8 = (uint32_t)strtoul(a + 11, nullptr, 10);
+    else if (!strncmp(a, "wide=", 5)) { mc.wide_bins = (uint32_t)strtoul(a + 5, nullptr, 10); wideGiven = true; }
     else if (!strncmp(a, "edges=", 6)) {
       edgesGiven = sscanf(a + 6, "%u,%u,%u", &tc.class_edge[0], &tc.class_edge[1], &tc.class_edge[2]) == 3;
       if (!edgesGiven) {
@@ -120,10 +141,15 @@ int main(int argc, char **argv)
   if (in.empty() || out.empty() || bins == 0 || frames == 0 || frames > (1u << 24) || !(rate > 0.0) || (!u8 && format != "s8")) {
     fprintf(stderr, "usage: iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] "
                     "out=power.u32 [log=spectrum.txt] [detect=runs.txt [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=] "
-                    "[track=tracks.txt [slots=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c]]]\n");
+                    "[track=tracks.txt [slots=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c] "
+                    "[measure=meas.txt [margin=] [beta_q16=] [carrier=] [minsum=] [carrier_q8=] [wide=]]]]\n");
     return 1;
   }
-  const bool detect = !detectPath.empty(), track = !trackPath.empty();
+  const bool detect = !detectPath.empty(), track = !trackPath.empty(), measure = !measurePath.empty();
+  if (measure && !track) {
+    fprintf(stderr, "iqdemod_spectrum: measure= needs track=\n");
+    return 1;
+  }
   if (track && !detect) {
     fprintf(stderr, "iqdemod_spectrum: track= needs detect=\n");
     return 1;
@@ -142,7 +168,8 @@ int main(int argc, char **argv)
   FILE *flog = fout && !log.empty() ? fopen(log.c_str(), "w") : nullptr;
   FILE *fdet = fout && detect ? fopen(detectPath.c_str(), "w") : nullptr;
   FILE *ftrk = fout && track ? fopen(trackPath.c_str(), "w") : nullptr;
-  if (!fin || !fout || (!log.empty() && !flog) || (detect && !fdet) || (track && !ftrk)) {
+  FILE *fmsr = fout && measure ? fopen(measurePath.c_str(), "w") : nullptr;
+  if (!fin || !fout || (!log.empty() && !flog) || (detect && !fdet) || (track && !ftrk) || (measure && !fmsr)) {
     fprintf(stderr, "iqdemod_spectrum: cannot open the files\n");
     return 1;
   }
@@ -204,6 +231,24 @@ int main(int argc, char **argv)
     }
   }
 
+  iqd_measure_t *ms = nullptr;
+  if (measure) {
+    mc.n_bins = bins;
+    mc.n_slots = tc.n_slots;
+    mc.dc_guard = dc.dc_guard;
+    if (!marginGiven) mc.margin = bins / 256 ? bins / 256 : 1;
+    if (!wideGiven) mc.wide_bins = bins / 32;
+    rc = iqd_measure_create(e, &mc, &ms);
+    if (rc != IQD_OK) {
+      fprintf(stderr, "iqdemod_spectrum: iqd_measure_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      iqd_track_destroy(t);
+      iqd_detect_destroy(d);
+      iqd_spectrum_destroy(s);
+      iqd_destroy(e);
+      return 1;
+    }
+  }
+
   // whole blocks, up to about 16 MiB of capture per call
   const size_t blockBytes = (size_t)2 * bins * frames;
   const size_t perCall = blockBytes >= (16u << 20) ? 1 : (16u << 20) / blockBytes;
@@ -217,8 +262,10 @@ int main(int argc, char **argv)
   std::vector<iqd_detection> dets(detect ? perCall * dc.max_detections : 0);
   std::vector<iqd_track_slot> slots(track ? perCall * tc.n_slots : 0);
   std::vector<iqd_track_block> tblocks(track ? perCall : 0);
+  std::vector<iqd_track_measure> meas(measure ? perCall * tc.n_slots : 0);
   uint64_t unplaced = 0;
   void *wideDev = nullptr, *powerDev = nullptr, *rowsDev = nullptr, *detDev = nullptr, *slotsDev = nullptr, *tblocksDev = nullptr;
+  void *measDev = nullptr;
   if (detect) {
     rc = iqd_dev_alloc(e, buf.size(), &wideDev);
     if (rc == IQD_OK) rc = iqd_dev_alloc(e, power.size() * sizeof(uint32_t), &powerDev);
@@ -226,8 +273,10 @@ int main(int argc, char **argv)
     if (rc == IQD_OK) rc = iqd_dev_alloc(e, dets.size() * sizeof(iqd_detection), &detDev);
     if (rc == IQD_OK && track) rc = iqd_dev_alloc(e, slots.size() * sizeof(iqd_track_slot), &slotsDev);
     if (rc == IQD_OK && track) rc = iqd_dev_alloc(e, tblocks.size() * sizeof(iqd_track_block), &tblocksDev);
+    if (rc == IQD_OK && measure) rc = iqd_dev_alloc(e, meas.size() * sizeof(iqd_track_measure), &measDev);
     if (rc != IQD_OK) {
       fprintf(stderr, "iqdemod_spectrum: iqd_dev_alloc: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      iqd_measure_destroy(ms);
       iqd_track_destroy(t);
       iqd_detect_destroy(d);
       iqd_spectrum_destroy(s);
@@ -250,14 +299,18 @@ int main(int argc, char **argv)
         if (rc == IQD_OK && track)
           rc = iqd_track_run_device(t, (const iqd_detect_row *)rowsDev, (const iqd_detection *)detDev, nb, (iqd_track_slot *)slotsDev,
                                     (iqd_track_block *)tblocksDev);
+        if (rc == IQD_OK && measure)
+          rc = iqd_measure_run_device(ms, (const uint32_t *)powerDev, (const iqd_detect_row *)rowsDev, (const iqd_track_slot *)slotsDev, nb,
+                                      (iqd_track_measure *)measDev);
         if (rc == IQD_OK) rc = iqd_dev_download(e, power.data(), powerDev, nb * bins * sizeof(uint32_t));
         if (rc == IQD_OK) rc = iqd_dev_download(e, rows.data(), rowsDev, nb * sizeof(iqd_detect_row));
         if (rc == IQD_OK) rc = iqd_dev_download(e, dets.data(), detDev, nb * dc.max_detections * sizeof(iqd_detection));
         if (rc == IQD_OK && track) rc = iqd_dev_download(e, slots.data(), slotsDev, nb * tc.n_slots * sizeof(iqd_track_slot));
         if (rc == IQD_OK && track) rc = iqd_dev_download(e, tblocks.data(), tblocksDev, nb * sizeof(iqd_track_block));
+        if (rc == IQD_OK && measure) rc = iqd_dev_download(e, meas.data(), measDev, nb * tc.n_slots * sizeof(iqd_track_measure));
       }
       if (rc != IQD_OK) {
-        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", track ? "spectrum, detector and tracker" : detect ? "spectrum and detector" : "iqd_spectrum_run", iqd_strerror(rc), iqd_last_error(e));
+        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", measure ? "spectrum, detector, tracker and measurements" : track ? "spectrum, detector and tracker" : detect ? "spectrum and detector" : "iqd_spectrum_run", iqd_strerror(rc), iqd_last_error(e));
         status = 3;
         break;
       }
@@ -296,6 +349,18 @@ int main(int argc, char **argv)
                   r.width_class);
         }
       }
+      for (size_t b = 0; measure && b < nb; b++)
+        for (uint32_t k = 0; k < tc.n_slots; k++) {
+          const iqd_track_measure &r = meas[b * tc.n_slots + k];
+          if (r.track_id == 0) continue;
+          int64_t lo = 0, hi = 0, peak = 0, cen = 0;
+          iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.obw_lo + 128u, &lo);
+          iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.obw_hi + 128u, &hi);
+          iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.peak_bin + 128u, &peak);
+          iqd_detect_offset_hz(bins, (uint32_t)rate, r.centroid_q8, &cen);
+          fprintf(fmsr, "%llu %u %u %lld %lld %lld %lld %u %llu %u %u\n", (unsigned long long)(block + b), k, r.track_id, (long long)lo,
+                  (long long)hi, (long long)peak, (long long)cen, r.carrier_q8, (unsigned long long)r.sum_excess, r.flags, r.hint);
+        }
       block += nb;
     }
     if (got < buf.size()) break;
@@ -303,8 +368,9 @@ int main(int argc, char **argv)
   if (dropped) fprintf(stderr, "iqdemod_spectrum: %zu bytes after the last whole block dropped\n", dropped);
   if (pastMax) fprintf(stderr, "iqdemod_spectrum: %llu runs past maxdet not written\n", (unsigned long long)pastMax);
   if (unplaced) fprintf(stderr, "iqdemod_spectrum: %llu detections found no free slot\n", (unsigned long long)unplaced);
-  for (void *p : {wideDev, powerDev, rowsDev, detDev, slotsDev, tblocksDev})
+  for (void *p : {wideDev, powerDev, rowsDev, detDev, slotsDev, tblocksDev, measDev})
     if (p) iqd_dev_free(e, p);
+  iqd_measure_destroy(ms);
   iqd_track_destroy(t);
   iqd_detect_destroy(d);
   iqd_spectrum_destroy(s);
@@ -314,5 +380,6 @@ int main(int argc, char **argv)
   if (flog && fclose(flog) != 0) status = status ? status : 1;
   if (fdet && fclose(fdet) != 0) status = status ? status : 1;
   if (ftrk && fclose(ftrk) != 0) status = status ? status : 1;
+  if (fmsr && fclose(fmsr) != 0) status = status ? status : 1;
   return status;
 }

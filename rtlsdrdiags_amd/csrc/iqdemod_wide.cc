@@ -12,6 +12,7 @@
 //   iqdemod_wide in=cap.iq rate=2048000 tracks=<S> bins=<N> frames=<F> modes=<m>[,...] [gains=<L>[,...]] out=pcm_%d.s16
 //                [blocks=K] [lag=0|1] [minstate=1|2] [tracklog=<file>] [squelch=<dBFS>[,...]]
 //                [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c]
+//                [measlog=<file>] [margin=] [beta_q16=] [carrier=] [minsum=] [carrier_q8=] [wide=]      (and modes=auto)
 //
 //   format     what the capture holds: u8 offset binary (an RTL-SDR; the default), s8 signed int8 (hackrf_transfer), s16
 //              little-endian signed int16 (SDRplay, Airspy, USRP, SDR++ / SDR# / SDRangel basebands).  s8 and s16 are for
@@ -60,6 +61,18 @@
 //              format=s8|s16.
 //   tracklog   one line per table block and channel: block (from 0, over the whole capture), channel, 1 if the block was
 //              cut (live) else 0, the phase_inc it was cut with as 0x%08x, and that increment as an offset in Hz
+//   modes=auto with tracks=: every channel starts as FM and the track measurements (include/iqdemod.h: "Band track
+//              measurements"; the keys margin ... wide are iqdemod_spectrum's, with its defaults) are queued behind the tracker
+//              in every call.  After a call the tool looks, per slot, at the track_id the slot has in the call's last block
+//              in which it is active: if it has not decided for that id yet, it takes the hint that most of the call's blocks
+//              in which this id is active give (ties go to the lowest hint; blocks without a hint do not vote) and sets
+//              the channel's mode with iqd_set_mode - CARRIER am, NARROW fm, WIDE wbfm, no hint at all fm.  THE MODE IS IN
+//              FORCE FROM THE NEXT CALL ON - a lag of one call (blocks= table blocks): the call that first sees a track
+//              active is still demodulated with the mode the channel had.  The mode then stays while that track_id lives.
+//              The hint is a hint: an unmodulated FM carrier looks like am, a sideband signal like fm.
+//   measlog    tracks= only, with or without modes=auto.  One line per measured record: "m", block (from 0, over the whole
+//              capture), slot, id, flags, hint, obw_hi - obw_lo + 1 in bins, carrier_q8, sum_excess; and one line per mode
+//              the tool sets: "mode", the first block of the call that decided it, slot, id, the mode (1 am 2 fm 3 wbfm).
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
 #include <math.h>
 #include <stdint.h>
@@ -99,7 +112,9 @@ std::vector<uint64_t> u64List(const char *s)
 }
 
 struct TrackArgs {
-  std::string in, out, tracklog;
+  std::string in, out, tracklog, measlog;
+  iqd_measure_config mc{};
+  bool autoModes = false, marginGiven = false, wideGiven = false;
   uint32_t m = 0, S = 0, bins = 0, frames = 0, blocks = 4, lag = 0, minstate = 2;
   double rate = 0;
   std::vector<double> modes, gains, squelch;
@@ -171,6 +186,20 @@ int runTracks(const TrackArgs &a)
     tc.class_edge[1] = N / 16;
     tc.class_edge[2] = N / 4;
   }
+  const bool measuring = a.autoModes || !a.measlog.empty();
+  iqd_measure_config mc = a.mc;
+  mc.n_sources = 1;
+  mc.n_bins = N;
+  mc.n_slots = n;
+  mc.dc_guard = dc.dc_guard;
+  if (!a.marginGiven) mc.margin = N / 256 ? N / 256 : 1;
+  if (!a.wideGiven) mc.wide_bins = N / 32;
+  iqd_measure_t *ms = nullptr;
+  FILE *mlog = nullptr;
+  if (!a.measlog.empty() && !(mlog = fopen(a.measlog.c_str(), "w"))) {
+    fprintf(stderr, "iqdemod_wide: cannot create %s\n", a.measlog.c_str());
+    return 1;
+  }
   iqd_channelizer_config zc{};
   zc.n_sources = 1;
   zc.n_channels = n;
@@ -182,6 +211,7 @@ int runTracks(const TrackArgs &a)
   rc = iqd_spectrum_create(e, &sc, &s);
   if (rc == IQD_OK) rc = iqd_detect_create(e, &dc, &d);
   if (rc == IQD_OK) rc = iqd_track_create(e, &tc, &t);
+  if (rc == IQD_OK && measuring) rc = iqd_measure_create(e, &mc, &ms);
   if (rc == IQD_OK) rc = iqd_channelizer_create(e, &zc, &z);
   std::vector<uint32_t> source(n, 0), inc(n, 0);
   std::vector<uint8_t> shift(n);
@@ -199,7 +229,7 @@ int runTracks(const TrackArgs &a)
   const uint32_t K = a.blocks, D = dc.max_detections;
   const size_t call = K * wide_block, row = K * bb;
   void *d_wide = nullptr, *d_pow = nullptr, *d_rows = nullptr, *d_det = nullptr, *d_slots = nullptr, *d_blocks = nullptr;
-  void *d_out = nullptr, *d_pcm = nullptr, *d_cnt = nullptr;
+  void *d_out = nullptr, *d_pcm = nullptr, *d_cnt = nullptr, *d_meas = nullptr;
   if (rc == IQD_OK) rc = iqd_dev_alloc(e, call, &d_wide);
   if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)K * N * 4, &d_pow);
   if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)K * sizeof(iqd_detect_row), &d_rows);
@@ -209,6 +239,7 @@ int runTracks(const TrackArgs &a)
   if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)n * row, &d_out);
   if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)n * (row / 64) * 2, &d_pcm);
   if (rc == IQD_OK) rc = iqd_dev_alloc(e, (size_t)n * 4, &d_cnt);
+  if (rc == IQD_OK && measuring) rc = iqd_dev_alloc(e, (size_t)K * n * sizeof(iqd_track_measure), &d_meas);
   if (rc != IQD_OK) {
     fprintf(stderr, "iqdemod_wide: setup: %s (%s)\n", iqd_strerror(rc), iqd_last_error(e));
     return 1;
@@ -218,6 +249,10 @@ int runTracks(const TrackArgs &a)
   std::vector<uint32_t> count(n);
   std::vector<iqd_track_slot> slots((size_t)K * n);
   std::vector<uint32_t> carry_live(n, 0), carry_inc(n, 0);   // the tool's copy of the followers' carries, for the log
+  std::vector<iqd_track_measure> meas(measuring ? (size_t)K * n : 0);
+  std::vector<uint32_t> decided(n, 0);                       // modes=auto: the track_id each channel's mode was chosen for
+  std::vector<int> current(n);
+  for (uint32_t c = 0; c < n; c++) current[c] = (int)a.modes[c % a.modes.size()];
   uint64_t block_no = 0;
   size_t dropped = 0;
   int status = 0;
@@ -239,12 +274,16 @@ int runTracks(const TrackArgs &a)
     if (r == IQD_OK) r = iqd_detect_run_device(d, (const uint32_t *)d_pow, nb, (iqd_detect_row *)d_rows, (iqd_detection *)d_det);
     if (r == IQD_OK) r = iqd_track_run_device(t, (const iqd_detect_row *)d_rows, (const iqd_detection *)d_det, nb,
                                               (iqd_track_slot *)d_slots, (iqd_track_block *)d_blocks);
+    if (r == IQD_OK && measuring)
+      r = iqd_measure_run_device(ms, (const uint32_t *)d_pow, (const iqd_detect_row *)d_rows, (const iqd_track_slot *)d_slots, nb,
+                                 (iqd_track_measure *)d_meas);
     if (r == IQD_OK) r = iqd_channelizer_set_track_table(z, &tf);
     if (r == IQD_OK) r = iqd_accept_wideband_device(e, z, 0, d_wide, bytes, d_out, d_pcm, d_cnt, nullptr, nullptr);
     if (r == IQD_OK) r = iqd_synchronize(e);
     if (r == IQD_OK) r = iqd_dev_download(e, pcm.data(), d_pcm, (size_t)n * (r_bytes / 64) * 2);
     if (r == IQD_OK) r = iqd_dev_download(e, count.data(), d_cnt, (size_t)n * 4);
-    if (r == IQD_OK && tlog) r = iqd_dev_download(e, slots.data(), d_slots, (size_t)nb * n * sizeof(iqd_track_slot));
+    if (r == IQD_OK && (tlog || measuring)) r = iqd_dev_download(e, slots.data(), d_slots, (size_t)nb * n * sizeof(iqd_track_slot));
+    if (r == IQD_OK && measuring) r = iqd_dev_download(e, meas.data(), d_meas, (size_t)nb * n * sizeof(iqd_track_measure));
     if (r != IQD_OK) {
       fprintf(stderr, "iqdemod_wide: tracks: %s (%s)\n", iqd_strerror(r), iqd_last_error(e));
       status = 3;
@@ -270,14 +309,48 @@ int runTracks(const TrackArgs &a)
         }
       for (uint32_t c = 0; c < n; c++) decide(nb - 1, c, carry_live[c], carry_inc[c]);
     }
+    for (uint32_t b = 0; mlog && b < nb; b++)
+      for (uint32_t c = 0; c < n; c++) {
+        const iqd_track_measure &q = meas[(size_t)b * n + c];
+        if (q.track_id)
+          fprintf(mlog, "m %llu %u %u %u %u %u %u %llu\n", (unsigned long long)(block_no + b), c, q.track_id, q.flags, q.hint,
+                  q.flags & IQD_MEASURE_F_EMPTY ? 0u : q.obw_hi - q.obw_lo + 1u, q.carrier_q8, (unsigned long long)q.sum_excess);
+      }
+    for (uint32_t c = 0; a.autoModes && c < n && status == 0; c++) {
+      uint32_t id = 0;
+      for (uint32_t b = 0; b < nb; b++)
+        if (slots[(size_t)b * n + c].state == IQD_TRACK_ACTIVE) id = slots[(size_t)b * n + c].track_id;
+      if (id == 0 || id == decided[c]) continue;
+      uint32_t votes[4] = {0, 0, 0, 0};
+      for (uint32_t b = 0; b < nb; b++) {
+        const iqd_track_slot &q = slots[(size_t)b * n + c];
+        if (q.state == IQD_TRACK_ACTIVE && q.track_id == id) votes[meas[(size_t)b * n + c].hint & 3]++;
+      }
+      uint32_t hint = IQD_HINT_NONE;
+      for (uint32_t h = IQD_HINT_CARRIER; h <= IQD_HINT_WIDE; h++)
+        if (votes[h] > (hint ? votes[hint] : 0u)) hint = h;
+      const int mode = hint == IQD_HINT_CARRIER ? 1 : hint == IQD_HINT_WIDE ? 3 : 2;
+      const int r2 = mode == current[c] ? IQD_OK : iqd_set_mode(e, c, 1, mode);   // (a channel that has the mode is left alone)
+      current[c] = mode;
+      if (r2 != IQD_OK) {
+        fprintf(stderr, "iqdemod_wide: iqd_set_mode: %s (%s)\n", iqd_strerror(r2), iqd_last_error(e));
+        status = 3;
+        break;
+      }
+      decided[c] = id;
+      if (mlog) fprintf(mlog, "mode %llu %u %u %d\n", (unsigned long long)block_no, c, id, mode);
+    }
+    if (status == 3) break;
     block_no += nb;
     if (got < call) break;
   }
   if (dropped) fprintf(stderr, "iqdemod_wide: %zu trailing bytes do not fill a table block: dropped\n", dropped);
   fclose(f);
   if (tlog) fclose(tlog);
+  if (mlog) fclose(mlog);
   for (FILE *q : sinks) fclose(q);
   iqd_channelizer_destroy(z);
+  iqd_measure_destroy(ms);
   iqd_track_destroy(t);
   iqd_detect_destroy(d);
   iqd_spectrum_destroy(s);
@@ -299,6 +372,10 @@ int main(int argc, char **argv)
   ta.tc.open_hits = 3;
   ta.tc.hold_blocks = 2;
   ta.tc.alpha_q8 = 64;
+  ta.mc.obw_tail_q16 = 328;
+  ta.mc.carrier_half = 1;
+  ta.mc.min_sum = 4096;
+  ta.mc.carrier_min_q8 = 160;
   std::string in, out, freqlog, surveylog, gainlog;
   uint32_t m = 0, den = 1, blocks = 4;
   bool m_given = false;
@@ -323,6 +400,7 @@ int main(int argc, char **argv)
     }
     else if (!strncmp(a, "rate=", 5)) rate = atof(a + 5);
     else if (!strncmp(a, "offsets=", 8)) offsets = numList(a + 8);
+    else if (!strcmp(a, "modes=auto")) { ta.autoModes = true; modes = {2.0}; }
     else if (!strncmp(a, "modes=", 6)) modes = numList(a + 6);
     else if (!strncmp(a, "gains=", 6)) gains = numList(a + 6);
     else if (!strncmp(a, "blocks=", 7)) blocks = (uint32_t)atoi(a + 7);
@@ -343,6 +421,13 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "lag=", 4)) ta.lag = (uint32_t)strtoul(a + 4, nullptr, 10);
     else if (!strncmp(a, "minstate=", 9)) ta.minstate = (uint32_t)strtoul(a + 9, nullptr, 10);
     else if (!strncmp(a, "tracklog=", 9)) ta.tracklog = a + 9;
+    else if (!strncmp(a, "measlog=", 8)) ta.measlog = a + 8;
+    else if (!strncmp(a, "margin=", 7)) { ta.mc.margin = (uint32_t)strtoul(a + 7, nullptr, 10); ta.marginGiven = true; }
+    else if (!strncmp(a, "beta_q16=", 9)) ta.mc.obw_tail_q16 = (uint32_t)strtoul(a + 9, nullptr, 10);
+    else if (!strncmp(a, "carrier=", 8)) ta.mc.carrier_half = (uint32_t)strtoul(a + 8, nullptr, 10);
+    else if (!strncmp(a, "minsum=", 7)) ta.mc.min_sum = (uint32_t)strtoul(a + 7, nullptr, 10);
+    else if (!strncmp(a, "carrier_q8=", 11)) ta.mc.carrier_min_q8 = (uint32_t)strtoul(a + 11, nullptr, 10);
+    else if (!strncmp(a, "wide=", 5)) { ta.mc.wide_bins = (uint32_t)strtoul(a + 5, nullptr, 10); ta.wideGiven = true; }
     else if (!strncmp(a, "rank=", 5)) { ta.dc.floor_rank = (uint32_t)strtoul(a + 5, nullptr, 10); ta.rankGiven = true; }
     else if (!strncmp(a, "ratio_q8=", 9)) ta.dc.ratio_q8 = (uint32_t)strtoul(a + 9, nullptr, 10);
     else if (!strncmp(a, "guard=", 6)) ta.dc.dc_guard = (uint32_t)strtoul(a + 6, nullptr, 10);
@@ -411,6 +496,10 @@ int main(int argc, char **argv)
             !scan.empty() ? "scan=" : den > 1 ? "a fractional rate" : "format=s8|s16");
     return 1;
   }
+  if (!ta.S && (ta.autoModes || !ta.measlog.empty())) {
+    fprintf(stderr, "iqdemod_wide: modes=auto and measlog= need tracks=\n");
+    return 1;
+  }
   if (ta.S) {
     if (!scan.empty() || gain_following || den > 1 || sample_format != IQD_WIDE_U8) {
       fprintf(stderr, "iqdemod_wide: tracks= cannot be combined with %s: channels that follow tracks are not built for it yet\n",
@@ -421,9 +510,13 @@ int main(int argc, char **argv)
         !ta.frames || ta.lag > 1 || ta.minstate < 1 || ta.minstate > 2 || !offsets.empty() || !survey.empty()) {
       fprintf(stderr, "usage: iqdemod_wide in=cap.iq rate=2048000 tracks=S(1..64) bins=N frames=F modes=<m,...> [gains=<L,...>] "
                       "out=pcm_%%d.s16 [blocks=K] [lag=0|1] [minstate=1|2] [tracklog=file] [squelch=dBFS,...] [rank=] [ratio_q8=] "
+                      "[measlog=file] [margin=] [beta_q16=] [carrier=] [minsum=] [carrier_q8=] [wide=] "
                       "[guard=] [bridge=] [minwidth=] [maxdet=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c]\n"
                       "  (not with offsets=, survey=, scan=, agc=, rxgain=, a fractional rate or format=s8|s16; the capture's whole table\n"
-                      "  blocks of bins x frames samples are run, a trailing part that does not fill one is dropped and counted)\n");
+                      "  blocks of bins x frames samples are run, a trailing part that does not fill one is dropped and counted;\n"
+                      "  modes=auto: every channel starts as fm, and the mode chosen from a track's measured hints - carrier am,\n"
+                      "  narrow fm, wide wbfm - is in force from the call AFTER the one that first sees the track active: a lag of\n"
+                      "  one call)\n");
       return 1;
     }
     ta.in = in;
