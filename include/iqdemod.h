@@ -905,6 +905,101 @@ int iqd_measure_run_device(iqd_measure_t *m, const uint32_t *power_dev, const iq
 int iqd_measure_run(iqd_measure_t *m, const uint32_t *power, const iqd_detect_row *rows, const iqd_track_slot *slots, size_t n_blocks,
                     iqd_track_measure *meas);
 
+/* Band track log: what the band DID - a running summary of every (source, slot) over its track's whole life, across blocks
+ * and calls, a mode hint voted over every measured block so far, and one compact event record when a track ends: when, where,
+ * how wide, what kind.  A stateful object queued on the engine's stream straight behind iqd_measure_run_device; capture ->
+ * spectrum -> detector -> tracker -> measurements -> log stays one stream and one synchronise, and the host reads a handful
+ * of 64-byte events instead of whole tables.  Integers only; every step is fixed here, so results are exact.
+ *
+ *   input     slots_dev[n_sources][n_blocks][S] (iqd_track_run_device's; of a slot only track_id, state, width_class and
+ *             centre_q8 are read); meas_dev[n_sources][n_blocks][S] (iqd_measure_run_device's).
+ *   config    S = n_slots 1 ... 64; E = max_events 1 ... 65536; min_active 1 ... 65535; vote_min 1 ... 65535; n_sources >= 1;
+ *             reserved 0.
+ *   state     per source: a uint64 block index g - the blocks of the source seen since create / reset - and S summaries.  It
+ *             persists across calls until iqd_tracklog_reset (all zero).  Sources are independent; the blocks of a source are
+ *             processed in order.
+ *   a block   per slot: t = the table's slot, m = its measurement record, st = the slot's summary.  st.flags becomes 0 first.
+ *     0 vanished    st.track_id != 0 and t.track_id != st.track_id: the track ends LOST.  It is an event - st as it stands, with
+ *                   flags = IQD_TLOG_F_LOST - if st.n_active >= min_active; otherwise it counts in n_short.  st becomes
+ *                   all-zero bytes.  This covers a tracker reset between calls, a tentative slot dropped at its first miss,
+ *                   and any foreign table.
+ *     1 start       t.track_id != 0 and st.track_id == 0: st.track_id = t.track_id, first_block = g, flag NEW,
+ *                   obw_lo_min = 0xffff (and is shown as such until a block votes).
+ *                   After steps 0 and 1 st.track_id == t.track_id.  A table slot with track_id 0 is free whatever its state
+ *                   says: steps 2 to 4 apply only where st.track_id != 0 (the tracker never writes such a slot; a foreign
+ *                   table could, and a summary must not gather blocks under no id).
+ *     2 accumulate  if t.state != 0: n_blocks += 1; state = t.state; width_class = t.width_class.  If t.state == 2:
+ *                   n_active += 1, sum_centre_q8 += t.centre_q8.  The block VOTES iff m.track_id == t.track_id and
+ *                   m.flags == 0 (neither empty nor weak); then n_measured += 1, sum_excess += m.sum_excess,
+ *                   peak_excess = max(peak_excess, m.peak_excess), obw_lo_min = min(obw_lo_min, m.obw_lo),
+ *                   obw_hi_max = max(obw_hi_max, m.obw_hi), and if m.hint is 1, 2 or 3: votes[m.hint - 1] += 1 (any other
+ *                   hint value adds to no vote).  Counters are mod 2^32.
+ *     3 decide      V = votes[0] + votes[1] + votes[2] (mod 2^32 like the counters).  mode_hint = 0 while V < vote_min;
+ *                   otherwise the hint with the most votes, ties to the lowest hint.  Flag MODE_CHANGED if it differs from
+ *                   the value st had before this block (0 -> x included).
+ *     4 close       t.state == 0 (the tracker's closing block: state 0 with the id still set): flag CLOSED, state = 0.  It is
+ *                   an event if n_active >= min_active; otherwise it counts in n_short.  The block's output shows this final
+ *                   record; afterwards st is all-zero bytes.
+ *     5 advance     g += 1, once per block of the source.
+ *   output    all three arrays are defined in full after every call.
+ *             summary_dev[n_sources][n_blocks][S]: st as it stands after the block (before step 4's zeroing); a free slot is
+ *             64 zero bytes.
+ *             events_dev[n_sources][E]: the call's events of that source, ordered by block and within a block by ascending
+ *             slot (a slot ends at most one track that is an event per block: a track that starts and closes in one block
+ *             has n_active 0 < min_active).  An event is the summary as it stood when the track ended.  Entries from n_stored
+ *             on are zero bytes.
+ *             counts_dev[n_sources]: n_events counts all events of the call, n_stored = min(n_events, E), n_lost those of
+ *             n_events that are LOST, n_short the ended tracks that were no event (mod 2^32; 2^32 events need 2^32 table
+ *             entries of 128 bytes in and out, more than a device holds).
+ *   calls     a call of b1 + b2 blocks gives the summaries of a call of b1 followed by one of b2; its events are the two
+ *             calls' events concatenated and its counts their sums, as long as E is not exceeded.
+ *   get_state the source's S summaries as they stand after the last block (flags included; a track closed in that block is
+ *             zero bytes already) and g.  Synchronises.
+ *   mean      iqd_tracklog_mean_centre(sum_centre_q8, n_active): floor(sum / n) on the host, no GPU; with
+ *             iqd_track_phase_inc the track's mean tuning.  IQD_EINVAL: n_active 0, centre_q8 NULL, or a quotient of 2^32 or more (no
+ *             sum of centres below 2^19 gives one).
+ *   bounds    centre_q8 < 2^19, so sum_centre_q8 stays below 2^51 over 2^32 blocks.  m.sum_excess < 2^43 per block: the uint64
+ *             sum_excess wraps only after 2^21 voting blocks of saturated rows, hence mod 2^64.
+ *   refusals  IQD_EINVAL with a message naming the argument, before anything is allocated or queued, the stream intact: a
+ *             NULL pointer, a field outside its range, a non-zero reserved word; at run: n_blocks 0, n_sources n_blocks above
+ *             2^31 - 1, a device pointer that is NULL or not 16-byte aligned; get_state: source >= n_sources.
+ * The _device form is queued and returns once queued; the host form takes host pointers and returns when done;
+ * iqd_tracklog_reset is queued. */
+typedef struct iqd_tracklog_config {
+    uint32_t n_sources;   /* >= 1 */
+    uint32_t n_slots;     /* S: 1 ... 64, the tracker's */
+    uint32_t max_events;  /* E: 1 ... 65536 event records per source and call */
+    uint32_t min_active;  /* 1 ... 65535: a track that ends with fewer active blocks is not an event */
+    uint32_t vote_min;    /* 1 ... 65535: votes needed before a mode is decided */
+    uint32_t reserved[3]; /* 0 */
+} iqd_tracklog_config;
+typedef struct iqd_track_summary {       /* 64 bytes, naturally aligned */
+    uint32_t track_id;                   /* 0: free */
+    uint8_t  state, flags, mode_hint, width_class;
+    uint64_t first_block;                /* the source's block index g at which the log first saw the track */
+    uint32_t n_blocks, n_active;         /* blocks seen live (state != 0) / active (state 2) */
+    uint32_t n_measured, votes[3];       /* blocks that voted; votes for IQD_HINT_CARRIER / NARROW / WIDE */
+    uint64_t sum_centre_q8;              /* sum of the slot's centre_q8 over its active blocks */
+    uint64_t sum_excess;                 /* sum of sum_excess over the blocks that voted, mod 2^64 */
+    uint32_t peak_excess;                /* max over the blocks that voted */
+    uint16_t obw_lo_min, obw_hi_max;     /* extremes over the blocks that voted */
+} iqd_track_summary;
+#define IQD_TLOG_F_NEW 1           /* first block of this summary */
+#define IQD_TLOG_F_MODE_CHANGED 2  /* mode_hint differs from the previous block's (0 -> x included) */
+#define IQD_TLOG_F_CLOSED 4        /* the tracker closed the track in this block */
+#define IQD_TLOG_F_LOST 8          /* events only: the track vanished from its slot without a closing block */
+typedef struct iqd_tracklog_counts { uint32_t n_events, n_stored, n_short, n_lost; } iqd_tracklog_counts;
+typedef struct iqd_tracklog iqd_tracklog_t;
+int iqd_tracklog_create(iqd_t *e, const iqd_tracklog_config *cfg, iqd_tracklog_t **out);
+void iqd_tracklog_destroy(iqd_tracklog_t *t);   /* before its engine's iqd_destroy */
+int iqd_tracklog_reset(iqd_tracklog_t *t);
+int iqd_tracklog_run_device(iqd_tracklog_t *t, const iqd_track_slot *slots_dev, const iqd_track_measure *meas_dev, size_t n_blocks,
+                            iqd_track_summary *summary_dev, iqd_track_summary *events_dev, iqd_tracklog_counts *counts_dev);
+int iqd_tracklog_run(iqd_tracklog_t *t, const iqd_track_slot *slots, const iqd_track_measure *meas, size_t n_blocks, iqd_track_summary *summary,
+                     iqd_track_summary *events, iqd_tracklog_counts *counts);
+int iqd_tracklog_get_state(iqd_tracklog_t *t, uint32_t source, iqd_track_summary *out /* [S] */, uint64_t *next_block /* g */);
+int iqd_tracklog_mean_centre(uint64_t sum_centre_q8, uint32_t n_active, uint32_t *centre_q8);
+
 /* PCM of several engines (one per GPU, one host process each or all in one) into one place over RCCL / xGMI.  The data
  * path itself has no collective - channels are independent, every GPU demodulates its own - this only
  * delivers the audio, 1/32 of the input volume, to one rank.  The reference has no counterpart (one dongle, one

@@ -92,6 +92,21 @@ HINT_NONE, HINT_CARRIER, HINT_NARROW, HINT_WIDE = 0, 1, 2, 3
 HINT_MODE = {HINT_NONE: "fm", HINT_CARRIER: "am", HINT_NARROW: "fm", HINT_WIDE: "wbfm"}   # what iqdemod_wide modes=auto sets
 
 
+class TrackLogConfig(C.Structure):
+    """iqd_tracklog_config (include/iqdemod.h: "Band track log")"""
+    _fields_ = [("n_sources", C.c_uint32), ("n_slots", C.c_uint32), ("max_events", C.c_uint32), ("min_active", C.c_uint32),
+                ("vote_min", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+# iqd_track_summary and iqd_tracklog_counts (include/iqdemod.h: "Band track log"), 64 and 16 bytes
+TRACK_SUMMARY = np.dtype([("track_id", "<u4"), ("state", "u1"), ("flags", "u1"), ("mode_hint", "u1"), ("width_class", "u1"),
+                          ("first_block", "<u8"), ("n_blocks", "<u4"), ("n_active", "<u4"), ("n_measured", "<u4"),
+                          ("votes", "<u4", (3,)), ("sum_centre_q8", "<u8"), ("sum_excess", "<u8"), ("peak_excess", "<u4"),
+                          ("obw_lo_min", "<u2"), ("obw_hi_max", "<u2")])
+TRACKLOG_COUNTS = np.dtype([("n_events", "<u4"), ("n_stored", "<u4"), ("n_short", "<u4"), ("n_lost", "<u4")])
+TLOG_F_NEW, TLOG_F_MODE_CHANGED, TLOG_F_CLOSED, TLOG_F_LOST = 1, 2, 4, 8
+
+
 class TrackFollow(C.Structure):
     """iqd_track_follow (include/iqdemod.h: "Track-following channels")"""
     _fields_ = [("slots_dev", C.c_void_p), ("n_slots", C.c_uint32), ("n_blocks", C.c_uint32), ("block_bytes", C.c_uint32),
@@ -131,6 +146,8 @@ EXPORTS = [
     "iqd_track_create", "iqd_track_destroy", "iqd_track_reset", "iqd_track_run_device", "iqd_track_run", "iqd_track_get_state",
     "iqd_track_phase_inc",
     "iqd_measure_create", "iqd_measure_destroy", "iqd_measure_run_device", "iqd_measure_run",
+    "iqd_tracklog_create", "iqd_tracklog_destroy", "iqd_tracklog_reset", "iqd_tracklog_run_device", "iqd_tracklog_run",
+    "iqd_tracklog_get_state", "iqd_tracklog_mean_centre",
     "iqd_channelizer_set_track_table", "iqd_channelizer_follow_tracks", "iqd_channelizer_track_window_outputs",
 ]
 
@@ -266,6 +283,14 @@ def _lib():
     L.iqd_measure_destroy.restype = None
     L.iqd_measure_run_device.argtypes = [vp, vp, vp, vp, sz, vp]
     L.iqd_measure_run.argtypes = [vp, vp, vp, vp, sz, vp]
+    L.iqd_tracklog_create.argtypes = [vp, C.POINTER(TrackLogConfig), C.POINTER(vp)]
+    L.iqd_tracklog_destroy.argtypes = [vp]
+    L.iqd_tracklog_destroy.restype = None
+    L.iqd_tracklog_reset.argtypes = [vp]
+    L.iqd_tracklog_run_device.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    L.iqd_tracklog_run.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    L.iqd_tracklog_get_state.argtypes = [vp, u32, vp, C.POINTER(C.c_uint64)]
+    L.iqd_tracklog_mean_centre.argtypes = [C.c_uint64, u32, C.POINTER(u32)]
     L.iqd_channelizer_set_track_table.argtypes = [vp, C.POINTER(TrackFollow)]
     L.iqd_channelizer_follow_tracks.argtypes = [vp, u32, u32, vp]
     L.iqd_channelizer_track_window_outputs.argtypes = [u32, u32]
@@ -1196,6 +1221,91 @@ class Measure:
         """iqd_measure_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
         if self._h and self._e._h:
             self._L.iqd_measure_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+
+def tracklog_defaults():
+    """the settings used where none are given: a track is an event from two active blocks on, a mode is decided from four
+    votes on, and a call keeps up to 256 events per source"""
+    return dict(min_active=2, vote_min=4, max_events=256)
+
+
+def tracklog_mean_centre(sum_centre_q8, n_active):
+    """iqd_tracklog_mean_centre (host only, no GPU): floor(sum_centre_q8 / n_active), a track's mean centre in 1/256 bins -
+    what detect_offset_hz and track_phase_inc take."""
+    out = C.c_uint32()
+    a, n = int(sum_centre_q8), int(n_active)
+    if not (0 <= a < 2 ** 64 and 0 <= n < 2 ** 32) or _lib().iqd_tracklog_mean_centre(a, n, C.byref(out)) != 0:
+        raise IqdError(-1, "iqd_tracklog_mean_centre: sum_centre_q8 %r or n_active %r out of range" % (sum_centre_q8, n_active))
+    return out.value
+
+
+class TrackLog:
+    """iqd_tracklog_*: a running summary of every (source, slot) of a Tracker's table over its track's whole life - blocks
+    seen and active, the mean centre's sum, the measurements' extremes, a mode hint voted over every measured block - and one
+    event record per track that ends with at least min_active active blocks.  n_slots is the Tracker's.  State is carried from
+    call to call until reset()."""
+
+    def __init__(self, engine, n_sources=1, n_slots=8, max_events=None, min_active=None, vote_min=None, reserved=(0, 0, 0)):
+        self._e, self._L = engine, engine._L
+        self._h = None
+        self.n_sources, self.n_slots = int(n_sources), int(n_slots)
+        given = dict(max_events=max_events, min_active=min_active, vote_min=vote_min)
+        v = dict(tracklog_defaults(), **{k: x for k, x in given.items() if x is not None})
+        self.max_events = int(v["max_events"])
+        cfg = TrackLogConfig(*[int(x) & 0xffffffff for x in (n_sources, n_slots, v["max_events"], v["min_active"], v["vote_min"])])
+        for i in range(3):
+            cfg.reserved[i] = int(reserved[i]) & 0xffffffff
+        h = C.c_void_p()
+        engine._check(self._L.iqd_tracklog_create(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        if not hasattr(engine, "_children"):
+            engine._children = weakref.WeakSet()
+        engine._children.add(self)
+
+    def run(self, slots, meas):
+        """slots [n_sources, n_blocks, n_slots] TRACK_SLOT and meas [n_sources, n_blocks, n_slots] TRACK_MEASURE (host arrays:
+        Tracker.run's and Measure.run's) -> (summary [n_sources, n_blocks, n_slots] TRACK_SUMMARY, events [n_sources,
+        max_events] TRACK_SUMMARY, counts [n_sources] TRACKLOG_COUNTS)."""
+        if getattr(slots, "dtype", None) != TRACK_SLOT or getattr(meas, "dtype", None) != TRACK_MEASURE:
+            raise TypeError("slots are TRACK_SLOT and meas TRACK_MEASURE arrays")
+        slots = np.ascontiguousarray(slots).reshape(self.n_sources, -1, self.n_slots)
+        nb = slots.shape[1]
+        meas = np.ascontiguousarray(meas).reshape(self.n_sources, nb, self.n_slots)
+        summary = np.zeros((self.n_sources, nb, self.n_slots), TRACK_SUMMARY)
+        events = np.zeros((self.n_sources, self.max_events), TRACK_SUMMARY)
+        counts = np.zeros(self.n_sources, TRACKLOG_COUNTS)
+        one = np.zeros(64, np.uint8)                              # (a refused call gets valid pointers all the same)
+        self._e._check(self._L.iqd_tracklog_run(self._h, _np_ptr(slots if nb else one), _np_ptr(meas if nb else one), nb,
+                                                _np_ptr(summary if nb else one), _np_ptr(events), _np_ptr(counts)))
+        return summary, events, counts
+
+    def run_device(self, slots_dev, meas_dev, n_blocks, summary_dev, events_dev, counts_dev):
+        """iqd_tracklog_run_device: device pointers (integers), queued on the engine's stream."""
+        self._e._check(self._L.iqd_tracklog_run_device(self._h, C.c_void_p(slots_dev or None), C.c_void_p(meas_dev or None), int(n_blocks),
+                                                       C.c_void_p(summary_dev or None), C.c_void_p(events_dev or None),
+                                                       C.c_void_p(counts_dev or None)))
+
+    def reset(self):
+        """iqd_tracklog_reset: every summary free, block indices count from 0 again."""
+        self._e._check(self._L.iqd_tracklog_reset(self._h))
+
+    def state(self, source=0):
+        """iqd_tracklog_get_state: (the source's n_slots summaries as they stand after the last block, its block index);
+        synchronises."""
+        out = np.zeros(self.n_slots, TRACK_SUMMARY)
+        g = C.c_uint64()
+        if not 0 <= int(source) <= 0xffffffff:
+            raise IqdError(-1, "iqd_tracklog_get_state: source %r out of range" % (source,))
+        self._e._check(self._L.iqd_tracklog_get_state(self._h, int(source), _np_ptr(out), C.byref(g)))
+        return out, g.value
+
+    def close(self):
+        """iqd_tracklog_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
+        if self._h and self._e._h:
+            self._L.iqd_tracklog_destroy(self._h)
         self._h = None
 
     __del__ = close

@@ -4,7 +4,8 @@
 //   iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] out=power.u32 [log=spectrum.txt]
 //                    [detect=runs.txt [rank=512] [ratio_q8=2048] [guard=1] [bridge=8] [minwidth=3] [maxdet=16]
 //                     [track=tracks.txt [slots=8] [gate_q8=512] [open=3] [hold=2] [alpha_q8=64] [bias=0] [edges=a,b,c]
-//                      [measure=meas.txt [margin=] [beta_q16=328] [carrier=1] [minsum=4096] [carrier_q8=160] [wide=]]]]
+//                      [measure=meas.txt [margin=] [beta_q16=328] [carrier=1] [minsum=4096] [carrier_q8=160] [wide=]
+//                       [events=events.txt [minactive=2] [votemin=4] [maxevents=256]]]]]
 //
 //   in       interleaved I/Q, one byte per rail
 //   rate     the capture's sample rate in Hz (for the log's offsets only)
@@ -32,6 +33,16 @@
 //            carrier_q8, sum_excess, flags, hint (0 none, 1 carrier, 2 narrow, 3 wide).
 //   margin beta_q16 carrier minsum carrier_q8 wide   iqd_measure_config's margin (left out: bins / 256, at least 1),
 //            obw_tail_q16, carrier_half, min_sum, carrier_min_q8, wide_bins (left out: bins / 32); dc_guard is guard=
+//   events   needs track= and measure=.  The track log (include/iqdemod.h: "Band track log") runs on the device behind the
+//            measurements, on the same stream, with its state carried from one read of the file to the next.  One line per
+//            event - a track that ended with at least minactive active blocks: id, slot, first block, number of blocks, start
+//            time and duration in seconds (blocks of bins x frames samples at rate, %.6f), the mean centre's offset in Hz
+//            (iqd_tracklog_mean_centre, iqd_detect_offset_hz; 0 without an active block), the offsets in Hz of obw_lo_min and
+//            obw_hi_max (the bin's middle; 0 0 without a voting block), the voted hint (0 none, 1 carrier, 2 narrow, 3 wide),
+//            its three vote counts, n_measured, the mean excess power floor(sum_excess / n_measured) (0 without a voting
+//            block), flags.  At the end of the input every track still live is read through iqd_tracklog_get_state and written
+//            in the same form with the word `open` appended.  Events past maxevents in one call are counted on stderr.
+//   minactive votemin maxevents   iqd_tracklog_config's min_active, vote_min, max_events
 // A capture that ends inside a block ends with its last whole block; the rest is dropped and counted on stderr.
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
 #include <math.h>
@@ -69,7 +80,12 @@ bool readWindow(const std::string &path, std::vector<int16_t> &v)
 
 int main(int argc, char **argv)
 {
-  std::string in, out, log, windowPath, detectPath, trackPath, measurePath, format = "u8";
+  std::string in, out, log, windowPath, detectPath, trackPath, measurePath, eventsPath, format = "u8";
+  iqd_tracklog_config lc{};
+  lc.n_sources = 1;
+  lc.max_events = 256;
+  lc.min_active = 2;
+  lc.vote_min = 4;
   iqd_measure_config mc{};
   mc.n_sources = 1;
   mc.obw_tail_q16 = 328;
@@ -125,6 +141,10 @@ int main(int argc, char **argv)
     else if (!strncmp(a, "minsum=", 7)) mc.min_sum = (uint32_t)strtoul(a + 7, nullptr, 10);
     else if (!strncmp(a, "carrier_q8=", 11)) mc.carrier_min_q8 = (uint32_t)strtoul(a + 11, nullptr, 10);
     else if (!strncmp(a, "wide=", 5)) { mc.wide_bins = (uint32_t)strtoul(a + 5, nullptr, 10); wideGiven = true; }
+    else if (!strncmp(a, "events=", 7)) eventsPath = a + 7;
+    else if (!strncmp(a, "minactive=", 10)) lc.min_active = (uint32_t)strtoul(a + 10, nullptr, 10);
+    else if (!strncmp(a, "votemin=", 8)) lc.vote_min = (uint32_t)strtoul(a + 8, nullptr, 10);
+    else if (!strncmp(a, "maxevents=", 10)) lc.max_events = (uint32_t)strtoul(a + 10, nullptr, 10);
     else if (!strncmp(a, "edges=", 6)) {
       edgesGiven = sscanf(a + 6, "%u,%u,%u", &tc.class_edge[0], &tc.class_edge[1], &tc.class_edge[2]) == 3;
       if (!edgesGiven) {
@@ -142,10 +162,15 @@ int main(int argc, char **argv)
     fprintf(stderr, "usage: iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] "
                     "out=power.u32 [log=spectrum.txt] [detect=runs.txt [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=] "
                     "[track=tracks.txt [slots=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c] "
-                    "[measure=meas.txt [margin=] [beta_q16=] [carrier=] [minsum=] [carrier_q8=] [wide=]]]]\n");
+                    "[measure=meas.txt [margin=] [beta_q16=] [carrier=] [minsum=] [carrier_q8=] [wide=] "
+                    "[events=events.txt [minactive=] [votemin=] [maxevents=]]]]]\n");
     return 1;
   }
-  const bool detect = !detectPath.empty(), track = !trackPath.empty(), measure = !measurePath.empty();
+  const bool detect = !detectPath.empty(), track = !trackPath.empty(), measure = !measurePath.empty(), events = !eventsPath.empty();
+  if (events && !(track && measure)) {
+    fprintf(stderr, "iqdemod_spectrum: events= needs track= and measure=\n");
+    return 1;
+  }
   if (measure && !track) {
     fprintf(stderr, "iqdemod_spectrum: measure= needs track=\n");
     return 1;
@@ -169,7 +194,8 @@ int main(int argc, char **argv)
   FILE *fdet = fout && detect ? fopen(detectPath.c_str(), "w") : nullptr;
   FILE *ftrk = fout && track ? fopen(trackPath.c_str(), "w") : nullptr;
   FILE *fmsr = fout && measure ? fopen(measurePath.c_str(), "w") : nullptr;
-  if (!fin || !fout || (!log.empty() && !flog) || (detect && !fdet) || (track && !ftrk) || (measure && !fmsr)) {
+  FILE *fevt = fout && events ? fopen(eventsPath.c_str(), "w") : nullptr;
+  if (!fin || !fout || (!log.empty() && !flog) || (detect && !fdet) || (track && !ftrk) || (measure && !fmsr) || (events && !fevt)) {
     fprintf(stderr, "iqdemod_spectrum: cannot open the files\n");
     return 1;
   }
@@ -249,6 +275,36 @@ int main(int argc, char **argv)
     }
   }
 
+  iqd_tracklog_t *tl = nullptr;
+  if (events) {
+    lc.n_slots = tc.n_slots;
+    rc = iqd_tracklog_create(e, &lc, &tl);
+    if (rc != IQD_OK) {
+      fprintf(stderr, "iqdemod_spectrum: iqd_tracklog_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      iqd_measure_destroy(ms);
+      iqd_track_destroy(t);
+      iqd_detect_destroy(d);
+      iqd_spectrum_destroy(s);
+      iqd_destroy(e);
+      return 1;
+    }
+  }
+  // one line of events=: an event, or a track still live at the end of the input
+  auto writeEvent = [&](uint32_t slot, const iqd_track_summary &r, bool open) {
+    const double blockSeconds = (double)bins * frames / rate;
+    int64_t cen = 0, lo = 0, hi = 0;
+    uint32_t mean = 0;
+    if (iqd_tracklog_mean_centre(r.sum_centre_q8, r.n_active, &mean) == IQD_OK) iqd_detect_offset_hz(bins, (uint32_t)rate, mean, &cen);
+    if (r.n_measured) {
+      iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.obw_lo_min + 128u, &lo);
+      iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.obw_hi_max + 128u, &hi);
+    }
+    fprintf(fevt, "%u %u %llu %u %.6f %.6f %lld %lld %lld %u %u %u %u %u %llu %u%s\n", r.track_id, slot, (unsigned long long)r.first_block,
+            r.n_blocks, (double)r.first_block * blockSeconds, (double)r.n_blocks * blockSeconds, (long long)cen, (long long)lo, (long long)hi,
+            r.mode_hint, r.votes[0], r.votes[1], r.votes[2], r.n_measured,
+            (unsigned long long)(r.n_measured ? r.sum_excess / r.n_measured : 0), r.flags, open ? " open" : "");
+  };
+
   // whole blocks, up to about 16 MiB of capture per call
   const size_t blockBytes = (size_t)2 * bins * frames;
   const size_t perCall = blockBytes >= (16u << 20) ? 1 : (16u << 20) / blockBytes;
@@ -263,9 +319,13 @@ int main(int argc, char **argv)
   std::vector<iqd_track_slot> slots(track ? perCall * tc.n_slots : 0);
   std::vector<iqd_track_block> tblocks(track ? perCall : 0);
   std::vector<iqd_track_measure> meas(measure ? perCall * tc.n_slots : 0);
-  uint64_t unplaced = 0;
+  std::vector<iqd_track_summary> evts(events ? lc.max_events : 0);
+  // an event record does not say which slot its track sat in: the tool keeps the id every slot of the table showed last
+  // (0: none, or closed) and names the slot when the table shows that id ending
+  std::vector<uint32_t> slotId(track ? tc.n_slots : 0, 0);
+  uint64_t unplaced = 0, eventsPast = 0;
   void *wideDev = nullptr, *powerDev = nullptr, *rowsDev = nullptr, *detDev = nullptr, *slotsDev = nullptr, *tblocksDev = nullptr;
-  void *measDev = nullptr;
+  void *measDev = nullptr, *summaryDev = nullptr, *eventsDev = nullptr, *countsDev = nullptr;
   if (detect) {
     rc = iqd_dev_alloc(e, buf.size(), &wideDev);
     if (rc == IQD_OK) rc = iqd_dev_alloc(e, power.size() * sizeof(uint32_t), &powerDev);
@@ -274,8 +334,12 @@ int main(int argc, char **argv)
     if (rc == IQD_OK && track) rc = iqd_dev_alloc(e, slots.size() * sizeof(iqd_track_slot), &slotsDev);
     if (rc == IQD_OK && track) rc = iqd_dev_alloc(e, tblocks.size() * sizeof(iqd_track_block), &tblocksDev);
     if (rc == IQD_OK && measure) rc = iqd_dev_alloc(e, meas.size() * sizeof(iqd_track_measure), &measDev);
+    if (rc == IQD_OK && events) rc = iqd_dev_alloc(e, meas.size() * sizeof(iqd_track_summary), &summaryDev);
+    if (rc == IQD_OK && events) rc = iqd_dev_alloc(e, evts.size() * sizeof(iqd_track_summary), &eventsDev);
+    if (rc == IQD_OK && events) rc = iqd_dev_alloc(e, sizeof(iqd_tracklog_counts), &countsDev);
     if (rc != IQD_OK) {
       fprintf(stderr, "iqdemod_spectrum: iqd_dev_alloc: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      iqd_tracklog_destroy(tl);
       iqd_measure_destroy(ms);
       iqd_track_destroy(t);
       iqd_detect_destroy(d);
@@ -287,6 +351,7 @@ int main(int argc, char **argv)
   for (;;) {
     const size_t got = fread(buf.data(), 1, buf.size(), fin);
     const size_t nb = got / blockBytes;
+    iqd_tracklog_counts evtCounts{};
     dropped = got - nb * blockBytes;
     if (nb) {
       if (!detect) {
@@ -302,15 +367,21 @@ int main(int argc, char **argv)
         if (rc == IQD_OK && measure)
           rc = iqd_measure_run_device(ms, (const uint32_t *)powerDev, (const iqd_detect_row *)rowsDev, (const iqd_track_slot *)slotsDev, nb,
                                       (iqd_track_measure *)measDev);
+        if (rc == IQD_OK && events)
+          rc = iqd_tracklog_run_device(tl, (const iqd_track_slot *)slotsDev, (const iqd_track_measure *)measDev, nb,
+                                       (iqd_track_summary *)summaryDev, (iqd_track_summary *)eventsDev, (iqd_tracklog_counts *)countsDev);
         if (rc == IQD_OK) rc = iqd_dev_download(e, power.data(), powerDev, nb * bins * sizeof(uint32_t));
         if (rc == IQD_OK) rc = iqd_dev_download(e, rows.data(), rowsDev, nb * sizeof(iqd_detect_row));
         if (rc == IQD_OK) rc = iqd_dev_download(e, dets.data(), detDev, nb * dc.max_detections * sizeof(iqd_detection));
         if (rc == IQD_OK && track) rc = iqd_dev_download(e, slots.data(), slotsDev, nb * tc.n_slots * sizeof(iqd_track_slot));
         if (rc == IQD_OK && track) rc = iqd_dev_download(e, tblocks.data(), tblocksDev, nb * sizeof(iqd_track_block));
         if (rc == IQD_OK && measure) rc = iqd_dev_download(e, meas.data(), measDev, nb * tc.n_slots * sizeof(iqd_track_measure));
+        if (rc == IQD_OK && events) rc = iqd_dev_download(e, &evtCounts, countsDev, sizeof(evtCounts));
+        if (rc == IQD_OK && events && evtCounts.n_stored)
+          rc = iqd_dev_download(e, evts.data(), eventsDev, (size_t)evtCounts.n_stored * sizeof(iqd_track_summary));
       }
       if (rc != IQD_OK) {
-        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", measure ? "spectrum, detector, tracker and measurements" : track ? "spectrum, detector and tracker" : detect ? "spectrum and detector" : "iqd_spectrum_run", iqd_strerror(rc), iqd_last_error(e));
+        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", events ? "spectrum, detector, tracker, measurements and track log" : measure ? "spectrum, detector, tracker and measurements" : track ? "spectrum, detector and tracker" : detect ? "spectrum and detector" : "iqd_spectrum_run", iqd_strerror(rc), iqd_last_error(e));
         status = 3;
         break;
       }
@@ -361,15 +432,42 @@ int main(int argc, char **argv)
           fprintf(fmsr, "%llu %u %u %lld %lld %lld %lld %u %llu %u %u\n", (unsigned long long)(block + b), k, r.track_id, (long long)lo,
                   (long long)hi, (long long)peak, (long long)cen, r.carrier_q8, (unsigned long long)r.sum_excess, r.flags, r.hint);
         }
+      if (events) {
+        // events come in block order and within a block in slot order, and so do the table's endings: walk both together
+        // (an ending with fewer than minactive active blocks is no event and is passed over; the tracker's ids are unique)
+        uint32_t next = 0;
+        for (size_t b = 0; b < nb; b++)
+          for (uint32_t k = 0; k < tc.n_slots; k++) {
+            const iqd_track_slot &r = slots[b * tc.n_slots + k];
+            const bool ends = slotId[k] != 0 && (r.track_id != slotId[k] || r.state == 0);
+            if (ends && next < evtCounts.n_stored && evts[next].track_id == slotId[k]) writeEvent(k, evts[next++], false);
+            slotId[k] = r.state == 0 ? 0 : r.track_id;
+          }
+        eventsPast += evtCounts.n_events - evtCounts.n_stored;
+      }
       block += nb;
     }
     if (got < buf.size()) break;
   }
+  if (events && status == 0) {
+    // the tracks still live when the input ended
+    std::vector<iqd_track_summary> live(tc.n_slots);
+    uint64_t g = 0;
+    rc = iqd_tracklog_get_state(tl, 0, live.data(), &g);
+    if (rc != IQD_OK) {
+      fprintf(stderr, "iqdemod_spectrum: iqd_tracklog_get_state: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
+      status = 3;
+    }
+    for (uint32_t k = 0; rc == IQD_OK && k < tc.n_slots; k++)
+      if (live[k].track_id != 0) writeEvent(k, live[k], true);
+  }
   if (dropped) fprintf(stderr, "iqdemod_spectrum: %zu bytes after the last whole block dropped\n", dropped);
   if (pastMax) fprintf(stderr, "iqdemod_spectrum: %llu runs past maxdet not written\n", (unsigned long long)pastMax);
+  if (eventsPast) fprintf(stderr, "iqdemod_spectrum: %llu events past maxevents in their call not written\n", (unsigned long long)eventsPast);
   if (unplaced) fprintf(stderr, "iqdemod_spectrum: %llu detections found no free slot\n", (unsigned long long)unplaced);
-  for (void *p : {wideDev, powerDev, rowsDev, detDev, slotsDev, tblocksDev, measDev})
+  for (void *p : {wideDev, powerDev, rowsDev, detDev, slotsDev, tblocksDev, measDev, summaryDev, eventsDev, countsDev})
     if (p) iqd_dev_free(e, p);
+  iqd_tracklog_destroy(tl);
   iqd_measure_destroy(ms);
   iqd_track_destroy(t);
   iqd_detect_destroy(d);
@@ -381,5 +479,6 @@ int main(int argc, char **argv)
   if (fdet && fclose(fdet) != 0) status = status ? status : 1;
   if (ftrk && fclose(ftrk) != 0) status = status ? status : 1;
   if (fmsr && fclose(fmsr) != 0) status = status ? status : 1;
+  if (fevt && fclose(fevt) != 0) status = status ? status : 1;
   return status;
 }
