@@ -303,6 +303,39 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _dev_ptr(x):
+    """a device pointer argument: an integer address; 0 or None is NULL"""
+    return C.c_void_p(x or None)
+
+
+def _ptr_or_placeholder(a):
+    """_np_ptr(a), but an empty array - its call will be refused - gets a valid pointer all the same"""
+    return _np_ptr(a if a.size else np.zeros(64, np.uint8))
+
+
+class _EngineChild:
+    """An object that queues on its engine's stream: made by iqd_<kind>_create, registered so that Engine.close() closes it
+    first, gone by iqd_<kind>_destroy.  _h is what the raw library takes."""
+    _e = _L = _h = _kind = None
+
+    def _create(self, engine, kind, cfg):
+        self._e, self._L, self._kind = engine, engine._L, kind
+        h = C.c_void_p()
+        engine._check(getattr(self._L, "iqd_%s_create" % kind)(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        if not hasattr(engine, "_children"):
+            engine._children = weakref.WeakSet()
+        engine._children.add(self)
+
+    def close(self):
+        """iqd_<kind>_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
+        if self._h and self._e._h:
+            getattr(self._L, "iqd_%s_destroy" % self._kind)(self._h)
+        self._h = None
+
+    __del__ = close
+
+
 class Engine:
     """N independent channels, each one reference IqDataProcessor + its four demodulators."""
 
@@ -487,8 +520,8 @@ class Engine:
         """iqd_accept_wideband_device: device pointers (integers), queued on the engine's stream; rows_dev receives the
         cut rows [n_channels, bytes_per_source / M] (fractional: bytes_per_source Q / P)."""
         self._check(self._L.iqd_accept_wideband_device(self._h, chz._h, int(first), C.c_void_p(wide_dev), int(bytes_per_source),
-                                                       C.c_void_p(rows_dev), C.c_void_p(pcm_dev), C.c_void_p(count_dev or None),
-                                                       C.c_void_p(mag_dev or None), C.c_void_p(allowed_dev or None)))
+                                                       C.c_void_p(rows_dev), C.c_void_p(pcm_dev), _dev_ptr(count_dev),
+                                                       _dev_ptr(mag_dev), _dev_ptr(allowed_dev)))
 
     def front_end(self, iq_u8, first=0, n=None):
         """u8 -> s8 -> rotation only: the bytes the reference leaves in its buffer / dumps over UDP."""
@@ -507,8 +540,8 @@ class Engine:
     def accept_device(self, iq_dev, bytes_per_ch, pcm_dev, count_dev=0, mag_dev=0, allowed_dev=0, first=0, n=None):
         f, n = self._range(first, n)
         self._check(self._L.iqd_accept_iq_device(self._h, f, n, C.c_void_p(iq_dev), bytes_per_ch,
-                                                 C.c_void_p(pcm_dev), C.c_void_p(count_dev or None),
-                                                 C.c_void_p(mag_dev or None), C.c_void_p(allowed_dev or None)))
+                                                 C.c_void_p(pcm_dev), _dev_ptr(count_dev),
+                                                 _dev_ptr(mag_dev), _dev_ptr(allowed_dev)))
 
     def synchronize(self):
         self._check(self._L.iqd_synchronize(self._h))
@@ -620,7 +653,7 @@ class Gatherer:
 
     def gather(self, send_dev, bytes_per_rank, recv_dev, row_stride):
         arr = (C.c_size_t * self.world)(*[int(b) for b in bytes_per_rank])
-        rc = self._L.iqd_gather_pcm(self._h, C.c_void_p(send_dev), arr, C.c_void_p(recv_dev or None), int(row_stride))
+        rc = self._L.iqd_gather_pcm(self._h, C.c_void_p(send_dev), arr, _dev_ptr(recv_dev), int(row_stride))
         if rc != 0:
             raise IqdError(rc, "iqd_gather_pcm failed")
 
@@ -700,7 +733,7 @@ class Filter:
 
     def run_device(self, in_dev, n_in, out_dev):
         """iqd_filter_run_device: device pointers (integers), queued on the engine's stream."""
-        self._e._check(self._L.iqd_filter_run_device(self._h, C.c_void_p(in_dev or None), int(n_in), C.c_void_p(out_dev or None)))
+        self._e._check(self._L.iqd_filter_run_device(self._h, _dev_ptr(in_dev), int(n_in), _dev_ptr(out_dev)))
 
     def reset(self):
         self._e._check(self._L.iqd_filter_reset(self._h))
@@ -792,15 +825,13 @@ def channelizer_track_window_outputs(decimation, n_taps):
     return int(_lib().iqd_channelizer_track_window_outputs(int(decimation), int(n_taps)))
 
 
-class Channelizer:
+class Channelizer(_EngineChild):
     """iqd_channelizer_*: n_channels channels cut out of n_sources wideband captures at decimation / decimation_den x
     256 kS/s (decimation_den 1, 2, 4 or 8; 2.4 MS/s is 75 / 8).  sample_format: what the captures hold - "u8" (offset
     binary, the RTL-SDR's), "s8" (int8) or "s16" (little-endian int16); run and accept_wideband then take
     [n_sources, 2 samples] arrays of that dtype."""
 
     def __init__(self, engine, decimation, n_channels, n_sources=1, taps=None, decimation_den=1, sample_format="u8"):
-        self._e, self._L = engine, engine._L
-        self._h = None
         if sample_format not in SAMPLE_FORMAT:
             raise ValueError("sample_format must be one of %s" % ", ".join(SAMPLE_FORMAT))
         self.sample_format = sample_format
@@ -813,12 +844,7 @@ class Channelizer:
         cfg = ChannelizerConfig(self.n_sources, self.n_channels, self.decimation,
                                 0 if self._taps is None else len(self._taps),
                                 None if self._taps is None else self._taps.ctypes.data, int(decimation_den), self._code)
-        h = C.c_void_p()
-        engine._check(self._L.iqd_channelizer_create(engine._h, C.byref(cfg), C.byref(h)))
-        self._h = h
-        if not hasattr(engine, "_children"):
-            engine._children = weakref.WeakSet()
-        engine._children.add(self)
+        self._create(engine, "channelizer", cfg)
 
     def set_channels(self, first=0, source=None, offset_hz=None, fs=None, phase_inc=None, gain_shift=None, n=None):
         """Retunes channels [first, first + n): offsets in Hz with the capture's rate fs, or raw increments; a field left
@@ -874,8 +900,7 @@ class Channelizer:
         block_bytes = int(block_bytes)
         row = wide.shape[1] // self.decimation * self.decimation_den
         out = np.zeros((self.n_sources, row // block_bytes if block_bytes > 0 else 0, self.n_points), np.uint32)
-        guard = out if out.size else np.zeros(4, np.uint32)      # (a refused call gets a valid pointer all the same)
-        self._e._check(self._L.iqd_channelizer_survey(self._h, _np_ptr(wide), wide.shape[1], block_bytes & 0xffffffff, _np_ptr(guard)))
+        self._e._check(self._L.iqd_channelizer_survey(self._h, _np_ptr(wide), wide.shape[1], block_bytes & 0xffffffff, _ptr_or_placeholder(out)))
         return out
 
     def survey_device(self, wide_dev, bytes_per_source, block_bytes, magnitude_dev):
@@ -925,14 +950,6 @@ class Channelizer:
                         (C.c_uint32 * 3)(*[int(r) for r in reserved]))
         self._e._check(self._L.iqd_channelizer_set_track_table(self._h, C.byref(t)))
 
-    def close(self):
-        """iqd_channelizer_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
-        if self._h and self._e._h:
-            self._L.iqd_channelizer_destroy(self._h)
-        self._h = None
-
-    __del__ = close
-
 
 def spectrum_default_window(n_bins):
     """iqd_spectrum_default_window (host only, no GPU): the integer Hann window of n_bins entries, int16."""
@@ -960,14 +977,12 @@ def spectrum_dbfs(power, p_fs):
     return 10.0 * np.log10(np.maximum(np.asarray(power, np.float64), 1.0) / float(p_fs))
 
 
-class Spectrum:
+class Spectrum(_EngineChild):
     """iqd_spectrum_*: the integer periodogram of n_sources wideband captures, n_bins bins (64 .. 2048, a power of two) from
     low to high frequency, the centre frequency at bin n_bins / 2.  window: n_bins int16 values (None: the default Hann
     window); sample_format "u8" or "s8"."""
 
     def __init__(self, engine, n_bins, n_sources=1, window=None, sample_format="u8"):
-        self._e, self._L = engine, engine._L
-        self._h = None
         if sample_format not in SAMPLE_FORMAT:
             raise ValueError("sample_format must be one of %s" % ", ".join(SAMPLE_FORMAT))
         self.sample_format = sample_format
@@ -978,12 +993,7 @@ class Spectrum:
             raise ValueError("the window must have n_bins (%d) entries" % self.n_bins)
         cfg = SpectrumConfig(self.n_sources & 0xffffffff, self.n_bins & 0xffffffff,
                              None if self._window is None else self._window.ctypes.data, self._code)
-        h = C.c_void_p()
-        engine._check(self._L.iqd_spectrum_create(engine._h, C.byref(cfg), C.byref(h)))
-        self._h = h
-        if not hasattr(engine, "_children"):
-            engine._children = weakref.WeakSet()
-        engine._children.add(self)
+        self._create(engine, "spectrum", cfg)
 
     def _capture(self, wide):
         """One call's capture as [n_sources, bytes_per_source] bytes; an array of the other format's dtype is a TypeError
@@ -1001,23 +1011,13 @@ class Spectrum:
         F = int(frames_per_block)
         nb = wide.shape[1] // (2 * self.n_bins * F) if F > 0 else 0
         out = np.zeros((self.n_sources, nb, self.n_bins), np.uint32)
-        guard = out if out.size else np.zeros(4, np.uint32)      # (a refused call gets a valid pointer all the same)
-        src = wide if wide.size else np.zeros(16, np.uint8)
-        self._e._check(self._L.iqd_spectrum_run(self._h, _np_ptr(src), wide.shape[1], F & 0xffffffff, _np_ptr(guard)))
+        self._e._check(self._L.iqd_spectrum_run(self._h, _ptr_or_placeholder(wide), wide.shape[1], F & 0xffffffff, _ptr_or_placeholder(out)))
         return out
 
     def run_device(self, wide_dev, bytes_per_source, frames_per_block, power_dev):
         """iqd_spectrum_run_device: device pointers (integers), queued on the engine's stream."""
-        self._e._check(self._L.iqd_spectrum_run_device(self._h, C.c_void_p(wide_dev or None), int(bytes_per_source),
-                                                       int(frames_per_block) & 0xffffffff, C.c_void_p(power_dev or None)))
-
-    def close(self):
-        """iqd_spectrum_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
-        if self._h and self._e._h:
-            self._L.iqd_spectrum_destroy(self._h)
-        self._h = None
-
-    __del__ = close
+        self._e._check(self._L.iqd_spectrum_run_device(self._h, _dev_ptr(wide_dev), int(bytes_per_source),
+                                                       int(frames_per_block) & 0xffffffff, _dev_ptr(power_dev)))
 
 
 def detect_offset_hz(n_bins, rate_hz, centroid_q8):
@@ -1030,24 +1030,17 @@ def detect_offset_hz(n_bins, rate_hz, centroid_q8):
     return hz.value
 
 
-class Detector:
+class Detector(_EngineChild):
     """iqd_detect_*: the occupied runs of band spectrum rows of n_bins bins (64 .. 2048, a power of two).  floor_rank: which
     of the row's sorted values is the noise floor (None: n_bins / 2, the upper median); ratio_q8: the threshold over it
     (256 = 1.0); dc_guard: bins N / 2 - d < k < N / 2 + d never count; bridge: the gap two hot bins of one run may have;
     min_width: narrower runs are dropped; max_detections: records per row."""
 
     def __init__(self, engine, n_bins, floor_rank=None, ratio_q8=2048, dc_guard=1, bridge=8, min_width=3, max_detections=16):
-        self._e, self._L = engine, engine._L
-        self._h = None
         self.n_bins, self.max_detections = int(n_bins), int(max_detections)
         rank = self.n_bins // 2 if floor_rank is None else int(floor_rank)
         cfg = DetectConfig(*[int(v) & 0xffffffff for v in (n_bins, rank, ratio_q8, dc_guard, bridge, min_width, max_detections)])
-        h = C.c_void_p()
-        engine._check(self._L.iqd_detect_create(engine._h, C.byref(cfg), C.byref(h)))
-        self._h = h
-        if not hasattr(engine, "_children"):
-            engine._children = weakref.WeakSet()
-        engine._children.add(self)
+        self._create(engine, "detect", cfg)
 
     def run(self, power):
         """[..., n_bins] uint32 (host array; a Spectrum.run result as it is) -> (rows [n_rows] DETECT_ROW,
@@ -1057,27 +1050,16 @@ class Detector:
         power = np.ascontiguousarray(power).reshape(-1, self.n_bins)
         rows = np.zeros(len(power), DETECT_ROW)
         det = np.zeros((len(power), self.max_detections), DETECTION)
-        src = power if power.size else np.zeros(4, np.uint32)     # (a refused call gets valid pointers all the same)
-        self._e._check(self._L.iqd_detect_run(self._h, _np_ptr(src), len(power), _np_ptr(rows if len(power) else np.zeros(1, DETECT_ROW)),
-                                              _np_ptr(det if len(power) else np.zeros(1, DETECTION))))
+        self._e._check(self._L.iqd_detect_run(self._h, _ptr_or_placeholder(power), len(power), _ptr_or_placeholder(rows), _ptr_or_placeholder(det)))
         return rows, det
 
     def run_device(self, power_dev, n_rows, rows_dev, det_dev):
         """iqd_detect_run_device: device pointers (integers), queued on the engine's stream."""
-        self._e._check(self._L.iqd_detect_run_device(self._h, C.c_void_p(power_dev or None), int(n_rows),
-                                                     C.c_void_p(rows_dev or None), C.c_void_p(det_dev or None)))
+        self._e._check(self._L.iqd_detect_run_device(self._h, _dev_ptr(power_dev), int(n_rows), _dev_ptr(rows_dev), _dev_ptr(det_dev)))
 
     def offset_hz(self, rate_hz, centroid_q8):
         """detect_offset_hz for this detector's n_bins"""
         return detect_offset_hz(self.n_bins, rate_hz, centroid_q8)
-
-    def close(self):
-        """iqd_detect_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
-        if self._h and self._e._h:
-            self._L.iqd_detect_destroy(self._h)
-        self._h = None
-
-    __del__ = close
 
 
 def track_phase_inc(n_bins, centroid_q8, inc_bias=0):
@@ -1096,7 +1078,7 @@ def track_default_edges(n_bins):
     return (max(n // 64, 1) + 1, max(n // 16, 2), max(n // 4, 2))
 
 
-class Tracker:
+class Tracker(_EngineChild):
     """iqd_track_*: the detector's runs followed from block to block - n_slots fixed slots per source, each a track with a
     persistent id, hysteresis (open after open_hits hits, held over hold_blocks misses), a centre smoothed by alpha_q8 / 256,
     its exact phase_inc (plus inc_bias) and a width class (class_edge: three widths in bins).  n_bins and max_detections
@@ -1104,8 +1086,6 @@ class Tracker:
 
     def __init__(self, engine, n_bins, n_sources=1, max_detections=16, n_slots=8, gate_q8=512, open_hits=3, hold_blocks=2,
                  alpha_q8=64, inc_bias=0, class_edge=None):
-        self._e, self._L = engine, engine._L
-        self._h = None
         self.n_bins, self.n_sources, self.max_detections, self.n_slots = int(n_bins), int(n_sources), int(max_detections), int(n_slots)
         edges = track_default_edges(n_bins) if class_edge is None else tuple(int(v) for v in class_edge)
         if len(edges) != 3:
@@ -1114,12 +1094,7 @@ class Tracker:
                                                           alpha_q8, inc_bias)])
         for i in range(3):
             cfg.class_edge[i] = edges[i] & 0xffffffff
-        h = C.c_void_p()
-        engine._check(self._L.iqd_track_create(engine._h, C.byref(cfg), C.byref(h)))
-        self._h = h
-        if not hasattr(engine, "_children"):
-            engine._children = weakref.WeakSet()
-        engine._children.add(self)
+        self._create(engine, "track", cfg)
 
     def run(self, rows, det):
         """rows [n_sources, n_blocks] DETECT_ROW and det [n_sources, n_blocks, max_detections] DETECTION (host arrays; a
@@ -1132,15 +1107,14 @@ class Tracker:
         det = np.ascontiguousarray(det).reshape(self.n_sources, nb, self.max_detections)
         slots = np.zeros((self.n_sources, nb, self.n_slots), TRACK_SLOT)
         blocks = np.zeros((self.n_sources, nb), TRACK_BLOCK)
-        one = np.zeros(64, np.uint8)                              # (a refused call gets valid pointers all the same)
-        self._e._check(self._L.iqd_track_run(self._h, _np_ptr(rows if nb else one), _np_ptr(det if nb else one), nb,
-                                             _np_ptr(slots if nb else one), _np_ptr(blocks if nb else one)))
+        self._e._check(self._L.iqd_track_run(self._h, _ptr_or_placeholder(rows), _ptr_or_placeholder(det), nb, _ptr_or_placeholder(slots),
+                                             _ptr_or_placeholder(blocks)))
         return slots, blocks
 
     def run_device(self, rows_dev, det_dev, n_blocks, slots_dev, blocks_dev):
         """iqd_track_run_device: device pointers (integers), queued on the engine's stream."""
-        self._e._check(self._L.iqd_track_run_device(self._h, C.c_void_p(rows_dev or None), C.c_void_p(det_dev or None), int(n_blocks),
-                                                    C.c_void_p(slots_dev or None), C.c_void_p(blocks_dev or None)))
+        self._e._check(self._L.iqd_track_run_device(self._h, _dev_ptr(rows_dev), _dev_ptr(det_dev), int(n_blocks),
+                                                    _dev_ptr(slots_dev), _dev_ptr(blocks_dev)))
 
     def reset(self):
         """iqd_track_reset: every slot free, ids count from 1 again."""
@@ -1154,14 +1128,6 @@ class Tracker:
         self._e._check(self._L.iqd_track_get_state(self._h, int(source), _np_ptr(out)))
         return out
 
-    def close(self):
-        """iqd_track_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
-        if self._h and self._e._h:
-            self._L.iqd_track_destroy(self._h)
-        self._h = None
-
-    __del__ = close
-
 
 def measure_defaults(n_bins):
     """the thresholds used where none are given (DESIGN 4.15 has the measurements they were chosen from): a margin of
@@ -1171,7 +1137,7 @@ def measure_defaults(n_bins):
     return dict(margin=max(n // 256, 1), obw_tail_q16=328, carrier_half=1, min_sum=4096, carrier_min_q8=160, wide_bins=max(n // 32, 2))
 
 
-class Measure:
+class Measure(_EngineChild):
     """iqd_measure_*: what every track of a Tracker's table is in a block - the excess power over the Detector's floor in the
     track's run widened by `margin` bins, the occupied bandwidth that leaves obw_tail_q16 / 65536 of it outside at each end,
     the share of it within carrier_half bins of the peak, and a mode hint (HINT_*) from wide_bins and carrier_min_q8.
@@ -1179,8 +1145,6 @@ class Measure:
 
     def __init__(self, engine, n_bins, n_sources=1, n_slots=8, dc_guard=1, margin=None, obw_tail_q16=None, carrier_half=None,
                  min_sum=None, carrier_min_q8=None, wide_bins=None, reserved=(0, 0)):
-        self._e, self._L = engine, engine._L
-        self._h = None
         self.n_bins, self.n_sources, self.n_slots = int(n_bins), int(n_sources), int(n_slots)
         given = dict(margin=margin, obw_tail_q16=obw_tail_q16, carrier_half=carrier_half, min_sum=min_sum,
                      carrier_min_q8=carrier_min_q8, wide_bins=wide_bins)
@@ -1189,12 +1153,7 @@ class Measure:
                                                             v["carrier_half"], v["min_sum"], v["carrier_min_q8"], v["wide_bins"])])
         for i in range(2):
             cfg.reserved[i] = int(reserved[i]) & 0xffffffff
-        h = C.c_void_p()
-        engine._check(self._L.iqd_measure_create(engine._h, C.byref(cfg), C.byref(h)))
-        self._h = h
-        if not hasattr(engine, "_children"):
-            engine._children = weakref.WeakSet()
-        engine._children.add(self)
+        self._create(engine, "measure", cfg)
 
     def run(self, power, rows, slots):
         """power [n_sources, n_blocks, n_bins] uint32, rows [n_sources, n_blocks] DETECT_ROW, slots [n_sources, n_blocks,
@@ -1207,23 +1166,14 @@ class Measure:
         power = np.ascontiguousarray(power).reshape(self.n_sources, nb, self.n_bins)
         slots = np.ascontiguousarray(slots).reshape(self.n_sources, nb, self.n_slots)
         meas = np.zeros((self.n_sources, nb, self.n_slots), TRACK_MEASURE)
-        one = np.zeros(64, np.uint8)                              # (a refused call gets valid pointers all the same)
-        self._e._check(self._L.iqd_measure_run(self._h, _np_ptr(power if nb else one), _np_ptr(rows if nb else one),
-                                               _np_ptr(slots if nb else one), nb, _np_ptr(meas if nb else one)))
+        self._e._check(self._L.iqd_measure_run(self._h, _ptr_or_placeholder(power), _ptr_or_placeholder(rows), _ptr_or_placeholder(slots), nb,
+                                               _ptr_or_placeholder(meas)))
         return meas
 
     def run_device(self, power_dev, rows_dev, slots_dev, n_blocks, meas_dev):
         """iqd_measure_run_device: device pointers (integers), queued on the engine's stream."""
-        self._e._check(self._L.iqd_measure_run_device(self._h, C.c_void_p(power_dev or None), C.c_void_p(rows_dev or None),
-                                                      C.c_void_p(slots_dev or None), int(n_blocks), C.c_void_p(meas_dev or None)))
-
-    def close(self):
-        """iqd_measure_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
-        if self._h and self._e._h:
-            self._L.iqd_measure_destroy(self._h)
-        self._h = None
-
-    __del__ = close
+        self._e._check(self._L.iqd_measure_run_device(self._h, _dev_ptr(power_dev), _dev_ptr(rows_dev),
+                                                      _dev_ptr(slots_dev), int(n_blocks), _dev_ptr(meas_dev)))
 
 
 def tracklog_defaults():
@@ -1242,15 +1192,13 @@ def tracklog_mean_centre(sum_centre_q8, n_active):
     return out.value
 
 
-class TrackLog:
+class TrackLog(_EngineChild):
     """iqd_tracklog_*: a running summary of every (source, slot) of a Tracker's table over its track's whole life - blocks
     seen and active, the mean centre's sum, the measurements' extremes, a mode hint voted over every measured block - and one
     event record per track that ends with at least min_active active blocks.  n_slots is the Tracker's.  State is carried from
     call to call until reset()."""
 
     def __init__(self, engine, n_sources=1, n_slots=8, max_events=None, min_active=None, vote_min=None, reserved=(0, 0, 0)):
-        self._e, self._L = engine, engine._L
-        self._h = None
         self.n_sources, self.n_slots = int(n_sources), int(n_slots)
         given = dict(max_events=max_events, min_active=min_active, vote_min=vote_min)
         v = dict(tracklog_defaults(), **{k: x for k, x in given.items() if x is not None})
@@ -1258,12 +1206,7 @@ class TrackLog:
         cfg = TrackLogConfig(*[int(x) & 0xffffffff for x in (n_sources, n_slots, v["max_events"], v["min_active"], v["vote_min"])])
         for i in range(3):
             cfg.reserved[i] = int(reserved[i]) & 0xffffffff
-        h = C.c_void_p()
-        engine._check(self._L.iqd_tracklog_create(engine._h, C.byref(cfg), C.byref(h)))
-        self._h = h
-        if not hasattr(engine, "_children"):
-            engine._children = weakref.WeakSet()
-        engine._children.add(self)
+        self._create(engine, "tracklog", cfg)
 
     def run(self, slots, meas):
         """slots [n_sources, n_blocks, n_slots] TRACK_SLOT and meas [n_sources, n_blocks, n_slots] TRACK_MEASURE (host arrays:
@@ -1277,16 +1220,14 @@ class TrackLog:
         summary = np.zeros((self.n_sources, nb, self.n_slots), TRACK_SUMMARY)
         events = np.zeros((self.n_sources, self.max_events), TRACK_SUMMARY)
         counts = np.zeros(self.n_sources, TRACKLOG_COUNTS)
-        one = np.zeros(64, np.uint8)                              # (a refused call gets valid pointers all the same)
-        self._e._check(self._L.iqd_tracklog_run(self._h, _np_ptr(slots if nb else one), _np_ptr(meas if nb else one), nb,
-                                                _np_ptr(summary if nb else one), _np_ptr(events), _np_ptr(counts)))
+        self._e._check(self._L.iqd_tracklog_run(self._h, _ptr_or_placeholder(slots), _ptr_or_placeholder(meas), nb, _ptr_or_placeholder(summary),
+                                                _np_ptr(events), _np_ptr(counts)))
         return summary, events, counts
 
     def run_device(self, slots_dev, meas_dev, n_blocks, summary_dev, events_dev, counts_dev):
         """iqd_tracklog_run_device: device pointers (integers), queued on the engine's stream."""
-        self._e._check(self._L.iqd_tracklog_run_device(self._h, C.c_void_p(slots_dev or None), C.c_void_p(meas_dev or None), int(n_blocks),
-                                                       C.c_void_p(summary_dev or None), C.c_void_p(events_dev or None),
-                                                       C.c_void_p(counts_dev or None)))
+        self._e._check(self._L.iqd_tracklog_run_device(self._h, _dev_ptr(slots_dev), _dev_ptr(meas_dev), int(n_blocks),
+                                                       _dev_ptr(summary_dev), _dev_ptr(events_dev), _dev_ptr(counts_dev)))
 
     def reset(self):
         """iqd_tracklog_reset: every summary free, block indices count from 0 again."""
@@ -1301,11 +1242,3 @@ class TrackLog:
             raise IqdError(-1, "iqd_tracklog_get_state: source %r out of range" % (source,))
         self._e._check(self._L.iqd_tracklog_get_state(self._h, int(source), _np_ptr(out), C.byref(g)))
         return out, g.value
-
-    def close(self):
-        """iqd_tracklog_destroy; Engine.close() calls it first, so it never runs on a destroyed engine's stream."""
-        if self._h and self._e._h:
-            self._L.iqd_tracklog_destroy(self._h)
-        self._h = None
-
-    __del__ = close

@@ -1,8 +1,10 @@
 // The band activity detector of libiqdemod.so (include/iqdemod.h: iqd_detect_*), on the engine's stream.  Kernel: iqd_detect.hip.
-#include "iqd_engine_impl.h"
+// Here: the config's ranges, the call's arrays, its row count's refusals and the launch; the skeleton around them is iqd_band_host.h.
+#include "iqd_band_host.h"
 #include "iqd_detect.h"
 
 static_assert(sizeof(iqd_detect_row) == iqd::DET_ROW_BYTES && sizeof(iqd_detection) == iqd::DET_RECORD_BYTES, "the ABI's records");
+static_assert(DET_MIN_BINS == BAND_MIN_BINS && DET_MAX_BINS == BAND_MAX_BINS, "the shared refusals' bounds");
 
 struct iqd_detect {
     iqd_t *e = nullptr;
@@ -10,13 +12,11 @@ struct iqd_detect {
     DevBuf st_in, st_rows, st_det;
 };
 
-static bool detect_bins_ok(uint32_t n) { return n >= DET_MIN_BINS && n <= DET_MAX_BINS && (n & (n - 1)) == 0; }
-
 extern "C" {
 
 int iqd_detect_offset_hz(uint32_t n_bins, uint32_t rate_hz, uint32_t centroid_q8, int64_t *hz)
 {
-    if (!hz || !detect_bins_ok(n_bins) || rate_hz == 0 || centroid_q8 >= 256u * n_bins) return IQD_EINVAL;
+    if (!hz || !band_bins_ok(n_bins) || rate_hz == 0 || centroid_q8 >= 256u * n_bins) return IQD_EINVAL;
     const int64_t den = 256ll * n_bins;
     const int64_t num = ((int64_t)centroid_q8 - 128ll * n_bins) * rate_hz + 128ll * n_bins;     // |num| < 2^19 x 2^32
     *hz = num / den - (num % den < 0 ? 1 : 0);
@@ -25,11 +25,10 @@ int iqd_detect_offset_hz(uint32_t n_bins, uint32_t rate_hz, uint32_t centroid_q8
 
 int iqd_detect_create(iqd_t *e, const iqd_detect_config *cfg, iqd_detect_t **out)
 {
-    if (!e) return IQD_EINVAL;
-    if (!out) return e->fail(IQD_EINVAL, "iqd_detect_create: out is NULL");
-    if (!cfg) return e->fail(IQD_EINVAL, "iqd_detect_create: cfg is NULL");
+    int rc = band_create_check(e, cfg, out, __func__);
+    if (rc != IQD_OK) return rc;
     const uint32_t n = cfg->n_bins;
-    if (!detect_bins_ok(n)) return e->fail(IQD_EINVAL, "iqd_detect_create: n_bins (%u) must be 64, 128, 256, 512, 1024 or 2048", n);
+    if ((rc = band_bins_check(e, n, __func__)) != IQD_OK) return rc;
     if (cfg->floor_rank >= n) return e->fail(IQD_EINVAL, "iqd_detect_create: floor_rank (%u) must be below n_bins (%u)", cfg->floor_rank, n);
     if (cfg->ratio_q8 < DET_MIN_RATIO || cfg->ratio_q8 > DET_MAX_RATIO)
         return e->fail(IQD_EINVAL, "iqd_detect_create: ratio_q8 (%u) must be 256 .. 2^24", cfg->ratio_q8);
@@ -39,7 +38,7 @@ int iqd_detect_create(iqd_t *e, const iqd_detect_config *cfg, iqd_detect_t **out
         return e->fail(IQD_EINVAL, "iqd_detect_create: min_width (%u) must be 1 .. n_bins (%u)", cfg->min_width, n);
     if (cfg->max_detections == 0 || cfg->max_detections > n / 2)
         return e->fail(IQD_EINVAL, "iqd_detect_create: max_detections (%u) must be 1 .. n_bins / 2 (%u)", cfg->max_detections, n / 2);
-    if (cfg->reserved[0]) return e->fail(IQD_EINVAL, "iqd_detect_create: reserved[0] is not 0");
+    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
     iqd_detect *d = new (std::nothrow) iqd_detect;
     if (!d) return IQD_ENOMEM;
     d->e = e;
@@ -48,22 +47,22 @@ int iqd_detect_create(iqd_t *e, const iqd_detect_config *cfg, iqd_detect_t **out
     return IQD_OK;
 }
 
-void iqd_detect_destroy(iqd_detect_t *d)
+void iqd_detect_destroy(iqd_detect_t *d) { band_destroy(d); }
+
+// the call's arrays, as run stages them
+static BandArgs<3> detect_args(iqd_detect_t *d, const void *power, size_t n_rows, void *rows, void *det)
 {
-    if (!d) return;
-    (void)hipSetDevice(d->e->device);
-    (void)hipStreamSynchronize(d->e->stream);
-    delete d;
+    return {{{"power", power, n_rows * d->cfg.n_bins * sizeof(uint32_t), &d->st_in, BAND_IN},
+             {"rows", rows, n_rows * sizeof(iqd_detect_row), &d->st_rows, BAND_OUT},
+             {"det", det, n_rows * d->cfg.max_detections * sizeof(iqd_detection), &d->st_det, BAND_OUT}}};
 }
 
-// the refusals of a run, before anything is queued
-static int detect_run_check(iqd_detect_t *d, const void *power, size_t n_rows, const void *rows, const void *det, const char *who)
+// rows have no sources: the count's refusals are the detector's own
+static int detect_run_check(iqd_detect_t *d, const BandArgs<3> &args, size_t n_rows, const char *who)
 {
-    if (!d) return IQD_EINVAL;
     iqd_t *e = d->e;
-    if (!power) return e->fail(IQD_EINVAL, "%s: power is NULL", who);
-    if (!rows) return e->fail(IQD_EINVAL, "%s: rows is NULL", who);
-    if (!det) return e->fail(IQD_EINVAL, "%s: det is NULL", who);
+    int rc = band_null_check(e, args, who);
+    if (rc != IQD_OK) return rc;
     if (n_rows == 0) return e->fail(IQD_EINVAL, "%s: n_rows is 0", who);
     if (n_rows > DET_MAX_ROWS) return e->fail(IQD_EINVAL, "%s: n_rows (%zu) is more than one launch covers (2^31 - 1)", who, n_rows);
     return IQD_OK;
@@ -71,12 +70,12 @@ static int detect_run_check(iqd_detect_t *d, const void *power, size_t n_rows, c
 
 int iqd_detect_run_device(iqd_detect_t *d, const uint32_t *power_dev, size_t n_rows, iqd_detect_row *rows_dev, iqd_detection *det_dev)
 {
-    int rc = detect_run_check(d, power_dev, n_rows, rows_dev, det_dev, "iqd_detect_run_device");
-    if (rc != IQD_OK) return rc;
+    if (!d) return IQD_EINVAL;
     iqd_t *e = d->e;
-    if ((uintptr_t)power_dev % 16) return e->fail(IQD_EINVAL, "iqd_detect_run_device: power_dev is not 16-byte aligned");
-    if ((uintptr_t)rows_dev % 16) return e->fail(IQD_EINVAL, "iqd_detect_run_device: rows_dev is not 16-byte aligned");
-    if ((uintptr_t)det_dev % 16) return e->fail(IQD_EINVAL, "iqd_detect_run_device: det_dev is not 16-byte aligned");
+    const BandArgs<3> args = detect_args(d, power_dev, n_rows, rows_dev, det_dev);
+    int rc = detect_run_check(d, args, n_rows, __func__);
+    if (rc == IQD_OK) rc = band_align_check(e, args, __func__);
+    if (rc != IQD_OK) return rc;
     (void)hipSetDevice(e->device);
     const iqd_detect_config &c = d->cfg;
     DetLaunch a{};
@@ -89,22 +88,13 @@ int iqd_detect_run_device(iqd_detect_t *d, const uint32_t *power_dev, size_t n_r
 
 int iqd_detect_run(iqd_detect_t *d, const uint32_t *power, size_t n_rows, iqd_detect_row *rows, iqd_detection *det)
 {
-    int rc = detect_run_check(d, power, n_rows, rows, det, "iqd_detect_run");
+    if (!d) return IQD_EINVAL;
+    const BandArgs<3> args = detect_args(d, power, n_rows, rows, det);
+    int rc = detect_run_check(d, args, n_rows, __func__);
     if (rc != IQD_OK) return rc;
-    iqd_t *e = d->e;
-    (void)hipSetDevice(e->device);
-    const size_t ib = n_rows * d->cfg.n_bins * sizeof(uint32_t), rb = n_rows * sizeof(iqd_detect_row);
-    const size_t db = n_rows * d->cfg.max_detections * sizeof(iqd_detection);
-    HIP_TRY(e, d->st_in.ensure(ib));
-    HIP_TRY(e, d->st_rows.ensure(rb));
-    HIP_TRY(e, d->st_det.ensure(db));
-    HIP_COPY(e, hipMemcpyAsync(d->st_in.p, power, ib, hipMemcpyHostToDevice, e->stream));
-    rc = iqd_detect_run_device(d, d->st_in.as<const uint32_t>(), n_rows, d->st_rows.as<iqd_detect_row>(), d->st_det.as<iqd_detection>());
-    if (rc != IQD_OK) return rc;
-    HIP_COPY(e, hipMemcpyAsync(rows, d->st_rows.p, rb, hipMemcpyDeviceToHost, e->stream));
-    HIP_COPY(e, hipMemcpyAsync(det, d->st_det.p, db, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return IQD_OK;
+    return band_staged_run(d->e, args, [&] {
+        return iqd_detect_run_device(d, d->st_in.as<const uint32_t>(), n_rows, d->st_rows.as<iqd_detect_row>(), d->st_det.as<iqd_detection>());
+    });
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
 // The band spectrum of libiqdemod.so (include/iqdemod.h: iqd_spectrum_*), on the engine's stream.  Kernel: iqd_spectrum.hip.
-#include "iqd_engine_impl.h"
+// Here: the window and the matrix packing, the config's and the lengths' refusals, the call's arrays and the launch; the skeleton
+// around them is iqd_band_host.h.
+#include "iqd_band_host.h"
 #include "iqd_chan.h"
 #include "iqd_spectrum.h"
 
@@ -10,7 +12,7 @@ struct iqd_spectrum {
     DevBuf st_in, st_out;
 };
 
-static bool spectrum_bins_ok(uint32_t n) { return n >= SPC_MIN_BINS && n <= SPC_MAX_BINS && (n & (n - 1)) == 0; }
+static_assert(SPC_MIN_BINS == BAND_MIN_BINS && SPC_MAX_BINS == BAND_MAX_BINS, "the shared refusals' bounds");
 
 // the window's bounds (include/iqdemod.h): the first entry out of range, n if the sum is, -1 if all hold
 static int64_t spectrum_window_bad(const int16_t *w, uint32_t n)
@@ -64,7 +66,7 @@ extern "C" {
 
 int iqd_spectrum_default_window(uint32_t n_bins, int16_t *out)
 {
-    if (!out || !spectrum_bins_ok(n_bins)) return IQD_EINVAL;
+    if (!out || !band_bins_ok(n_bins)) return IQD_EINVAL;
     std::vector<int16_t> phasor(2 * CHZ_PHASOR);
     chz_phasor_table(phasor.data());
     spectrum_default_window(phasor.data(), n_bins, out);
@@ -73,7 +75,7 @@ int iqd_spectrum_default_window(uint32_t n_bins, int16_t *out)
 
 int iqd_spectrum_full_scale(const int16_t *window, uint32_t n_bins, uint32_t *p_fs)
 {
-    if (!p_fs || !spectrum_bins_ok(n_bins)) return IQD_EINVAL;
+    if (!p_fs || !band_bins_ok(n_bins)) return IQD_EINVAL;
     std::vector<int16_t> w(n_bins);
     if (window) {
         if (spectrum_window_bad(window, n_bins) >= 0) return IQD_EINVAL;
@@ -90,18 +92,15 @@ int iqd_spectrum_full_scale(const int16_t *window, uint32_t n_bins, uint32_t *p_
 
 int iqd_spectrum_create(iqd_t *e, const iqd_spectrum_config *cfg, iqd_spectrum_t **out)
 {
-    if (!e) return IQD_EINVAL;
-    if (!out) return e->fail(IQD_EINVAL, "iqd_spectrum_create: out is NULL");
-    if (!cfg) return e->fail(IQD_EINVAL, "iqd_spectrum_create: cfg is NULL");
+    int rc = band_create_check(e, cfg, out, __func__);
+    if (rc != IQD_OK) return rc;
     if (cfg->n_sources == 0) return e->fail(IQD_EINVAL, "iqd_spectrum_create: n_sources is 0");
-    if (!spectrum_bins_ok(cfg->n_bins))
-        return e->fail(IQD_EINVAL, "iqd_spectrum_create: n_bins (%u) must be 64, 128, 256, 512, 1024 or 2048", cfg->n_bins);
+    if ((rc = band_bins_check(e, cfg->n_bins, __func__)) != IQD_OK) return rc;
     if (cfg->sample_format == IQD_WIDE_S16)
         return e->fail(IQD_EINVAL, "iqd_spectrum_create: sample_format IQD_WIDE_S16 is not supported (IQD_WIDE_U8 or IQD_WIDE_S8)");
     if (cfg->sample_format > IQD_WIDE_S16)
         return e->fail(IQD_EINVAL, "iqd_spectrum_create: sample_format (%u) is none of IQD_WIDE_U8, IQD_WIDE_S8", cfg->sample_format);
-    for (int i = 0; i < 3; i++)
-        if (cfg->reserved[i]) return e->fail(IQD_EINVAL, "iqd_spectrum_create: reserved[%d] is not 0", i);
+    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
     const uint32_t n = cfg->n_bins;
     if (cfg->window) {
         const int64_t bad = spectrum_window_bad(cfg->window, n);
@@ -125,22 +124,22 @@ int iqd_spectrum_create(iqd_t *e, const iqd_spectrum_config *cfg, iqd_spectrum_t
     return IQD_OK;
 }
 
-void iqd_spectrum_destroy(iqd_spectrum_t *s)
+void iqd_spectrum_destroy(iqd_spectrum_t *s) { band_destroy(s); }
+
+// the call's arrays, as run stages them: [n_sources] captures in, [n_sources][n_blocks][n_bins] powers out
+static BandArgs<2> spectrum_args(iqd_spectrum_t *s, const void *wide, size_t bytes_per_source, uint32_t frames, void *power)
 {
-    if (!s) return;
-    (void)hipSetDevice(s->e->device);
-    (void)hipStreamSynchronize(s->e->stream);
-    delete s;
+    const size_t n_blocks = frames ? bytes_per_source / ((size_t)2 * s->n * frames) : 0;
+    return {{{"wide", wide, (size_t)s->n_src * bytes_per_source, &s->st_in, BAND_IN},
+             {"power", power, (size_t)s->n_src * n_blocks * s->n * sizeof(uint32_t), &s->st_out, BAND_OUT}}};
 }
 
-// the refusals of a run, before anything is queued
-static int spectrum_run_check(iqd_spectrum_t *s, const void *wide, size_t bytes_per_source, uint32_t frames, const void *power,
-                              const char *who)
+// a call is whole blocks of frames_per_block frames: the lengths' refusals are the spectrum's own
+static int spectrum_run_check(iqd_spectrum_t *s, const BandArgs<2> &args, size_t bytes_per_source, uint32_t frames, const char *who)
 {
-    if (!s) return IQD_EINVAL;
     iqd_t *e = s->e;
-    if (!wide) return e->fail(IQD_EINVAL, "%s: wide is NULL", who);
-    if (!power) return e->fail(IQD_EINVAL, "%s: power is NULL", who);
+    int rc = band_null_check(e, args, who);
+    if (rc != IQD_OK) return rc;
     if (frames == 0 || frames > SPC_MAX_FRAMES) return e->fail(IQD_EINVAL, "%s: frames_per_block (%u) must be 1 .. 2^24", who, frames);
     const size_t blk = (size_t)2 * s->n * frames;
     if (bytes_per_source == 0 || bytes_per_source % blk != 0)
@@ -156,11 +155,12 @@ static int spectrum_run_check(iqd_spectrum_t *s, const void *wide, size_t bytes_
 int iqd_spectrum_run_device(iqd_spectrum_t *s, const void *wide_dev, size_t bytes_per_source, uint32_t frames_per_block,
                             uint32_t *power_dev)
 {
-    int rc = spectrum_run_check(s, wide_dev, bytes_per_source, frames_per_block, power_dev, "iqd_spectrum_run_device");
-    if (rc != IQD_OK) return rc;
+    if (!s) return IQD_EINVAL;
     iqd_t *e = s->e;
-    if ((uintptr_t)wide_dev % 16) return e->fail(IQD_EINVAL, "iqd_spectrum_run_device: wide_dev is not 16-byte aligned");
-    if ((uintptr_t)power_dev % 16) return e->fail(IQD_EINVAL, "iqd_spectrum_run_device: power_dev is not 16-byte aligned");
+    const BandArgs<2> args = spectrum_args(s, wide_dev, bytes_per_source, frames_per_block, power_dev);
+    int rc = spectrum_run_check(s, args, bytes_per_source, frames_per_block, __func__);
+    if (rc == IQD_OK) rc = band_align_check(e, args, __func__);
+    if (rc != IQD_OK) return rc;
     (void)hipSetDevice(e->device);
     SpcLaunch a{};
     a.wide = (const uint8_t *)wide_dev; a.power = power_dev; a.amat = s->amat.as<const uint4>();
@@ -173,20 +173,13 @@ int iqd_spectrum_run_device(iqd_spectrum_t *s, const void *wide_dev, size_t byte
 
 int iqd_spectrum_run(iqd_spectrum_t *s, const void *wide, size_t bytes_per_source, uint32_t frames_per_block, uint32_t *power)
 {
-    int rc = spectrum_run_check(s, wide, bytes_per_source, frames_per_block, power, "iqd_spectrum_run");
+    if (!s) return IQD_EINVAL;
+    const BandArgs<2> args = spectrum_args(s, wide, bytes_per_source, frames_per_block, power);
+    int rc = spectrum_run_check(s, args, bytes_per_source, frames_per_block, __func__);
     if (rc != IQD_OK) return rc;
-    iqd_t *e = s->e;
-    (void)hipSetDevice(e->device);
-    const size_t ib = (size_t)s->n_src * bytes_per_source;
-    const size_t ob = (size_t)s->n_src * (bytes_per_source / ((size_t)2 * s->n * frames_per_block)) * s->n * sizeof(uint32_t);
-    HIP_TRY(e, s->st_in.ensure(ib));
-    HIP_TRY(e, s->st_out.ensure(ob));
-    HIP_COPY(e, hipMemcpyAsync(s->st_in.p, wide, ib, hipMemcpyHostToDevice, e->stream));
-    rc = iqd_spectrum_run_device(s, s->st_in.p, bytes_per_source, frames_per_block, s->st_out.as<uint32_t>());
-    if (rc != IQD_OK) return rc;
-    HIP_COPY(e, hipMemcpyAsync(power, s->st_out.p, ob, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return IQD_OK;
+    return band_staged_run(s->e, args, [&] {
+        return iqd_spectrum_run_device(s, s->st_in.p, bytes_per_source, frames_per_block, s->st_out.as<uint32_t>());
+    });
 }
 
 }  // extern "C"

@@ -13,68 +13,43 @@ line and writes it to profiles/spectrum_bench.json:
                  their share of the matrix cores' dense int8 rate, 2.5 x 10^15 MAC/s (twice the 2.5 PF BF16 rate)
   survey_ms      the 163-point survey of tools/chan_bench.py --survey on the same capture (block_bytes 32768: the same
                  2^18 capture bytes per block), and over_survey = spectrum_ms / survey_ms per N"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import band_bench_common as bb
 
 I8_MAC_PEAK = 2.5e15
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--settle-ms", type=float, default=300.0)
-    ap.add_argument("--sizes", default="256,1024,2048")
-    ap.add_argument("--no-write", action="store_true", help="print only")
-    args = ap.parse_args()
-    from chan_bench import timed
+    args = bb.arguments()
     from rtlsdrdiags_amd import capi, synth
 
-    n_src, bps, M, n_pts, bb = 16, 1 << 20, 8, 163, 32768
-    sizes = [int(v) for v in args.sizes.split(",")]
+    n_src, bps, M, n_pts, block = bb.N_SRC, bb.BPS, 8, 163, 32768
     eng = capi.Engine(1)
     d_in = eng.dev_alloc(n_src * bps)
     eng.dev_upload(d_in, np.concatenate([synth.white_u8(bps // 2, seed=s) for s in range(n_src)]))
     calls = {}
-    for N in sizes:
+    for N in args.sizes:
         F = (1 << 17) // N
         s = capi.Spectrum(eng, N, n_sources=n_src)
         d_out = eng.dev_alloc(n_src * (bps // (2 * N * F)) * N * 4)
         calls[N] = (lambda s=s, F=F, d_out=d_out: s.run_device(d_in, bps, F, d_out))
     zs = capi.Channelizer(eng, M, 1, n_src)
     zs.set_survey(offset_hz=[12500.0 * (p - n_pts // 2) for p in range(n_pts)], fs=256000.0 * M, gain_shift=3)
-    d_mag = eng.dev_alloc(n_src * (bps // M // bb) * n_pts * 4)
-    survey = lambda: zs.survey_device(d_in, bps, bb, d_mag)
+    d_mag = eng.dev_alloc(n_src * (bps // M // block) * n_pts * 4)
+    calls["survey"] = lambda: zs.survey_device(d_in, bps, block, d_mag)
 
-    ms = {N: [] for N in sizes}
-    sv = []
-    for _ in range(3):
-        for N in sizes:
-            ms[N].append(round(timed(calls[N], eng.synchronize, args.steps, args.settle_ms)[0], 4))
-        sv.append(round(timed(survey, eng.synchronize, args.steps, args.settle_ms)[0], 4))
+    ms, med = bb.alternate(calls, eng, args)
     samples = n_src * bps // 2
-    sv_med = float(np.median(sv))
     line = {"workload": "band spectrum, 16 sources x 2^20 bytes / blocks of 2^18 bytes (F = 2^17 / N) / default window / u8",
-            "steps": args.steps, "settle_ms": args.settle_ms, "survey_ms": sv, "sizes": {}}
-    for N in sizes:
-        med = float(np.median(ms[N]))
+            "steps": args.steps, "settle_ms": args.settle_ms, "survey_ms": ms["survey"], "sizes": {}}
+    for N in args.sizes:
         macs = 8 * N * samples
         line["sizes"][str(N)] = {"frames_per_block": (1 << 17) // N, "spectrum_ms": ms[N],
-                                 "gsamples_s": round(samples / med / 1e6, 2), "mac_s": float("%.4g" % (macs / (med / 1e3))),
-                                 "mfma_share": round(macs / (med / 1e3) / I8_MAC_PEAK, 4),
-                                 "over_survey": round(med / sv_med, 4)}
-    print(json.dumps(line))
-    if not args.no_write:
-        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-        with open(os.path.join(ROOT, "profiles", "spectrum_bench.json"), "w") as f:
-            f.write(json.dumps(line) + "\n")
+                                 "gsamples_s": round(samples / med[N] / 1e6, 2), "mac_s": float("%.4g" % (macs / (med[N] / 1e3))),
+                                 "mfma_share": round(macs / (med[N] / 1e3) / I8_MAC_PEAK, 4),
+                                 "over_survey": round(med[N] / med["survey"], 4)}
+    bb.finish(line, args, "spectrum_bench.json")
     eng.close()
 
 
