@@ -1,5 +1,6 @@
 // Wideband channelizer (include/iqdemod.h: iqd_channelizer_*): launch descriptor of the gfx950 kernel and the host-only
-// pieces of its integer spec, shared by iqd_chan.hip (device) and iqd_chan.cpp (host orchestration).
+// pieces of its integer spec, shared by iqd_chan.hip (device) and the host code (iqd_chan.cpp, iqd_chan_layout.cpp,
+// iqd_chan_design.cpp, iqd_chan_survey.cpp).
 //
 // Per source the filter is a GEMM on v_mfma_i32_16x16x64_i8: A = (8 channels x {Ar, Ai}) x (2 Kp bytes of window),
 // B = (2 Kp bytes) x (16 outputs), the sliding window over the source's interleaved signed bytes.  Kp = K rounded up to
@@ -186,9 +187,9 @@ hipError_t launch_channelizer_gain(const ChzLaunch &a, uint32_t n_wgs, const Chz
 // per run of run_blocks table blocks chz_track_build_kernel and chz_track_kernel<0> (iqd_chan_track.hip)
 hipError_t launch_channelizer_track(const ChzLaunch &a, uint32_t n_wgs, const ChzTrackLaunch &t, uint32_t run_blocks, hipStream_t st);
 
-// host-only spec pieces (iqd_chan.cpp)
+// host-only spec pieces (iqd_chan_design.cpp)
 void chz_phasor_table(int16_t *out /* [8192] (c, s) pairs */);
-// complex taps of one channel: gr, gi [K]
+// complex taps of one channel: gr, gi [K] (iqd_chan_layout.cpp)
 void chz_channel_taps(const int16_t *h, uint32_t k, uint32_t inc, const int16_t *phasor, int16_t *gr, int16_t *gi);
 
 // the engine's side (iqd_engine.cpp)

@@ -10,7 +10,7 @@
 #include "iqd_engine_impl.h"
 #include "iqd_chan.h"
 
-// The channelizer (iqd_chan.cpp) reports through the engine's error text and needs its call geometry.
+// The channelizer (iqd_chan.cpp, iqd_chan_survey.cpp) reports through the engine's error text and needs its call geometry.
 namespace iqd {
 int engine_fail(iqd_t *e, int code, const char *msg) { return e->fail(code, "%s", msg); }
 void engine_geometry(const iqd_t *e, uint32_t *n_ch, uint32_t *block_bytes, uint32_t *flags)

@@ -1,6 +1,6 @@
 // The engine behind the C ABI (include/iqdemod.h), for the translation units that implement it: iqd_engine.cpp (lifecycle,
 // setters, AGC, scanner, traces, stats), iqd_accept.cpp (the accept path), iqd_resampler.cpp and iqd_devmem.cpp.  Internal:
-// the channelizer (iqd_chan.cpp) talks to the engine through the shims of iqd_chan.h and does not see this struct.
+// the channelizer (iqd_chan.cpp, iqd_chan_survey.cpp) talks to the engine through the shims of iqd_chan.h and does not see this struct.
 #pragma once
 #include "iqdemod.h"
 

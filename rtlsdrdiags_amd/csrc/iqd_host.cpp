@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "iqdemod.h"
 #include "iqd_taps.h"
 #include "iqd_prims.h"
 #include "iqd_stream.h"
@@ -101,6 +102,17 @@ void build_consts(Consts &c)
     c.deemph_cinv = (float)(1.0 / cc);
     c.dc_a1 = taps::DCBLOCK_A1;
     c.dc_cseg = (float)pow(-(double)taps::DCBLOCK_A1, 32.0);
+}
+
+// DbfsCalculator's table as the squelch reads it (db_table above, magnitude_dbfs in iqd_chains.h)
+extern "C" int32_t iqd_magnitude_dbfs(uint32_t magnitude)
+{
+    static const std::vector<int32_t> table = [] {
+        Consts c;
+        build_consts(c);
+        return std::vector<int32_t>(c.db_table, c.db_table + 128);
+    }();
+    return table[magnitude > 127u ? 127u : magnitude] - 42;
 }
 
 void build_atan2_lut(std::vector<float> &lut)

@@ -10,7 +10,7 @@ INCS = [0, 1, 2 ** 31, 2 ** 31 - 1, 2 ** 32 - 1]
 
 
 def window(M, Q, K):
-    """outputs per window of the kernels (iqd_chan.cpp: chz_t_max)"""
+    """outputs per window of the kernels (iqd_chan_layout.h: ChzGeometry::t_max)"""
     kb = -(-K // Q)
     kp = -(-kb // 32) * 32
     if Q > 1:

@@ -63,7 +63,7 @@ MODEL_BUDGET = 4e7        # tap x wideband-sample products the model may spend p
 
 
 def t_max(M, K):
-    """outputs per window of the kernels (iqd_chan.cpp: chz_queue)"""
+    """outputs per window of the kernels (iqd_chan.cpp: chz_launch)"""
     kp = (K + 31) // 32 * 32
     return min(1024, (16384 - kp) // M) // 64 * 64
 
@@ -290,7 +290,7 @@ def plain_case(rng, ctx):
 
 # ------------------------------------------------------------------------------------------------ fractional cases
 def frac_t_max(P, Q, kb):
-    """outputs per window of chz_frac_kernel (iqd_chan.cpp: chz_queue)"""
+    """outputs per window of chz_frac_kernel (iqd_chan.cpp: chz_launch)"""
     kp = (kb + 31) // 32 * 32
     g = 16 * max(4, Q)
     return min(1024, (12288 - kp) * Q // P) // g * g
