@@ -13,110 +13,68 @@
 //   chunk     samples per channel and call (default 65536); the filter state carries over, so the output does not depend
 //             on it
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "iqd_tool_chain.h"
 
-#include <string>
-#include <vector>
-
-#include "iqdemod.h"
-
-namespace {
-
-bool readCoefficients(const std::string &path, std::vector<float> &v)
-{
-  FILE *f = fopen(path.c_str(), "r");
-  if (!f) return false;
-  char tok[128];
-  while (fscanf(f, " %127[^ \t\r\n,]", tok) == 1) {
-    v.push_back(strtof(tok, nullptr));
-    int c = fgetc(f);
-    if (c != ',' && c != EOF) ungetc(c, f);
-  }
-  fclose(f);
-  return !v.empty();
-}
-
-std::string channelName(const std::string &pattern, uint32_t ch)
-{
-  char buf[4096];
-  snprintf(buf, sizeof(buf), pattern.c_str(), ch);
-  return buf;
-}
-
-}  // namespace
+using namespace iqdtool;
 
 int main(int argc, char **argv)
 {
+  const char *const TOOL = "iqdemod_filter";
   std::string kindName, tapsPath, denPath, in, out;
   uint32_t factor = 1, channels = 0;
   size_t chunk = 65536;
-  for (int i = 1; i < argc; i++) {
-    const char *a = argv[i];
-    if (!strncmp(a, "kind=", 5)) kindName = a + 5;
-    else if (!strncmp(a, "taps=", 5)) tapsPath = a + 5;
-    else if (!strncmp(a, "den=", 4)) denPath = a + 4;
-    else if (!strncmp(a, "factor=", 7)) factor = (uint32_t)strtoul(a + 7, nullptr, 10);
-    else if (!strncmp(a, "channels=", 9)) channels = (uint32_t)strtoul(a + 9, nullptr, 10);
-    else if (!strncmp(a, "in=", 3)) in = a + 3;
-    else if (!strncmp(a, "out=", 4)) out = a + 4;
-    else if (!strncmp(a, "chunk=", 6)) chunk = (size_t)strtoull(a + 6, nullptr, 10);
-    else {
-      fprintf(stderr, "iqdemod_filter: unknown argument %s\n", a);
-      return 1;
-    }
-  }
+  const std::vector<Row> keys = {text("kind=", kindName), text("taps=", tapsPath),  text("den=", denPath), u32("factor=", factor),
+                                 u32("channels=", channels), text("in=", in), text("out=", out), viaStrtoull("chunk=", chunk)};
+  if (!parse(argc, argv, keys, TOOL)) return 1;
   static const char *const kinds[] = {"decimate_i16", "fir_i16", "fir_f32", "iir_f32"};
   int kind = -1;
   for (int k = 0; k < 4; k++)
     if (kindName == kinds[k]) kind = k;
-  const bool files = channels != 0;
-  if (kind < 0 || tapsPath.empty() || chunk == 0 || chunk > 0x7fffffffu || (files && (in.empty() || out.empty())) ||
-      (!files && (!in.empty() || !out.empty()))) {
+  const bool fromFiles = channels != 0;
+  if (kind < 0 || tapsPath.empty() || chunk == 0 || chunk > 0x7fffffffu || (fromFiles && (in.empty() || out.empty())) ||
+      (!fromFiles && (!in.empty() || !out.empty()))) {
     fprintf(stderr, "usage: iqdemod_filter kind=decimate_i16|fir_i16|fir_f32|iir_f32 taps=h.txt [factor=4] [den=a.txt] "
                     "[channels=N in=x_%%d.raw out=y_%%d.raw] [chunk=samples]\n");
     return 1;
   }
   std::vector<float> num, den;
-  if (!readCoefficients(tapsPath, num)) {
+  const auto coefficient = [](const char *tok, float &x) {
+    x = strtof(tok, nullptr);
+    return true;
+  };
+  if (!readNumbers(tapsPath, num, coefficient)) {
     fprintf(stderr, "iqdemod_filter: no coefficients in %s\n", tapsPath.c_str());
     return 1;
   }
-  if (!denPath.empty() && !readCoefficients(denPath, den)) {
+  if (!denPath.empty() && !readNumbers(denPath, den, coefficient)) {
     fprintf(stderr, "iqdemod_filter: no coefficients in %s\n", denPath.c_str());
     return 1;
   }
-  const uint32_t n = files ? channels : 1;
+  const uint32_t n = fromFiles ? channels : 1;
   const size_t elem = kind <= IQD_FILTER_FIR_I16 ? 2 : 4;
 
+  Files files(TOOL);
   std::vector<FILE *> fin(n, nullptr), fout(n, nullptr);
   for (uint32_t c = 0; c < n; c++) {
-    fin[c] = files ? fopen(channelName(in, c).c_str(), "rb") : stdin;
-    fout[c] = files ? fopen(channelName(out, c).c_str(), "wb") : stdout;
+    fin[c] = fromFiles ? files.open(channelName(in, c), "rb", Files::Quiet) : stdin;
+    fout[c] = fromFiles ? files.open(channelName(out, c), "wb", Files::Quiet) : stdout;
     if (!fin[c] || !fout[c]) {
       fprintf(stderr, "iqdemod_filter: cannot open the files of channel %u\n", c);
       return 1;
     }
   }
 
-  iqd_config cfg{};
-  cfg.abi_version = IQD_ABI_VERSION;
-  cfg.n_channels = 1;
-  cfg.device = -1;
-  iqd_t *e = nullptr;
-  int rc = iqd_create(&cfg, &e);
+  Engine e;
+  int rc = createEngine(e, 1);
   if (rc != IQD_OK) {
     fprintf(stderr, "iqdemod_filter: iqd_create: %s\n", iqd_strerror(rc));
     return 1;
   }
-  iqd_filter_t *f = nullptr;
+  Filter f;
   rc = iqd_filter_create(e, kind, num.data(), (uint32_t)num.size(), den.empty() ? nullptr : den.data(), (uint32_t)den.size(),
-                         factor, n, &f);
+                         factor, n, &f.p);
   if (rc != IQD_OK) {
     fprintf(stderr, "iqdemod_filter: iqd_filter_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
-    iqd_destroy(e);
     return 1;
   }
 
@@ -146,11 +104,6 @@ int main(int argc, char **argv)
       }
     if (status != 0 || got < chunk) break;
   }
-  iqd_filter_destroy(f);
-  iqd_destroy(e);
-  for (uint32_t c = 0; c < n; c++) {
-    if (files) fclose(fin[c]);
-    if (files ? fclose(fout[c]) != 0 : fflush(stdout) != 0) status = status ? status : 1;
-  }
+  if ((fromFiles ? !files.close() : fflush(stdout) != 0) && status == 0) status = 1;
   return status;
 }

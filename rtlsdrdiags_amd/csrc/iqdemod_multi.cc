@@ -19,21 +19,15 @@
 // capture that ends inside a call is processed up to its last whole 64-byte unit (a short block, Radio.cc:1895-1906);
 // channels whose captures are shorter than the others simply stop earlier.  Exit status 0, 1 (no device / bad
 // arguments / I/O), 3 (a call was rejected).
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <condition_variable>
 #include <mutex>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "iqdemod.h"
+#include "iqd_tool_chain.h"
 
 namespace {
 
+using namespace iqdtool;
 const size_t BLOCK = 32768;
 
 struct Options {
@@ -44,35 +38,15 @@ struct Options {
   int threshold = -200, agc = -1;
 };
 
-std::vector<int> intList(const char *s)
+bool parseOptions(int argc, char **argv, Options &o)
 {
-  std::vector<int> v;
-  for (const char *q = s; *q;) {
-    v.push_back(atoi(q));
-    const char *c = strchr(q, ',');
-    if (!c) break;
-    q = c + 1;
-  }
-  return v;
-}
-
-bool parse(int argc, char **argv, Options &o)
-{
-  for (int i = 1; i < argc; i++) {
-    const char *a = argv[i];
-    if (!strncmp(a, "channels=", 9)) o.channels = (uint32_t)atoi(a + 9);
-    else if (!strncmp(a, "blocks=", 7)) o.blocks = (uint32_t)atoi(a + 7);
-    else if (!strncmp(a, "in=", 3)) o.in = a + 3;
-    else if (!strncmp(a, "out=", 4)) o.out = a + 4;
-    else if (!strncmp(a, "modes=", 6)) o.modes = intList(a + 6);
-    else if (!strncmp(a, "rotation=", 9)) o.rotations = intList(a + 9);
-    else if (!strncmp(a, "threshold=", 10)) o.threshold = atoi(a + 10);
-    else if (!strncmp(a, "agc=", 4)) o.agc = atoi(a + 4);
-    else if (!strcmp(a, "layout=files")) o.interleaved = false;
-    else if (!strcmp(a, "layout=interleaved")) o.interleaved = true;
-    else return false;
-  }
-  return o.channels > 0 && o.blocks > 0 && !o.in.empty() && !o.out.empty() && !o.modes.empty() && !o.rotations.empty();
+  const std::vector<Row> keys = {viaAtoi("channels=", o.channels), viaAtoi("blocks=", o.blocks), text("in=", o.in), text("out=", o.out),
+                                 {"modes=", [&o](const char *v) { o.modes = intList(v); return true; }},
+                                 {"rotation=", [&o](const char *v) { o.rotations = intList(v); return true; }},
+                                 viaAtoi("threshold=", o.threshold), viaAtoi("agc=", o.agc),
+                                 word("layout=files", [&o] { o.interleaved = false; }), word("layout=interleaved", [&o] { o.interleaved = true; })};
+  return parse(argc, argv, keys, nullptr) && o.channels > 0 && o.blocks > 0 && !o.in.empty() && !o.out.empty() && !o.modes.empty() &&
+         !o.rotations.empty();
 }
 
 // One filled input buffer: [channels][blocks * BLOCK] bytes, of which channel c has got[c] (a multiple of 64)
@@ -84,22 +58,14 @@ struct Batch {
 
 struct Reader {
   const Options &o;
+  Files owned{"iqdemod_multi"};
   std::vector<FILE *> files;
   explicit Reader(const Options &opt) : o(opt) {}
   bool open()
   {
-    char name[4096];
-    if (o.interleaved) {
-      FILE *f = fopen(o.in.c_str(), "rb");
-      if (!f) { perror(o.in.c_str()); return false; }
-      files.push_back(f);
-      return true;
-    }
-    for (uint32_t c = 0; c < o.channels; c++) {
-      snprintf(name, sizeof name, o.in.c_str(), (int)c);
-      FILE *f = fopen(name, "rb");
-      if (!f) { perror(name); return false; }
-      files.push_back(f);
+    for (uint32_t c = 0; c < (o.interleaved ? 1 : o.channels); c++) {
+      files.push_back(owned.open(o.interleaved ? o.in : channelName(o.in, c), "rb", Files::Perror));
+      if (!files.back()) return false;
     }
     return true;
   }
@@ -127,10 +93,6 @@ struct Reader {
       }
     return any;
   }
-  ~Reader()
-  {
-    for (FILE *f : files) fclose(f);
-  }
 };
 
 }  // namespace
@@ -138,19 +100,13 @@ struct Reader {
 int main(int argc, char **argv)
 {
   Options o;
-  if (!parse(argc, argv, o)) {
+  if (!parseOptions(argc, argv, o)) {
     fprintf(stderr, "usage: %s channels=N in=<pattern %%d | file> out=<pattern %%d> [modes=2,3,...] [layout=files|interleaved] "
                     "[blocks=K] [threshold=dBFS] [rotation=1,0,-1,...] [agc=0|1]\n", argv[0]);
     return 1;
   }
-  iqd_config cfg;
-  memset(&cfg, 0, sizeof cfg);
-  cfg.abi_version = IQD_ABI_VERSION;
-  cfg.n_channels = o.channels;
-  cfg.block_bytes = (uint32_t)BLOCK;
-  cfg.device = -1;
-  iqd_t *e = nullptr;
-  int rc = iqd_create(&cfg, &e);
+  Engine e;
+  int rc = createEngine(e, o.channels, (uint32_t)BLOCK);
   if (rc != IQD_OK) {
     fprintf(stderr, "iqdemod_multi: %s\n", iqd_strerror(rc));   // IQD_ENODEV without a GPU: there is no CPU path
     return 1;
@@ -167,32 +123,27 @@ int main(int argc, char **argv)
 
   Reader reader(o);
   if (!reader.open()) return 1;
+  Files sinks("iqdemod_multi");
   std::vector<FILE *> outs(o.channels);
-  for (uint32_t c = 0; c < o.channels; c++) {
-    char name[4096];
-    snprintf(name, sizeof name, o.out.c_str(), (int)c);
-    outs[c] = fopen(name, "wb");
-    if (!outs[c]) { perror(name); return 1; }
-  }
+  for (uint32_t c = 0; c < o.channels; c++)
+    if (!(outs[c] = sinks.open(channelName(o.out, c), "wb", Files::Perror))) return 1;
 
   const size_t row = (size_t)o.blocks * BLOCK, pcmRow = row / 64;
   Batch batch[2];
-  for (Batch &b : batch) {
-    void *p = nullptr;
-    if (iqd_host_alloc(e, (size_t)o.channels * row, &p) != IQD_OK) { fprintf(stderr, "iqdemod_multi: %s\n", iqd_last_error(e)); return 1; }
-    b.iq = (uint8_t *)p;
-    b.got.assign(o.channels, 0);
+  HostBuffer<uint8_t> iq[2];
+  for (int k = 0; k < 2; k++) {
+    if (iq[k].alloc(e, (size_t)o.channels * row, iqd_host_alloc) != IQD_OK) { fprintf(stderr, "iqdemod_multi: %s\n", iqd_last_error(e)); return 1; }
+    batch[k].iq = iq[k];
+    batch[k].got.assign(o.channels, 0);
   }
-  void *pp = nullptr;
-  if (iqd_host_alloc(e, (size_t)o.channels * pcmRow * sizeof(int16_t), &pp) != IQD_OK) return 1;
-  int16_t *pcm = (int16_t *)pp;
+  HostBuffer<int16_t> pcm;
+  if (pcm.alloc(e, (size_t)o.channels * pcmRow, iqd_host_alloc) != IQD_OK) return 1;
   std::vector<uint32_t> count(o.channels);
 
   // the reader runs one batch ahead of the engine
   std::mutex mu;
   std::condition_variable cv;
   int filled[2] = {0, 0};   // 0 free, 1 ready, 2 ready and nothing behind it
-  bool readerDone = false;
   std::thread rd([&] {
     for (int k = 0;; k ^= 1) {
       {
@@ -204,7 +155,7 @@ int main(int argc, char **argv)
       filled[k] = any ? (batch[k].last ? 2 : 1) : 2;
       if (!any) for (size_t &g : batch[k].got) g = 0;
       cv.notify_all();
-      if (filled[k] == 2) { readerDone = true; return; }
+      if (filled[k] == 2) return;
     }
   });
 
@@ -258,12 +209,7 @@ int main(int argc, char **argv)
     if (state == 2) break;
   }
   rd.join();
-  (void)readerDone;
-  for (FILE *f : outs) fclose(f);
   fprintf(stderr, "iqdemod_multi: %u channels, %llu IQ samples in, %llu PCM samples out\n", o.channels,
           (unsigned long long)samples, (unsigned long long)pcmOut);
-  iqd_host_free(e, pcm);
-  for (Batch &b : batch) iqd_host_free(e, b.iq);
-  iqd_destroy(e);
   return status;
 }

@@ -46,439 +46,287 @@
 // A capture that ends inside a block ends with its last whole block; the rest is dropped and counted on stderr.
 // Exit status 0, 1 (no device / bad arguments / I/O), 3 (a call was rejected).
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
-#include <string>
-#include <vector>
-
-#include "iqdemod.h"
+#include "iqd_tool_chain.h"
 
 namespace {
 
-bool readWindow(const std::string &path, std::vector<int16_t> &v)
+using namespace iqdtool;
+const char *const TOOL = "iqdemod_spectrum";
+
+struct Options {
+  std::string in, out, log, window, detect, track, measure, events, format = "u8";
+  double rate = 0.0;
+  uint32_t bins = 0, frames = 0;
+  BandArgs band;
+  int depth() const { return 1 + !detect.empty() + !track.empty() + !measure.empty() + !events.empty(); }   // (once refusal() passed)
+};
+
+// the first thing wrong with the arguments as a whole, as the line to print; nullptr: nothing
+const char *refusal(const Options &o)
 {
-  FILE *f = fopen(path.c_str(), "r");
-  if (!f) return false;
-  char tok[128];
-  bool ok = true;
-  while (fscanf(f, " %127[^ \t\r\n,]", tok) == 1) {
-    char *end = nullptr;
-    const long x = strtol(tok, &end, 10);
-    if (*end != 0 || x < -32768 || x > 32767) ok = false;
-    v.push_back((int16_t)x);
-    int c = fgetc(f);
-    if (c != ',' && c != EOF) ungetc(c, f);
+  const bool detect = !o.detect.empty(), track = !o.track.empty(), measure = !o.measure.empty(), events = !o.events.empty();
+  if (o.in.empty() || o.out.empty() || o.bins == 0 || o.frames == 0 || o.frames > (1u << 24) || !(o.rate > 0.0) ||
+      (o.format != "u8" && o.format != "s8"))
+    return "usage: iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] "
+           "out=power.u32 [log=spectrum.txt] [detect=runs.txt [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=] "
+           "[track=tracks.txt [slots=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c] "
+           "[measure=meas.txt [margin=] [beta_q16=] [carrier=] [minsum=] [carrier_q8=] [wide=] "
+           "[events=events.txt [minactive=] [votemin=] [maxevents=]]]]]\n";
+  if (events && !(track && measure)) return "iqdemod_spectrum: events= needs track= and measure=\n";
+  if (measure && !track) return "iqdemod_spectrum: measure= needs track=\n";
+  if (track && !detect) return "iqdemod_spectrum: track= needs detect=\n";
+  if (detect && (o.rate != floor(o.rate) || o.rate > 4294967295.0))
+    return "iqdemod_spectrum: detect= needs rate as a whole number of Hz below 2^32\n";
+  return nullptr;
+}
+
+// what turns bins and powers into the Hz and dBFS of the text files
+struct Scale {
+  uint32_t bins, frames;
+  double rate;
+  uint32_t pfs;
+  double binHz(uint32_t k) const { return ((double)k - bins / 2) * rate / bins; }
+  double dbfs(uint32_t p) const { return 10.0 * log10((double)(p ? p : 1) / (double)(pfs ? pfs : 1)); }
+  long long hz(uint32_t q8) const
+  {
+    int64_t v = 0;
+    iqd_detect_offset_hz(bins, (uint32_t)rate, q8, &v);
+    return (long long)v;
   }
-  fclose(f);
-  return ok && !v.empty();
+  long long midHz(uint32_t k) const { return hz(256u * k + 128u); }   // the middle of bin k
+};
+
+void writeLog(FILE *f, const Scale &s, uint64_t block, uint32_t k, uint32_t p)
+{
+  fprintf(f, "%llu %.3f %u %.2f\n", (unsigned long long)block, s.binHz(k), p, s.dbfs(p));
+}
+
+void writeDetection(FILE *f, const Scale &s, uint64_t block, const iqd_detection &r)
+{
+  fprintf(f, "%llu %.3f %.3f %lld %.2f %llu\n", (unsigned long long)block, s.binHz(r.first_bin), s.binHz(r.last_bin), s.hz(r.centroid_q8),
+          s.dbfs(r.peak_power), (unsigned long long)r.sum_power);
+}
+
+void writeSlot(FILE *f, const Scale &s, uint64_t block, uint32_t k, const iqd_track_slot &r)
+{
+  fprintf(f, "%llu %u %u %u %u %lld 0x%08x %.3f %.3f %u\n", (unsigned long long)block, k, r.track_id, r.state, r.flags, s.hz(r.centre_q8),
+          r.phase_inc, s.binHz(r.first_bin), s.binHz(r.last_bin), r.width_class);
+}
+
+void writeMeasure(FILE *f, const Scale &s, uint64_t block, uint32_t k, const iqd_track_measure &r)
+{
+  fprintf(f, "%llu %u %u %lld %lld %lld %lld %u %llu %u %u\n", (unsigned long long)block, k, r.track_id, s.midHz(r.obw_lo), s.midHz(r.obw_hi),
+          s.midHz(r.peak_bin), s.hz(r.centroid_q8), r.carrier_q8, (unsigned long long)r.sum_excess, r.flags, r.hint);
+}
+
+// one line of events=: an event, or a track still live at the end of the input
+void writeEvent(FILE *f, const Scale &s, uint32_t slot, const iqd_track_summary &r, bool open)
+{
+  const double blockSeconds = (double)s.bins * s.frames / s.rate;
+  uint32_t mean = 0;
+  const long long cen = iqd_tracklog_mean_centre(r.sum_centre_q8, r.n_active, &mean) == IQD_OK ? s.hz(mean) : 0;
+  const long long lo = r.n_measured ? s.midHz(r.obw_lo_min) : 0, hi = r.n_measured ? s.midHz(r.obw_hi_max) : 0;
+  fprintf(f, "%u %u %llu %u %.6f %.6f %lld %lld %lld %u %u %u %u %u %llu %u%s\n", r.track_id, slot, (unsigned long long)r.first_block,
+          r.n_blocks, (double)r.first_block * blockSeconds, (double)r.n_blocks * blockSeconds, cen, lo, hi, r.mode_hint, r.votes[0],
+          r.votes[1], r.votes[2], r.n_measured, (unsigned long long)(r.n_measured ? r.sum_excess / r.n_measured : 0), r.flags,
+          open ? " open" : "");
+}
+
+// One call's results on the host, and what the run has counted so far
+struct Results {
+  std::vector<uint32_t> power;
+  std::vector<iqd_detect_row> rows;
+  std::vector<iqd_detection> dets;
+  std::vector<iqd_track_slot> slots;
+  std::vector<iqd_track_block> tblocks;
+  std::vector<iqd_track_measure> meas;
+  std::vector<iqd_track_summary> evts;
+  iqd_tracklog_counts counts{};
+  // an event record does not say which slot its track sat in: the tool keeps the id every slot of the table showed last
+  // (0: none, or closed) and names the slot when the table shows that id ending
+  std::vector<uint32_t> slotId;
+  uint64_t block = 0, pastMax = 0, unplaced = 0, eventsPast = 0;
+};
+
+// the device arrays' first nb blocks to the host (the first download waits for the stream)
+int download(const BandChain &c, const BandArgs &a, size_t nb, Results &r)
+{
+  int rc = c.power.download(r.power.data(), nb * a.dc.n_bins);
+  if (rc == IQD_OK) rc = c.rows.download(r.rows.data(), nb);
+  if (rc == IQD_OK) rc = c.det.download(r.dets.data(), nb * a.dc.max_detections);
+  if (rc == IQD_OK && c.made >= BandChain::TRACK) rc = c.slots.download(r.slots.data(), nb * a.tc.n_slots);
+  if (rc == IQD_OK && c.made >= BandChain::TRACK) rc = c.blocks.download(r.tblocks.data(), nb);
+  if (rc == IQD_OK && c.made >= BandChain::MEASURE) rc = c.meas.download(r.meas.data(), nb * a.tc.n_slots);
+  if (rc == IQD_OK && c.made >= BandChain::LOG) rc = c.counts.download(&r.counts, 1);
+  if (rc == IQD_OK && c.made >= BandChain::LOG && r.counts.n_stored) rc = c.events.download(r.evts.data(), r.counts.n_stored);
+  return rc;
+}
+
+// the text files' lines of one call of nb blocks
+void writeCall(const Scale &s, const BandArgs &a, size_t nb, Results &r, FILE *flog, FILE *fdet, FILE *ftrk, FILE *fmsr, FILE *fevt)
+{
+  const uint32_t N = s.bins, D = a.dc.max_detections, S = a.tc.n_slots;
+  for (size_t b = 0; flog && b < nb; b++)
+    for (uint32_t k = 0; k < N; k++) writeLog(flog, s, r.block + b, k, r.power[b * N + k]);
+  for (size_t b = 0; fdet && b < nb; b++) {
+    const uint32_t found = r.rows[b].n_found, shown = found < D ? found : D;
+    r.pastMax += found - shown;
+    for (uint32_t i = 0; i < shown; i++) writeDetection(fdet, s, r.block + b, r.dets[b * D + i]);
+  }
+  for (size_t b = 0; ftrk && b < nb; b++) {
+    r.unplaced += r.tblocks[b].n_unplaced;
+    for (uint32_t k = 0; k < S; k++)
+      if (r.slots[b * S + k].track_id != 0) writeSlot(ftrk, s, r.block + b, k, r.slots[b * S + k]);
+  }
+  for (size_t b = 0; fmsr && b < nb; b++)
+    for (uint32_t k = 0; k < S; k++)
+      if (r.meas[b * S + k].track_id != 0) writeMeasure(fmsr, s, r.block + b, k, r.meas[b * S + k]);
+  if (!fevt) return;
+  // events come in block order and within a block in slot order, and so do the table's endings: walk both together
+  // (an ending with fewer than minactive active blocks is no event and is passed over; the tracker's ids are unique)
+  uint32_t next = 0;
+  for (size_t b = 0; b < nb; b++)
+    for (uint32_t k = 0; k < S; k++) {
+      const iqd_track_slot &q = r.slots[b * S + k];
+      const bool ends = r.slotId[k] != 0 && (q.track_id != r.slotId[k] || q.state == 0);
+      if (ends && next < r.counts.n_stored && r.evts[next].track_id == r.slotId[k]) writeEvent(fevt, s, k, r.evts[next++], false);
+      r.slotId[k] = q.state == 0 ? 0 : q.track_id;
+    }
+  r.eventsPast += r.counts.n_events - r.counts.n_stored;
 }
 
 }  // namespace
 
 int main(int argc, char **argv)
 {
-  std::string in, out, log, windowPath, detectPath, trackPath, measurePath, eventsPath, format = "u8";
-  iqd_tracklog_config lc{};
-  lc.n_sources = 1;
-  lc.max_events = 256;
-  lc.min_active = 2;
-  lc.vote_min = 4;
-  iqd_measure_config mc{};
-  mc.n_sources = 1;
-  mc.obw_tail_q16 = 328;
-  mc.carrier_half = 1;
-  mc.min_sum = 4096;
-  mc.carrier_min_q8 = 160;
-  bool marginGiven = false, wideGiven = false;
-  iqd_track_config tc{};
-  tc.n_sources = 1;
-  tc.n_slots = 8;
-  tc.gate_q8 = 512;
-  tc.open_hits = 3;
-  tc.hold_blocks = 2;
-  tc.alpha_q8 = 64;
-  bool edgesGiven = false;
-  double rate = 0.0;
-  uint32_t bins = 0, frames = 0;
-  iqd_detect_config dc{};
-  dc.ratio_q8 = 2048;
-  dc.dc_guard = 1;
-  dc.bridge = 8;
-  dc.min_width = 3;
-  dc.max_detections = 16;
-  bool rankGiven = false;
-  for (int i = 1; i < argc; i++) {
-    const char *a = argv[i];
-    if (!strncmp(a, "in=", 3)) in = a + 3;
-    else if (!strncmp(a, "out=", 4)) out = a + 4;
-    else if (!strncmp(a, "log=", 4)) log = a + 4;
-    else if (!strncmp(a, "window=", 7)) windowPath = a + 7;
-    else if (!strncmp(a, "format=", 7)) format = a + 7;
-    else if (!strncmp(a, "rate=", 5)) rate = strtod(a + 5, nullptr);
-    else if (!strncmp(a, "bins=", 5)) bins = (uint32_t)strtoul(a + 5, nullptr, 10);
-    else if (!strncmp(a, "frames=", 7)) frames = (uint32_t)strtoul(a + 7, nullptr, 10);
-    else if (!strncmp(a, "detect=", 7)) detectPath = a + 7;
-    else if (!strncmp(a, "rank=", 5)) { dc.floor_rank = (uint32_t)strtoul(a + 5, nullptr, 10); rankGiven = true; }
-    else if (!strncmp(a, "ratio_q8=", 9)) dc.ratio_q8 = (uint32_t)strtoul(a + 9, nullptr, 10);
-    else if (!strncmp(a, "guard=", 6)) dc.dc_guard = (uint32_t)strtoul(a + 6, nullptr, 10);
-    else if (!strncmp(a, "bridge=", 7)) dc.bridge = (uint32_t)strtoul(a + 7, nullptr, 10);
-    else if (!strncmp(a, "minwidth=", 9)) dc.min_width = (uint32_t)strtoul(a + 9, nullptr, 10);
-    else if (!strncmp(a, "maxdet=", 7)) dc.max_detections = (uint32_t)strtoul(a + 7, nullptr, 10);
-    else if (!strncmp(a, "track=", 6)) trackPath = a + 6;
-    else if (!strncmp(a, "slots=", 6)) tc.n_slots = (uint32_t)strtoul(a + 6, nullptr, 10);
-    else if (!strncmp(a, "gate_q8=", 8)) tc.gate_q8 = (uint32_t)strtoul(a + 8, nullptr, 10);
-    else if (!strncmp(a, "open=", 5)) tc.open_hits = (uint32_t)strtoul(a + 5, nullptr, 10);
-    else if (!strncmp(a, "hold=", 5)) tc.hold_blocks = (uint32_t)strtoul(a + 5, nullptr, 10);
-    else if (!strncmp(a, "alpha_q8=", 9)) tc.alpha_q8 = (uint32_t)strtoul(a + 9, nullptr, 10);
-    else if (!strncmp(a, "bias=", 5)) tc.inc_bias = (uint32_t)strtoul(a + 5, nullptr, 0);
-    else if (!strncmp(a, "measure=", 8)) measurePath = a + 8;
-    else if (!strncmp(a, "margin=", 7)) { mc.margin = (uint32_t)strtoul(a + 7, nullptr, 10); marginGiven = true; }
-    else if (!strncmp(a, "beta_q16=", 9)) mc.obw_tail_q16 = (uint32_t)strtoul(a + 9, nullptr, 10);
-    else if (!strncmp(a, "carrier=", 8)) mc.carrier_half = (uint32_t)strtoul(a + 8, nullptr, 10);
-    else if (!strncmp(a, "minsum=", 7)) mc.min_sum = (uint32_t)strtoul(a + 7, nullptr, 10);
-    else if (!strncmp(a, "carrier_q8=", 11)) mc.carrier_min_q8 = (uint32_t)strtoul(a + 11, nullptr, 10);
-    else if (!strncmp(a, "wide=", 5)) { mc.wide_bins = (uint32_t)strtoul(a + 5, nullptr, 10); wideGiven = true; }
-    else if (!strncmp(a, "events=", 7)) eventsPath = a + 7;
-    else if (!strncmp(a, "minactive=", 10)) lc.min_active = (uint32_t)strtoul(a + 10, nullptr, 10);
-    else if (!strncmp(a, "votemin=", 8)) lc.vote_min = (uint32_t)strtoul(a + 8, nullptr, 10);
-    else if (!strncmp(a, "maxevents=", 10)) lc.max_events = (uint32_t)strtoul(a + 10, nullptr, 10);
-    else if (!strncmp(a, "edges=", 6)) {
-      edgesGiven = sscanf(a + 6, "%u,%u,%u", &tc.class_edge[0], &tc.class_edge[1], &tc.class_edge[2]) == 3;
-      if (!edgesGiven) {
-        fprintf(stderr, "iqdemod_spectrum: edges= takes three widths in bins, a,b,c\n");
-        return 1;
-      }
-    }
-    else {
-      fprintf(stderr, "iqdemod_spectrum: unknown argument %s\n", a);
-      return 1;
-    }
-  }
-  const bool u8 = format == "u8";
-  if (in.empty() || out.empty() || bins == 0 || frames == 0 || frames > (1u << 24) || !(rate > 0.0) || (!u8 && format != "s8")) {
-    fprintf(stderr, "usage: iqdemod_spectrum in=cap.iq rate=2048000 bins=1024 frames=250 format=u8|s8 [window=w.txt] "
-                    "out=power.u32 [log=spectrum.txt] [detect=runs.txt [rank=] [ratio_q8=] [guard=] [bridge=] [minwidth=] [maxdet=] "
-                    "[track=tracks.txt [slots=] [gate_q8=] [open=] [hold=] [alpha_q8=] [bias=] [edges=a,b,c] "
-                    "[measure=meas.txt [margin=] [beta_q16=] [carrier=] [minsum=] [carrier_q8=] [wide=] "
-                    "[events=events.txt [minactive=] [votemin=] [maxevents=]]]]]\n");
-    return 1;
-  }
-  const bool detect = !detectPath.empty(), track = !trackPath.empty(), measure = !measurePath.empty(), events = !eventsPath.empty();
-  if (events && !(track && measure)) {
-    fprintf(stderr, "iqdemod_spectrum: events= needs track= and measure=\n");
-    return 1;
-  }
-  if (measure && !track) {
-    fprintf(stderr, "iqdemod_spectrum: measure= needs track=\n");
-    return 1;
-  }
-  if (track && !detect) {
-    fprintf(stderr, "iqdemod_spectrum: track= needs detect=\n");
-    return 1;
-  }
-  if (detect && (rate != floor(rate) || rate > 4294967295.0)) {
-    fprintf(stderr, "iqdemod_spectrum: detect= needs rate as a whole number of Hz below 2^32\n");
+  Options o;
+  BandArgs &band = o.band;
+  std::vector<Row> keys = {text("in=", o.in), text("out=", o.out), text("log=", o.log), text("window=", o.window), text("format=", o.format),
+                           real("rate=", o.rate), u32("bins=", o.bins), u32("frames=", o.frames), text("detect=", o.detect),
+                           text("track=", o.track), text("measure=", o.measure), text("events=", o.events)};
+  band.rows(keys, TOOL);
+  band.logRows(keys);
+  if (!parse(argc, argv, keys, TOOL)) return 1;
+  if (const char *why = refusal(o)) {
+    fputs(why, stderr);
     return 1;
   }
   std::vector<int16_t> window;
-  if (!windowPath.empty() && (!readWindow(windowPath, window) || window.size() != bins)) {
-    fprintf(stderr, "iqdemod_spectrum: %s does not hold %u int16 values\n", windowPath.c_str(), bins);
+  const auto int16 = [](const char *tok, int16_t &x) {
+    char *end = nullptr;
+    const long v = strtol(tok, &end, 10);
+    x = (int16_t)v;
+    return *end == 0 && v >= -32768 && v <= 32767;
+  };
+  if (!o.window.empty() && (!readNumbers(o.window, window, int16) || window.size() != o.bins)) {
+    fprintf(stderr, "iqdemod_spectrum: %s does not hold %u int16 values\n", o.window.c_str(), o.bins);
     return 1;
   }
-  FILE *fin = fopen(in.c_str(), "rb");
-  FILE *fout = fin ? fopen(out.c_str(), "wb") : nullptr;
-  FILE *flog = fout && !log.empty() ? fopen(log.c_str(), "w") : nullptr;
-  FILE *fdet = fout && detect ? fopen(detectPath.c_str(), "w") : nullptr;
-  FILE *ftrk = fout && track ? fopen(trackPath.c_str(), "w") : nullptr;
-  FILE *fmsr = fout && measure ? fopen(measurePath.c_str(), "w") : nullptr;
-  FILE *fevt = fout && events ? fopen(eventsPath.c_str(), "w") : nullptr;
-  if (!fin || !fout || (!log.empty() && !flog) || (detect && !fdet) || (track && !ftrk) || (measure && !fmsr) || (events && !fevt)) {
+  // the capture, the powers, and one text file per object of the chain that was asked for
+  Files files(TOOL);
+  FILE *fin = files.open(o.in, "rb", Files::Quiet);
+  FILE *fout = fin ? files.open(o.out, "wb", Files::Quiet) : nullptr;
+  bool missing = !fout;
+  const auto lines = [&](const std::string &path) -> FILE * {
+    FILE *f = fout && !path.empty() ? files.open(path, "w", Files::Quiet) : nullptr;
+    missing = missing || (!path.empty() && !f);
+    return f;
+  };
+  FILE *flog = lines(o.log), *fdet = lines(o.detect), *ftrk = lines(o.track), *fmsr = lines(o.measure), *fevt = lines(o.events);
+  if (missing) {
     fprintf(stderr, "iqdemod_spectrum: cannot open the files\n");
     return 1;
   }
 
-  iqd_config cfg{};
-  cfg.abi_version = IQD_ABI_VERSION;
-  cfg.n_channels = 1;
-  cfg.device = -1;
-  iqd_t *e = nullptr;
-  int rc = iqd_create(&cfg, &e);
+  Engine e;
+  int rc = createEngine(e, 1);
   if (rc != IQD_OK) {
     fprintf(stderr, "iqdemod_spectrum: iqd_create: %s\n", iqd_strerror(rc));
     return 1;
   }
+  const uint32_t bins = o.bins, frames = o.frames;
+  const int depth = o.depth();
+  const bool detect = depth >= BandChain::DETECT;
   iqd_spectrum_config sc{};
   sc.n_sources = 1;
   sc.n_bins = bins;
   sc.window = window.empty() ? nullptr : window.data();
-  sc.sample_format = u8 ? IQD_WIDE_U8 : IQD_WIDE_S8;
-  iqd_spectrum_t *s = nullptr;
-  rc = iqd_spectrum_create(e, &sc, &s);
-  uint32_t pfs = 1;
-  if (rc == IQD_OK) rc = iqd_spectrum_full_scale(sc.window, bins, &pfs);
-  if (rc != IQD_OK) {
-    fprintf(stderr, "iqdemod_spectrum: iqd_spectrum_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
-    iqd_destroy(e);
-    return 1;
-  }
-
-  iqd_detect_t *d = nullptr;
-  if (detect) {
-    dc.n_bins = bins;
-    if (!rankGiven) dc.floor_rank = bins / 2;
-    rc = iqd_detect_create(e, &dc, &d);
-    if (rc != IQD_OK) {
-      fprintf(stderr, "iqdemod_spectrum: iqd_detect_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
-      iqd_spectrum_destroy(s);
-      iqd_destroy(e);
-      return 1;
-    }
-  }
-
-  iqd_track_t *t = nullptr;
-  if (track) {
-    tc.n_bins = bins;
-    tc.max_detections = dc.max_detections;
-    if (!edgesGiven) {
-      tc.class_edge[0] = bins / 64 + 1;
-      tc.class_edge[1] = bins / 16;
-      tc.class_edge[2] = bins / 4;
-    }
-    rc = iqd_track_create(e, &tc, &t);
-    if (rc != IQD_OK) {
-      fprintf(stderr, "iqdemod_spectrum: iqd_track_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
-      iqd_detect_destroy(d);
-      iqd_spectrum_destroy(s);
-      iqd_destroy(e);
-      return 1;
-    }
-  }
-
-  iqd_measure_t *ms = nullptr;
-  if (measure) {
-    mc.n_bins = bins;
-    mc.n_slots = tc.n_slots;
-    mc.dc_guard = dc.dc_guard;
-    if (!marginGiven) mc.margin = bins / 256 ? bins / 256 : 1;
-    if (!wideGiven) mc.wide_bins = bins / 32;
-    rc = iqd_measure_create(e, &mc, &ms);
-    if (rc != IQD_OK) {
-      fprintf(stderr, "iqdemod_spectrum: iqd_measure_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
-      iqd_track_destroy(t);
-      iqd_detect_destroy(d);
-      iqd_spectrum_destroy(s);
-      iqd_destroy(e);
-      return 1;
-    }
-  }
-
-  iqd_tracklog_t *tl = nullptr;
-  if (events) {
-    lc.n_slots = tc.n_slots;
-    rc = iqd_tracklog_create(e, &lc, &tl);
-    if (rc != IQD_OK) {
-      fprintf(stderr, "iqdemod_spectrum: iqd_tracklog_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
-      iqd_measure_destroy(ms);
-      iqd_track_destroy(t);
-      iqd_detect_destroy(d);
-      iqd_spectrum_destroy(s);
-      iqd_destroy(e);
-      return 1;
-    }
-  }
-  // one line of events=: an event, or a track still live at the end of the input
-  auto writeEvent = [&](uint32_t slot, const iqd_track_summary &r, bool open) {
-    const double blockSeconds = (double)bins * frames / rate;
-    int64_t cen = 0, lo = 0, hi = 0;
-    uint32_t mean = 0;
-    if (iqd_tracklog_mean_centre(r.sum_centre_q8, r.n_active, &mean) == IQD_OK) iqd_detect_offset_hz(bins, (uint32_t)rate, mean, &cen);
-    if (r.n_measured) {
-      iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.obw_lo_min + 128u, &lo);
-      iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.obw_hi_max + 128u, &hi);
-    }
-    fprintf(fevt, "%u %u %llu %u %.6f %.6f %lld %lld %lld %u %u %u %u %u %llu %u%s\n", r.track_id, slot, (unsigned long long)r.first_block,
-            r.n_blocks, (double)r.first_block * blockSeconds, (double)r.n_blocks * blockSeconds, (long long)cen, (long long)lo, (long long)hi,
-            r.mode_hint, r.votes[0], r.votes[1], r.votes[2], r.n_measured,
-            (unsigned long long)(r.n_measured ? r.sum_excess / r.n_measured : 0), r.flags, open ? " open" : "");
-  };
-
+  sc.sample_format = o.format == "u8" ? IQD_WIDE_U8 : IQD_WIDE_S8;
+  band.derive(bins, band.tc.n_slots);
+  BandChain chain;
+  const char *call = "";
+  Scale scale{bins, frames, o.rate, 1};
+  rc = chain.create(e, sc, band, BandChain::SPECTRUM, &call);
+  if (rc == IQD_OK) rc = iqd_spectrum_full_scale(sc.window, bins, &scale.pfs);
+  if (rc == IQD_OK) rc = chain.create(e, sc, band, depth, &call);
   // whole blocks, up to about 16 MiB of capture per call
   const size_t blockBytes = (size_t)2 * bins * frames;
   const size_t perCall = blockBytes >= (16u << 20) ? 1 : (16u << 20) / blockBytes;
-  std::vector<uint8_t> buf(perCall * blockBytes);
-  std::vector<uint32_t> power(perCall * bins);
-  int status = 0;
-  uint64_t block = 0, pastMax = 0;
-  size_t dropped = 0;
-  // detect=: the capture, the power rows and the detector's two arrays stay on the device from one call to the next
-  std::vector<iqd_detect_row> rows(detect ? perCall : 0);
-  std::vector<iqd_detection> dets(detect ? perCall * dc.max_detections : 0);
-  std::vector<iqd_track_slot> slots(track ? perCall * tc.n_slots : 0);
-  std::vector<iqd_track_block> tblocks(track ? perCall : 0);
-  std::vector<iqd_track_measure> meas(measure ? perCall * tc.n_slots : 0);
-  std::vector<iqd_track_summary> evts(events ? lc.max_events : 0);
-  // an event record does not say which slot its track sat in: the tool keeps the id every slot of the table showed last
-  // (0: none, or closed) and names the slot when the table shows that id ending
-  std::vector<uint32_t> slotId(track ? tc.n_slots : 0, 0);
-  uint64_t unplaced = 0, eventsPast = 0;
-  void *wideDev = nullptr, *powerDev = nullptr, *rowsDev = nullptr, *detDev = nullptr, *slotsDev = nullptr, *tblocksDev = nullptr;
-  void *measDev = nullptr, *summaryDev = nullptr, *eventsDev = nullptr, *countsDev = nullptr;
-  if (detect) {
-    rc = iqd_dev_alloc(e, buf.size(), &wideDev);
-    if (rc == IQD_OK) rc = iqd_dev_alloc(e, power.size() * sizeof(uint32_t), &powerDev);
-    if (rc == IQD_OK) rc = iqd_dev_alloc(e, rows.size() * sizeof(iqd_detect_row), &rowsDev);
-    if (rc == IQD_OK) rc = iqd_dev_alloc(e, dets.size() * sizeof(iqd_detection), &detDev);
-    if (rc == IQD_OK && track) rc = iqd_dev_alloc(e, slots.size() * sizeof(iqd_track_slot), &slotsDev);
-    if (rc == IQD_OK && track) rc = iqd_dev_alloc(e, tblocks.size() * sizeof(iqd_track_block), &tblocksDev);
-    if (rc == IQD_OK && measure) rc = iqd_dev_alloc(e, meas.size() * sizeof(iqd_track_measure), &measDev);
-    if (rc == IQD_OK && events) rc = iqd_dev_alloc(e, meas.size() * sizeof(iqd_track_summary), &summaryDev);
-    if (rc == IQD_OK && events) rc = iqd_dev_alloc(e, evts.size() * sizeof(iqd_track_summary), &eventsDev);
-    if (rc == IQD_OK && events) rc = iqd_dev_alloc(e, sizeof(iqd_tracklog_counts), &countsDev);
-    if (rc != IQD_OK) {
-      fprintf(stderr, "iqdemod_spectrum: iqd_dev_alloc: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
-      iqd_tracklog_destroy(tl);
-      iqd_measure_destroy(ms);
-      iqd_track_destroy(t);
-      iqd_detect_destroy(d);
-      iqd_spectrum_destroy(s);
-      iqd_destroy(e);
-      return 1;
-    }
+  // detect=: the capture, the power rows and the chain's arrays stay on the device from one call to the next
+  if (rc == IQD_OK && detect) {
+    call = "iqd_dev_alloc";
+    rc = chain.alloc(band, perCall, frames);
   }
+  if (rc != IQD_OK) {
+    fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", call, iqd_strerror(rc), iqd_last_error(e));
+    return 1;
+  }
+  const uint32_t S = band.tc.n_slots;
+  std::vector<uint8_t> buf(perCall * blockBytes);
+  Results r;
+  r.power.resize(perCall * bins);
+  r.rows.resize(detect ? perCall : 0);
+  r.dets.resize(detect ? perCall * band.dc.max_detections : 0);
+  r.slots.resize(ftrk ? perCall * S : 0);
+  r.tblocks.resize(ftrk ? perCall : 0);
+  r.meas.resize(fmsr ? perCall * S : 0);
+  r.evts.resize(fevt ? band.lc.max_events : 0);
+  r.slotId.assign(ftrk ? S : 0, 0);
+  static const char *const what[] = {"", "iqd_spectrum_run", "spectrum and detector", "spectrum, detector and tracker", "spectrum, detector, tracker and measurements",
+                                     "spectrum, detector, tracker, measurements and track log"};
+  int status = 0;
+  size_t dropped = 0;
   for (;;) {
     const size_t got = fread(buf.data(), 1, buf.size(), fin);
     const size_t nb = got / blockBytes;
-    iqd_tracklog_counts evtCounts{};
     dropped = got - nb * blockBytes;
     if (nb) {
-      if (!detect) {
-        rc = iqd_spectrum_run(s, buf.data(), nb * blockBytes, frames, power.data());
-      } else {
-        // spectrum and detector queued back to back on the engine's stream; the host sees the results after both
-        rc = iqd_dev_upload(e, wideDev, buf.data(), nb * blockBytes);
-        if (rc == IQD_OK) rc = iqd_spectrum_run_device(s, wideDev, nb * blockBytes, frames, (uint32_t *)powerDev);
-        if (rc == IQD_OK) rc = iqd_detect_run_device(d, (const uint32_t *)powerDev, nb, (iqd_detect_row *)rowsDev, (iqd_detection *)detDev);
-        if (rc == IQD_OK && track)
-          rc = iqd_track_run_device(t, (const iqd_detect_row *)rowsDev, (const iqd_detection *)detDev, nb, (iqd_track_slot *)slotsDev,
-                                    (iqd_track_block *)tblocksDev);
-        if (rc == IQD_OK && measure)
-          rc = iqd_measure_run_device(ms, (const uint32_t *)powerDev, (const iqd_detect_row *)rowsDev, (const iqd_track_slot *)slotsDev, nb,
-                                      (iqd_track_measure *)measDev);
-        if (rc == IQD_OK && events)
-          rc = iqd_tracklog_run_device(tl, (const iqd_track_slot *)slotsDev, (const iqd_track_measure *)measDev, nb,
-                                       (iqd_track_summary *)summaryDev, (iqd_track_summary *)eventsDev, (iqd_tracklog_counts *)countsDev);
-        if (rc == IQD_OK) rc = iqd_dev_download(e, power.data(), powerDev, nb * bins * sizeof(uint32_t));
-        if (rc == IQD_OK) rc = iqd_dev_download(e, rows.data(), rowsDev, nb * sizeof(iqd_detect_row));
-        if (rc == IQD_OK) rc = iqd_dev_download(e, dets.data(), detDev, nb * dc.max_detections * sizeof(iqd_detection));
-        if (rc == IQD_OK && track) rc = iqd_dev_download(e, slots.data(), slotsDev, nb * tc.n_slots * sizeof(iqd_track_slot));
-        if (rc == IQD_OK && track) rc = iqd_dev_download(e, tblocks.data(), tblocksDev, nb * sizeof(iqd_track_block));
-        if (rc == IQD_OK && measure) rc = iqd_dev_download(e, meas.data(), measDev, nb * tc.n_slots * sizeof(iqd_track_measure));
-        if (rc == IQD_OK && events) rc = iqd_dev_download(e, &evtCounts, countsDev, sizeof(evtCounts));
-        if (rc == IQD_OK && events && evtCounts.n_stored)
-          rc = iqd_dev_download(e, evts.data(), eventsDev, (size_t)evtCounts.n_stored * sizeof(iqd_track_summary));
-      }
+      r.counts = iqd_tracklog_counts{};
+      if (!detect) rc = iqd_spectrum_run(chain.spectrum, buf.data(), nb * blockBytes, frames, r.power.data());
+      else rc = chain.queue(buf.data(), (uint32_t)nb, frames);   // the host sees the results after the whole chain
+      if (rc == IQD_OK && detect) rc = download(chain, band, nb, r);
       if (rc != IQD_OK) {
-        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", events ? "spectrum, detector, tracker, measurements and track log" : measure ? "spectrum, detector, tracker and measurements" : track ? "spectrum, detector and tracker" : detect ? "spectrum and detector" : "iqd_spectrum_run", iqd_strerror(rc), iqd_last_error(e));
+        fprintf(stderr, "iqdemod_spectrum: %s: %s: %s\n", what[depth], iqd_strerror(rc), iqd_last_error(e));
         status = 3;
         break;
       }
-      if (fwrite(power.data(), sizeof(uint32_t), nb * bins, fout) != nb * bins) {
+      if (fwrite(r.power.data(), sizeof(uint32_t), nb * bins, fout) != nb * bins) {
         fprintf(stderr, "iqdemod_spectrum: write failed\n");
         status = 1;
         break;
       }
-      for (size_t b = 0; flog && b < nb; b++)
-        for (uint32_t k = 0; k < bins; k++) {
-          const uint32_t p = power[b * bins + k];
-          fprintf(flog, "%llu %.3f %u %.2f\n", (unsigned long long)(block + b), ((double)k - bins / 2) * rate / bins, p,
-                  10.0 * log10((double)(p ? p : 1) / (double)(pfs ? pfs : 1)));
-        }
-      for (size_t b = 0; detect && b < nb; b++) {
-        const uint32_t found = rows[b].n_found, shown = found < dc.max_detections ? found : dc.max_detections;
-        pastMax += found - shown;
-        for (uint32_t i = 0; i < shown; i++) {
-          const iqd_detection &r = dets[b * dc.max_detections + i];
-          int64_t hz = 0;
-          iqd_detect_offset_hz(bins, (uint32_t)rate, r.centroid_q8, &hz);
-          fprintf(fdet, "%llu %.3f %.3f %lld %.2f %llu\n", (unsigned long long)(block + b), ((double)r.first_bin - bins / 2) * rate / bins,
-                  ((double)r.last_bin - bins / 2) * rate / bins, (long long)hz,
-                  10.0 * log10((double)(r.peak_power ? r.peak_power : 1) / (double)(pfs ? pfs : 1)), (unsigned long long)r.sum_power);
-        }
-      }
-      for (size_t b = 0; track && b < nb; b++) {
-        unplaced += tblocks[b].n_unplaced;
-        for (uint32_t k = 0; k < tc.n_slots; k++) {
-          const iqd_track_slot &r = slots[b * tc.n_slots + k];
-          if (r.track_id == 0) continue;
-          int64_t hz = 0;
-          iqd_detect_offset_hz(bins, (uint32_t)rate, r.centre_q8, &hz);
-          fprintf(ftrk, "%llu %u %u %u %u %lld 0x%08x %.3f %.3f %u\n", (unsigned long long)(block + b), k, r.track_id, r.state, r.flags,
-                  (long long)hz, r.phase_inc, ((double)r.first_bin - bins / 2) * rate / bins, ((double)r.last_bin - bins / 2) * rate / bins,
-                  r.width_class);
-        }
-      }
-      for (size_t b = 0; measure && b < nb; b++)
-        for (uint32_t k = 0; k < tc.n_slots; k++) {
-          const iqd_track_measure &r = meas[b * tc.n_slots + k];
-          if (r.track_id == 0) continue;
-          int64_t lo = 0, hi = 0, peak = 0, cen = 0;
-          iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.obw_lo + 128u, &lo);
-          iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.obw_hi + 128u, &hi);
-          iqd_detect_offset_hz(bins, (uint32_t)rate, 256u * r.peak_bin + 128u, &peak);
-          iqd_detect_offset_hz(bins, (uint32_t)rate, r.centroid_q8, &cen);
-          fprintf(fmsr, "%llu %u %u %lld %lld %lld %lld %u %llu %u %u\n", (unsigned long long)(block + b), k, r.track_id, (long long)lo,
-                  (long long)hi, (long long)peak, (long long)cen, r.carrier_q8, (unsigned long long)r.sum_excess, r.flags, r.hint);
-        }
-      if (events) {
-        // events come in block order and within a block in slot order, and so do the table's endings: walk both together
-        // (an ending with fewer than minactive active blocks is no event and is passed over; the tracker's ids are unique)
-        uint32_t next = 0;
-        for (size_t b = 0; b < nb; b++)
-          for (uint32_t k = 0; k < tc.n_slots; k++) {
-            const iqd_track_slot &r = slots[b * tc.n_slots + k];
-            const bool ends = slotId[k] != 0 && (r.track_id != slotId[k] || r.state == 0);
-            if (ends && next < evtCounts.n_stored && evts[next].track_id == slotId[k]) writeEvent(k, evts[next++], false);
-            slotId[k] = r.state == 0 ? 0 : r.track_id;
-          }
-        eventsPast += evtCounts.n_events - evtCounts.n_stored;
-      }
-      block += nb;
+      writeCall(scale, band, nb, r, flog, fdet, ftrk, fmsr, fevt);
+      r.block += nb;
     }
     if (got < buf.size()) break;
   }
-  if (events && status == 0) {
+  if (fevt && status == 0) {
     // the tracks still live when the input ended
-    std::vector<iqd_track_summary> live(tc.n_slots);
+    std::vector<iqd_track_summary> live(S);
     uint64_t g = 0;
-    rc = iqd_tracklog_get_state(tl, 0, live.data(), &g);
+    rc = iqd_tracklog_get_state(chain.tracklog, 0, live.data(), &g);
     if (rc != IQD_OK) {
       fprintf(stderr, "iqdemod_spectrum: iqd_tracklog_get_state: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
       status = 3;
     }
-    for (uint32_t k = 0; rc == IQD_OK && k < tc.n_slots; k++)
-      if (live[k].track_id != 0) writeEvent(k, live[k], true);
+    for (uint32_t k = 0; rc == IQD_OK && k < S; k++)
+      if (live[k].track_id != 0) writeEvent(fevt, scale, k, live[k], true);
   }
   if (dropped) fprintf(stderr, "iqdemod_spectrum: %zu bytes after the last whole block dropped\n", dropped);
-  if (pastMax) fprintf(stderr, "iqdemod_spectrum: %llu runs past maxdet not written\n", (unsigned long long)pastMax);
-  if (eventsPast) fprintf(stderr, "iqdemod_spectrum: %llu events past maxevents in their call not written\n", (unsigned long long)eventsPast);
-  if (unplaced) fprintf(stderr, "iqdemod_spectrum: %llu detections found no free slot\n", (unsigned long long)unplaced);
-  for (void *p : {wideDev, powerDev, rowsDev, detDev, slotsDev, tblocksDev, measDev, summaryDev, eventsDev, countsDev})
-    if (p) iqd_dev_free(e, p);
-  iqd_tracklog_destroy(tl);
-  iqd_measure_destroy(ms);
-  iqd_track_destroy(t);
-  iqd_detect_destroy(d);
-  iqd_spectrum_destroy(s);
-  iqd_destroy(e);
-  fclose(fin);
-  if (fclose(fout) != 0) status = status ? status : 1;
-  if (flog && fclose(flog) != 0) status = status ? status : 1;
-  if (fdet && fclose(fdet) != 0) status = status ? status : 1;
-  if (ftrk && fclose(ftrk) != 0) status = status ? status : 1;
-  if (fmsr && fclose(fmsr) != 0) status = status ? status : 1;
-  if (fevt && fclose(fevt) != 0) status = status ? status : 1;
+  if (r.pastMax) fprintf(stderr, "iqdemod_spectrum: %llu runs past maxdet not written\n", (unsigned long long)r.pastMax);
+  if (r.eventsPast) fprintf(stderr, "iqdemod_spectrum: %llu events past maxevents in their call not written\n", (unsigned long long)r.eventsPast);
+  if (r.unplaced) fprintf(stderr, "iqdemod_spectrum: %llu detections found no free slot\n", (unsigned long long)r.unplaced);
+  if (!files.close() && status == 0) status = 1;
   return status;
 }
