@@ -119,184 +119,154 @@ class IqdError(RuntimeError):
         self.status = status
 
 
-EXPORTS = [
-    "iqd_abi_version", "iqd_strerror", "iqd_last_error", "iqd_create", "iqd_destroy", "iqd_set_mode",
-    "iqd_set_gain", "iqd_set_squelch", "iqd_set_rx_gain_db", "iqd_set_rotation", "iqd_reset", "iqd_reset_demod",
-    "iqd_accept_iq", "iqd_accept_iq_device", "iqd_synchronize", "iqd_get_stats", "iqd_set_profiling",
-    "iqd_get_channel_mode", "iqd_get_channel_gain", "iqd_dev_alloc", "iqd_dev_free", "iqd_dev_upload",
-    "iqd_dev_download", "iqd_dev_tile", "iqd_stream", "iqd_debug_stamps", "iqd_debug_stamps_ext", "iqd_host_alloc", "iqd_host_free",
-    "iqd_get_rx_gain_db", "iqd_agc_set_type", "iqd_agc_set_deadband", "iqd_agc_set_blanking_limit",
-    "iqd_agc_set_operating_point", "iqd_agc_set_filter_coefficient", "iqd_agc_enable", "iqd_agc_get_state",
-    "iqd_set_gain_trace", "iqd_get_gain_trace", "iqd_scanner_set_parameters", "iqd_scanner_start",
-    "iqd_scanner_get", "iqd_get_frequency_trace", "iqd_front_end", "iqd_front_end_device", "iqd_convert_fs_over_4",
-    "iqd_resampler_create", "iqd_resampler_destroy", "iqd_resampler_reset", "iqd_resampler_out_count",
-    "iqd_resampler_run", "iqd_resampler_run_device", "iqd_gather_unique_id", "iqd_gather_create", "iqd_gather_pcm", "iqd_gather_destroy",
-    "iqd_demod_accept", "iqd_demod_set_sideband", "iqd_get_device", "iqd_gather_info", "iqd_device_count",
-    "iqd_channelizer_create", "iqd_channelizer_destroy", "iqd_channelizer_reset", "iqd_channelizer_set_channels",
-    "iqd_channelizer_run_device", "iqd_channelizer_run", "iqd_accept_wideband", "iqd_channelizer_phasor_table",
-    "iqd_channelizer_default_taps", "iqd_channelizer_set_source_frequency", "iqd_channelizer_follow_scanner",
-    "iqd_channelizer_tuning", "iqd_accept_wideband_device", "iqd_channelizer_default_taps_q",
-    "iqd_channelizer_set_survey", "iqd_channelizer_survey_device", "iqd_channelizer_survey", "iqd_magnitude_dbfs",
-    "iqd_channelizer_window_outputs", "iqd_channelizer_follow_gain",
-    "iqd_filter_create", "iqd_filter_destroy", "iqd_filter_reset", "iqd_filter_out_count", "iqd_filter_run",
-    "iqd_filter_run_device", "iqd_filter_tile_samples", "iqd_filter_clamp_free_taps",
-    "iqd_spectrum_create", "iqd_spectrum_destroy", "iqd_spectrum_run_device", "iqd_spectrum_run",
-    "iqd_spectrum_default_window", "iqd_spectrum_full_scale",
-    "iqd_detect_create", "iqd_detect_destroy", "iqd_detect_run_device", "iqd_detect_run", "iqd_detect_offset_hz",
-    "iqd_track_create", "iqd_track_destroy", "iqd_track_reset", "iqd_track_run_device", "iqd_track_run", "iqd_track_get_state",
-    "iqd_track_phase_inc",
-    "iqd_measure_create", "iqd_measure_destroy", "iqd_measure_run_device", "iqd_measure_run",
-    "iqd_tracklog_create", "iqd_tracklog_destroy", "iqd_tracklog_reset", "iqd_tracklog_run_device", "iqd_tracklog_run",
-    "iqd_tracklog_get_state", "iqd_tracklog_mean_centre",
-    "iqd_channelizer_set_track_table", "iqd_channelizer_follow_tracks", "iqd_channelizer_track_window_outputs",
-]
+_vp, _u32, _u64, _sz, _int, _P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_size_t, C.c_int, C.POINTER
+
+# Every function of include/iqdemod.h, in its order: name -> (what it returns, what it takes).  Handles, device and host
+# buffers are c_void_p; POINTER(...) is where callers pass byref().  tests/test_abi_prototypes.py holds this against the header.
+PROTOTYPES = {
+    "iqd_create": (_int, (_P(Config), _P(_vp))),
+    "iqd_destroy": (None, (_vp,)),
+    "iqd_set_mode": (_int, (_vp, _u32, _u32, _int)),
+    "iqd_set_gain": (_int, (_vp, _u32, _u32, _int, C.c_float)),
+    "iqd_set_squelch": (_int, (_vp, _u32, _u32, C.c_int32)),
+    "iqd_set_rx_gain_db": (_int, (_vp, _u32, _u32, _u32)),
+    "iqd_get_rx_gain_db": (_int, (_vp, _u32, _P(_u32))),
+    "iqd_agc_set_type": (_int, (_vp, _u32, _u32, _u32)),
+    "iqd_agc_set_deadband": (_int, (_vp, _u32, _u32, _u32)),
+    "iqd_agc_set_blanking_limit": (_int, (_vp, _u32, _u32, _u32)),
+    "iqd_agc_set_operating_point": (_int, (_vp, _u32, _u32, C.c_int32)),
+    "iqd_agc_set_filter_coefficient": (_int, (_vp, _u32, _u32, C.c_float)),
+    "iqd_agc_enable": (_int, (_vp, _u32, _u32, _int)),
+    "iqd_agc_get_state": (_int, (_vp, _u32, _P(AgcState))),
+    "iqd_scanner_set_parameters": (_int, (_vp, _u32, _u32, _u64, _u64, _u64)),
+    "iqd_scanner_start": (_int, (_vp, _u32, _u32, _int)),
+    "iqd_scanner_get": (_int, (_vp, _u32, _P(_u64), _P(_u64), _P(_int))),
+    "iqd_set_gain_trace": (_int, (_vp, _int)),
+    "iqd_get_gain_trace": (_int, (_vp, _u32, _u32, _vp, _sz)),
+    "iqd_get_frequency_trace": (_int, (_vp, _u32, _u32, _vp, _sz)),
+    "iqd_set_rotation": (_int, (_vp, _u32, _u32, _int)),
+    "iqd_reset": (_int, (_vp, _u32, _u32)),
+    "iqd_reset_demod": (_int, (_vp, _u32, _u32, _int)),
+    "iqd_accept_iq": (_int, (_vp, _u32, _u32, _vp, _sz, _vp, _vp, _vp, _vp)),
+    "iqd_accept_iq_device": (_int, (_vp, _u32, _u32, _vp, _sz, _vp, _vp, _vp, _vp)),
+    "iqd_synchronize": (_int, (_vp,)),
+    "iqd_demod_accept": (_int, (_vp, _u32, _u32, _int, _vp, _sz, _vp)),
+    "iqd_demod_set_sideband": (_int, (_vp, _u32, _u32, _int)),
+    "iqd_front_end": (_int, (_vp, _u32, _u32, _vp, _sz, _vp)),
+    "iqd_front_end_device": (_int, (_vp, _u32, _u32, _vp, _sz, _vp)),
+    "iqd_convert_fs_over_4": (_int, (_vp, _int, _vp, _sz)),
+    "iqd_get_stats": (_int, (_vp, _P(Stats))),
+    "iqd_set_profiling": (_int, (_vp, _int)),
+    "iqd_get_channel_mode": (_int, (_vp, _u32, _P(_int))),
+    "iqd_get_channel_gain": (_int, (_vp, _u32, _int, _P(C.c_float))),
+    "iqd_last_error": (C.c_char_p, (_vp,)),
+    "iqd_strerror": (C.c_char_p, (_int,)),
+    "iqd_abi_version": (_u32, ()),
+    "iqd_resampler_create": (_int, (_vp, _int, _vp, _u32, _u32, _u32, _P(_vp))),
+    "iqd_resampler_destroy": (None, (_vp,)),
+    "iqd_resampler_reset": (_int, (_vp,)),
+    "iqd_resampler_out_count": (_sz, (_vp, _sz)),
+    "iqd_resampler_run": (_int, (_vp, _vp, _sz, _vp)),
+    "iqd_resampler_run_device": (_int, (_vp, _vp, _sz, _vp)),
+    "iqd_filter_create": (_int, (_vp, _int, _vp, _u32, _vp, _u32, _u32, _u32, _P(_vp))),
+    "iqd_filter_destroy": (None, (_vp,)),
+    "iqd_filter_reset": (_int, (_vp,)),
+    "iqd_filter_out_count": (_sz, (_vp, _sz)),
+    "iqd_filter_run": (_int, (_vp, _vp, _sz, _vp)),
+    "iqd_filter_run_device": (_int, (_vp, _vp, _sz, _vp)),
+    "iqd_filter_tile_samples": (_u32, (_int, _u32, _u32, _u32)),
+    "iqd_filter_clamp_free_taps": (_u32, (_vp, _u32)),
+    "iqd_channelizer_create": (_int, (_vp, _P(ChannelizerConfig), _P(_vp))),
+    "iqd_channelizer_destroy": (None, (_vp,)),
+    "iqd_channelizer_reset": (_int, (_vp,)),
+    "iqd_channelizer_set_channels": (_int, (_vp, _u32, _u32, _vp, _vp, _vp)),
+    "iqd_channelizer_run_device": (_int, (_vp, _vp, _sz, _vp)),
+    "iqd_channelizer_run": (_int, (_vp, _vp, _sz, _vp)),
+    "iqd_accept_wideband": (_int, (_vp, _vp, _u32, _vp, _sz, _vp, _vp, _vp, _vp)),
+    "iqd_channelizer_phasor_table": (_int, (_vp,)),
+    "iqd_channelizer_default_taps": (_int, (_u32, _vp, _u32)),
+    "iqd_channelizer_default_taps_q": (_int, (_u32, _u32, _vp, _u32)),
+    "iqd_channelizer_window_outputs": (_u32, (_u32, _u32, _u32)),
+    "iqd_channelizer_set_source_frequency": (_int, (_vp, _u32, _u32, _vp)),
+    "iqd_channelizer_follow_scanner": (_int, (_vp, _u32, _u32, _int)),
+    "iqd_channelizer_tuning": (_int, (_u32, _u64, _u64, _int, _P(_u32))),
+    "iqd_accept_wideband_device": (_int, (_vp, _vp, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _vp)),
+    "iqd_channelizer_follow_gain": (_int, (_vp, _u32, _u32, _int)),
+    "iqd_channelizer_set_survey": (_int, (_vp, _u32, _vp, _vp)),
+    "iqd_channelizer_survey_device": (_int, (_vp, _vp, _sz, _u32, _vp)),
+    "iqd_channelizer_survey": (_int, (_vp, _vp, _sz, _u32, _vp)),
+    "iqd_magnitude_dbfs": (C.c_int32, (_u32,)),
+    "iqd_spectrum_create": (_int, (_vp, _P(SpectrumConfig), _P(_vp))),
+    "iqd_spectrum_destroy": (None, (_vp,)),
+    "iqd_spectrum_run_device": (_int, (_vp, _vp, _sz, _u32, _vp)),
+    "iqd_spectrum_run": (_int, (_vp, _vp, _sz, _u32, _vp)),
+    "iqd_spectrum_default_window": (_int, (_u32, _vp)),
+    "iqd_spectrum_full_scale": (_int, (_vp, _u32, _P(_u32))),
+    "iqd_detect_create": (_int, (_vp, _P(DetectConfig), _P(_vp))),
+    "iqd_detect_destroy": (None, (_vp,)),
+    "iqd_detect_run_device": (_int, (_vp, _vp, _sz, _vp, _vp)),
+    "iqd_detect_run": (_int, (_vp, _vp, _sz, _vp, _vp)),
+    "iqd_detect_offset_hz": (_int, (_u32, _u32, _u32, _P(C.c_int64))),
+    "iqd_track_create": (_int, (_vp, _P(TrackConfig), _P(_vp))),
+    "iqd_track_destroy": (None, (_vp,)),
+    "iqd_track_reset": (_int, (_vp,)),
+    "iqd_track_run_device": (_int, (_vp, _vp, _vp, _sz, _vp, _vp)),
+    "iqd_track_run": (_int, (_vp, _vp, _vp, _sz, _vp, _vp)),
+    "iqd_track_get_state": (_int, (_vp, _u32, _vp)),
+    "iqd_track_phase_inc": (_int, (_u32, _u32, _u32, _P(_u32))),
+    "iqd_channelizer_set_track_table": (_int, (_vp, _P(TrackFollow))),
+    "iqd_channelizer_follow_tracks": (_int, (_vp, _u32, _u32, _vp)),
+    "iqd_channelizer_track_window_outputs": (_u32, (_u32, _u32)),
+    "iqd_measure_create": (_int, (_vp, _P(MeasureConfig), _P(_vp))),
+    "iqd_measure_destroy": (None, (_vp,)),
+    "iqd_measure_run_device": (_int, (_vp, _vp, _vp, _vp, _sz, _vp)),
+    "iqd_measure_run": (_int, (_vp, _vp, _vp, _vp, _sz, _vp)),
+    "iqd_tracklog_create": (_int, (_vp, _P(TrackLogConfig), _P(_vp))),
+    "iqd_tracklog_destroy": (None, (_vp,)),
+    "iqd_tracklog_reset": (_int, (_vp,)),
+    "iqd_tracklog_run_device": (_int, (_vp, _vp, _vp, _sz, _vp, _vp, _vp)),
+    "iqd_tracklog_run": (_int, (_vp, _vp, _vp, _sz, _vp, _vp, _vp)),
+    "iqd_tracklog_get_state": (_int, (_vp, _u32, _vp, _P(_u64))),
+    "iqd_tracklog_mean_centre": (_int, (_u64, _u32, _P(_u32))),
+    "iqd_gather_unique_id": (_int, (_vp,)),
+    "iqd_gather_create": (_int, (_vp, C.c_char_p, _u32, _u32, _u32, _P(_vp))),
+    "iqd_gather_pcm": (_int, (_vp, _vp, _P(_sz), _vp, _sz)),
+    "iqd_gather_destroy": (None, (_vp,)),
+    "iqd_gather_info": (_int, (_vp, _P(_int), _P(_int), _P(_int))),
+    "iqd_dev_alloc": (_int, (_vp, _sz, _P(_vp))),
+    "iqd_dev_free": (_int, (_vp, _vp)),
+    "iqd_dev_upload": (_int, (_vp, _vp, _vp, _sz)),
+    "iqd_dev_download": (_int, (_vp, _vp, _vp, _sz)),
+    "iqd_host_alloc": (_int, (_vp, _sz, _P(_vp))),
+    "iqd_host_free": (_int, (_vp, _vp)),
+    "iqd_dev_tile": (_int, (_vp, _vp, _sz, _sz)),
+    "iqd_stream": (_vp, (_vp,)),
+    "iqd_device_count": (_int, ()),
+    "iqd_get_device": (_int, (_vp, _P(_int))),
+    "iqd_debug_stamps": (_int, (_vp, _vp)),
+    "iqd_debug_stamps_ext": (_int, (_vp, _vp, _u32)),
+}
+EXPORTS = list(PROTOTYPES)
 
 _LIB = None
+
+
+def _bind(L):
+    """Gives every function of `L` its prototype (a library without one of them raises); returns L."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
+    return L
 
 
 def _lib():
     """Loads libiqdemod.so (raises if it has not been built — there is no fallback)."""
     global _LIB
-    if _LIB is not None:
-        return _LIB
-    if not os.path.exists(LIB):
-        raise FileNotFoundError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB)
-    L = C.CDLL(LIB)
-    vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
-    L.iqd_abi_version.restype = u32
-    L.iqd_strerror.restype = C.c_char_p
-    L.iqd_strerror.argtypes = [C.c_int]
-    L.iqd_last_error.restype = C.c_char_p
-    L.iqd_last_error.argtypes = [vp]
-    L.iqd_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    L.iqd_destroy.argtypes = [vp]
-    L.iqd_destroy.restype = None
-    L.iqd_set_mode.argtypes = [vp, u32, u32, C.c_int]
-    L.iqd_set_gain.argtypes = [vp, u32, u32, C.c_int, C.c_float]
-    L.iqd_set_squelch.argtypes = [vp, u32, u32, C.c_int32]
-    L.iqd_set_rx_gain_db.argtypes = [vp, u32, u32, u32]
-    L.iqd_set_rotation.argtypes = [vp, u32, u32, C.c_int]
-    L.iqd_reset.argtypes = [vp, u32, u32]
-    L.iqd_reset_demod.argtypes = [vp, u32, u32, C.c_int]
-    L.iqd_accept_iq.argtypes = [vp, u32, u32, vp, sz, vp, vp, vp, vp]
-    L.iqd_accept_iq_device.argtypes = [vp, u32, u32, vp, sz, vp, vp, vp, vp]
-    L.iqd_synchronize.argtypes = [vp]
-    L.iqd_demod_accept.argtypes = [vp, u32, u32, C.c_int, vp, sz, vp]
-    L.iqd_demod_set_sideband.argtypes = [vp, u32, u32, C.c_int]
-    L.iqd_front_end.argtypes = [vp, u32, u32, vp, sz, vp]
-    L.iqd_resampler_create.argtypes = [vp, C.c_int, vp, u32, u32, u32, C.POINTER(vp)]
-    L.iqd_resampler_destroy.argtypes = [vp]
-    L.iqd_resampler_destroy.restype = None
-    L.iqd_resampler_reset.argtypes = [vp]
-    L.iqd_resampler_out_count.argtypes = [vp, sz]
-    L.iqd_resampler_out_count.restype = sz
-    L.iqd_resampler_run.argtypes = [vp, vp, sz, vp]
-    L.iqd_resampler_run_device.argtypes = [vp, vp, sz, vp]
-    L.iqd_filter_create.argtypes = [vp, C.c_int, vp, u32, vp, u32, u32, u32, C.POINTER(vp)]
-    L.iqd_filter_destroy.argtypes = [vp]
-    L.iqd_filter_destroy.restype = None
-    L.iqd_filter_reset.argtypes = [vp]
-    L.iqd_filter_out_count.argtypes = [vp, sz]
-    L.iqd_filter_out_count.restype = sz
-    L.iqd_filter_run.argtypes = [vp, vp, sz, vp]
-    L.iqd_filter_run_device.argtypes = [vp, vp, sz, vp]
-    L.iqd_filter_tile_samples.argtypes = [C.c_int, u32, u32, u32]
-    L.iqd_filter_tile_samples.restype = u32
-    L.iqd_filter_clamp_free_taps.argtypes = [vp, u32]
-    L.iqd_filter_clamp_free_taps.restype = u32
-    L.iqd_front_end_device.argtypes = [vp, u32, u32, vp, sz, vp]
-    L.iqd_convert_fs_over_4.argtypes = [vp, C.c_int, vp, sz]
-    L.iqd_get_stats.argtypes = [vp, C.POINTER(Stats)]
-    L.iqd_set_profiling.argtypes = [vp, C.c_int]
-    L.iqd_get_channel_mode.argtypes = [vp, u32, C.POINTER(C.c_int)]
-    L.iqd_get_channel_gain.argtypes = [vp, u32, C.c_int, C.POINTER(C.c_float)]
-    L.iqd_dev_alloc.argtypes = [vp, sz, C.POINTER(vp)]
-    L.iqd_dev_free.argtypes = [vp, vp]
-    L.iqd_dev_upload.argtypes = [vp, vp, vp, sz]
-    L.iqd_dev_download.argtypes = [vp, vp, vp, sz]
-    L.iqd_dev_tile.argtypes = [vp, vp, sz, sz]
-    L.iqd_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
-    L.iqd_host_free.argtypes = [vp, vp]
-    L.iqd_get_rx_gain_db.argtypes = [vp, u32, C.POINTER(u32)]
-    L.iqd_agc_set_type.argtypes = [vp, u32, u32, u32]
-    L.iqd_agc_set_deadband.argtypes = [vp, u32, u32, u32]
-    L.iqd_agc_set_blanking_limit.argtypes = [vp, u32, u32, u32]
-    L.iqd_agc_set_operating_point.argtypes = [vp, u32, u32, C.c_int32]
-    L.iqd_agc_set_filter_coefficient.argtypes = [vp, u32, u32, C.c_float]
-    L.iqd_agc_enable.argtypes = [vp, u32, u32, C.c_int]
-    L.iqd_agc_get_state.argtypes = [vp, u32, C.POINTER(AgcState)]
-    L.iqd_set_gain_trace.argtypes = [vp, C.c_int]
-    L.iqd_get_gain_trace.argtypes = [vp, u32, u32, vp, sz]
-    u64 = C.c_uint64
-    L.iqd_scanner_set_parameters.argtypes = [vp, u32, u32, u64, u64, u64]
-    L.iqd_scanner_start.argtypes = [vp, u32, u32, C.c_int]
-    L.iqd_scanner_get.argtypes = [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int)]
-    L.iqd_get_frequency_trace.argtypes = [vp, u32, u32, vp, sz]
-    L.iqd_stream.argtypes = [vp]
-    L.iqd_stream.restype = vp
-    L.iqd_channelizer_create.argtypes = [vp, C.POINTER(ChannelizerConfig), C.POINTER(vp)]
-    L.iqd_channelizer_destroy.argtypes = [vp]
-    L.iqd_channelizer_destroy.restype = None
-    L.iqd_channelizer_reset.argtypes = [vp]
-    L.iqd_channelizer_set_channels.argtypes = [vp, u32, u32, vp, vp, vp]
-    L.iqd_channelizer_run_device.argtypes = [vp, vp, sz, vp]
-    L.iqd_channelizer_run.argtypes = [vp, vp, sz, vp]
-    L.iqd_accept_wideband.argtypes = [vp, vp, u32, vp, sz, vp, vp, vp, vp]
-    L.iqd_channelizer_phasor_table.argtypes = [vp]
-    L.iqd_channelizer_default_taps.argtypes = [u32, vp, u32]
-    L.iqd_channelizer_default_taps_q.argtypes = [u32, u32, vp, u32]
-    L.iqd_channelizer_set_source_frequency.argtypes = [vp, u32, u32, vp]
-    L.iqd_channelizer_follow_scanner.argtypes = [vp, u32, u32, C.c_int]
-    L.iqd_channelizer_follow_gain.argtypes = [vp, u32, u32, C.c_int]
-    L.iqd_channelizer_tuning.argtypes = [u32, u64, u64, C.c_int, C.POINTER(u32)]
-    L.iqd_accept_wideband_device.argtypes = [vp, vp, u32, vp, sz, vp, vp, vp, vp, vp]
-    L.iqd_channelizer_set_survey.argtypes = [vp, u32, vp, vp]
-    L.iqd_channelizer_survey_device.argtypes = [vp, vp, sz, u32, vp]
-    L.iqd_channelizer_survey.argtypes = [vp, vp, sz, u32, vp]
-    L.iqd_channelizer_window_outputs.argtypes = [u32, u32, u32]
-    L.iqd_channelizer_window_outputs.restype = u32
-    L.iqd_magnitude_dbfs.argtypes = [u32]
-    L.iqd_magnitude_dbfs.restype = C.c_int32
-    L.iqd_spectrum_create.argtypes = [vp, C.POINTER(SpectrumConfig), C.POINTER(vp)]
-    L.iqd_spectrum_destroy.argtypes = [vp]
-    L.iqd_spectrum_destroy.restype = None
-    L.iqd_spectrum_run_device.argtypes = [vp, vp, sz, u32, vp]
-    L.iqd_spectrum_run.argtypes = [vp, vp, sz, u32, vp]
-    L.iqd_spectrum_default_window.argtypes = [u32, vp]
-    L.iqd_spectrum_full_scale.argtypes = [vp, u32, C.POINTER(u32)]
-    L.iqd_detect_create.argtypes = [vp, C.POINTER(DetectConfig), C.POINTER(vp)]
-    L.iqd_detect_destroy.argtypes = [vp]
-    L.iqd_detect_destroy.restype = None
-    L.iqd_detect_run_device.argtypes = [vp, vp, sz, vp, vp]
-    L.iqd_detect_run.argtypes = [vp, vp, sz, vp, vp]
-    L.iqd_detect_offset_hz.argtypes = [u32, u32, u32, C.POINTER(C.c_int64)]
-    L.iqd_track_create.argtypes = [vp, C.POINTER(TrackConfig), C.POINTER(vp)]
-    L.iqd_track_destroy.argtypes = [vp]
-    L.iqd_track_destroy.restype = None
-    L.iqd_track_reset.argtypes = [vp]
-    L.iqd_track_run_device.argtypes = [vp, vp, vp, sz, vp, vp]
-    L.iqd_track_run.argtypes = [vp, vp, vp, sz, vp, vp]
-    L.iqd_track_get_state.argtypes = [vp, u32, vp]
-    L.iqd_track_phase_inc.argtypes = [u32, u32, u32, C.POINTER(u32)]
-    L.iqd_measure_create.argtypes = [vp, C.POINTER(MeasureConfig), C.POINTER(vp)]
-    L.iqd_measure_destroy.argtypes = [vp]
-    L.iqd_measure_destroy.restype = None
-    L.iqd_measure_run_device.argtypes = [vp, vp, vp, vp, sz, vp]
-    L.iqd_measure_run.argtypes = [vp, vp, vp, vp, sz, vp]
-    L.iqd_tracklog_create.argtypes = [vp, C.POINTER(TrackLogConfig), C.POINTER(vp)]
-    L.iqd_tracklog_destroy.argtypes = [vp]
-    L.iqd_tracklog_destroy.restype = None
-    L.iqd_tracklog_reset.argtypes = [vp]
-    L.iqd_tracklog_run_device.argtypes = [vp, vp, vp, sz, vp, vp, vp]
-    L.iqd_tracklog_run.argtypes = [vp, vp, vp, sz, vp, vp, vp]
-    L.iqd_tracklog_get_state.argtypes = [vp, u32, vp, C.POINTER(C.c_uint64)]
-    L.iqd_tracklog_mean_centre.argtypes = [C.c_uint64, u32, C.POINTER(u32)]
-    L.iqd_channelizer_set_track_table.argtypes = [vp, C.POINTER(TrackFollow)]
-    L.iqd_channelizer_follow_tracks.argtypes = [vp, u32, u32, vp]
-    L.iqd_channelizer_track_window_outputs.argtypes = [u32, u32]
-    L.iqd_channelizer_track_window_outputs.restype = u32
-    _LIB = L
-    return L
+    if _LIB is None:
+        if not os.path.exists(LIB):
+            raise FileNotFoundError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB)
+        _LIB = _bind(C.CDLL(LIB))
+    return _LIB
 
 
 def _np_ptr(a):
@@ -309,8 +279,33 @@ def _dev_ptr(x):
 
 
 def _ptr_or_placeholder(a):
-    """_np_ptr(a), but an empty array - its call will be refused - gets a valid pointer all the same"""
+    """_np_ptr(a), but an empty array - its call is refused or writes nothing - gets a valid pointer all the same"""
     return _np_ptr(a if a.size else np.zeros(64, np.uint8))
+
+
+def _ok(rc, detail):
+    """for calls that leave no text with an engine: a status other than IQD_OK raises with `detail`"""
+    if rc != 0:
+        raise IqdError(rc, detail)
+
+
+def _u32_config(cls, values, **arrays):
+    """cls(*values), its array fields filled entry by entry from `arrays`, every value taken modulo 2^32"""
+    cfg = cls(*[int(v) & 0xffffffff for v in values])
+    for name, vals in arrays.items():
+        field = getattr(cfg, name)
+        for i in range(len(field)):
+            field[i] = int(vals[i]) & 0xffffffff
+    return cfg
+
+
+def _u32_function(name, out, args, detail, bits=32):
+    """A host-only function of unsigned arguments (the first of `bits` bits, the others of 32) that fills `out`: an argument
+    out of range, like any refusal of the library's, is IQD_EINVAL with `detail`."""
+    args = [int(v) for v in args]
+    if not all(0 <= v < 2 ** b for v, b in zip(args, [bits, 32, 32])) or getattr(_lib(), name)(*args, C.byref(out)) != 0:
+        raise IqdError(-1, detail)
+    return out.value
 
 
 class _EngineChild:
@@ -318,13 +313,15 @@ class _EngineChild:
     first, gone by iqd_<kind>_destroy.  _h is what the raw library takes."""
     _e = _L = _h = _kind = None
 
-    def _create(self, engine, kind, cfg):
+    def _create(self, engine, kind, *args, failed=None):
+        """iqd_<kind>_create(engine, *args, &handle); `failed` is the error's text where the engine keeps none"""
         self._e, self._L, self._kind = engine, engine._L, kind
         h = C.c_void_p()
-        engine._check(getattr(self._L, "iqd_%s_create" % kind)(engine._h, C.byref(cfg), C.byref(h)))
+        rc = getattr(self._L, "iqd_%s_create" % kind)(engine._h, *args, C.byref(h))
+        if failed:
+            _ok(rc, failed)
+        engine._check(rc)
         self._h = h
-        if not hasattr(engine, "_children"):
-            engine._children = weakref.WeakSet()
         engine._children.add(self)
 
     def close(self):
@@ -340,8 +337,8 @@ class Engine:
     """N independent channels, each one reference IqDataProcessor + its four demodulators."""
 
     def __init__(self, n_channels=1, block_bytes=0, device=-1, flags=0):
+        self._h, self._children, self._pinned = C.c_void_p(), weakref.WeakSet(), {}    # (what close() needs, first)
         self._L = _lib()
-        self._h = C.c_void_p()
         cfg = Config(self._L.iqd_abi_version(), n_channels, block_bytes, device, flags)
         rc = self._L.iqd_create(C.byref(cfg), C.byref(self._h))
         if rc != 0:
@@ -351,9 +348,9 @@ class Engine:
         self.block_bytes = block_bytes or 32768
 
     def close(self):
-        for child in list(getattr(self, "_children", ())):   # channelizers go before their engine (include/iqdemod.h)
+        for child in list(self._children):   # every _EngineChild goes before its engine (include/iqdemod.h)
             child.close()
-        if getattr(self, "_h", None):
+        if self._h:
             self._L.iqd_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -365,6 +362,13 @@ class Engine:
 
     def _range(self, first, n):
         return first, (self.n_channels - first if n is None else n)
+
+    def _unless_refused(self, rc, refusals=(-6,)):
+        """True / False like the reference's setters: IQD_EALREADY (for the AGC's, IQD_EINVAL too) is their `false`"""
+        if rc in refusals:
+            return False
+        self._check(rc)
+        return True
 
     # ---- the reference's control surface -------------------------------------------------
     def set_mode(self, mode, first=0, n=None):
@@ -412,11 +416,7 @@ class Engine:
     # ---- AutomaticGainControl: True/False like the reference's setters -----------------------
     def _agc(self, fn, value, first, n):
         f, n = self._range(first, n)
-        rc = fn(self._h, f, n, value)
-        if rc in (-1, -6):   # IQD_EINVAL / IQD_EALREADY: the reference method returns false
-            return False
-        self._check(rc)
-        return True
+        return self._unless_refused(fn(self._h, f, n, value), (-1, -6))
 
     def agc_set_type(self, t, first=0, n=None):
         return self._agc(self._L.iqd_agc_set_type, int(t), first, n)
@@ -458,19 +458,11 @@ class Engine:
     # ---- FrequencyScanner -------------------------------------------------------------------
     def scanner_set_parameters(self, start_hz, end_hz, increment_hz, first=0, n=None):
         f, n = self._range(first, n)
-        rc = self._L.iqd_scanner_set_parameters(self._h, f, n, int(start_hz), int(end_hz), int(increment_hz))
-        if rc == -6:
-            return False
-        self._check(rc)
-        return True
+        return self._unless_refused(self._L.iqd_scanner_set_parameters(self._h, f, n, int(start_hz), int(end_hz), int(increment_hz)))
 
     def scanner_start(self, start=True, first=0, n=None):
         f, n = self._range(first, n)
-        rc = self._L.iqd_scanner_start(self._h, f, n, 1 if start else 0)
-        if rc == -6:
-            return False
-        self._check(rc)
-        return True
+        return self._unless_refused(self._L.iqd_scanner_start(self._h, f, n, 1 if start else 0))
 
     def scanner_tuned(self, ch=0):
         """(frequency the radio was last told to tune to, number of tuning commands)"""
@@ -571,13 +563,11 @@ class Engine:
 
     def debug_stamps_ext(self, n=64):
         out = (C.c_ulonglong * n)()
-        self._L.iqd_debug_stamps_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         self._check(self._L.iqd_debug_stamps_ext(self._h, out, n))
         return list(out)
 
     def debug_stamps(self):
         out = (C.c_ulonglong * 16)()
-        self._L.iqd_debug_stamps.argtypes = [C.c_void_p, C.c_void_p]
         self._check(self._L.iqd_debug_stamps(self._h, out))
         return list(out)
 
@@ -605,12 +595,11 @@ class Engine:
         self._check(self._L.iqd_host_alloc(self._h, n, C.byref(p)))
         buf = (C.c_uint8 * n).from_address(p.value)
         a = np.frombuffer(buf, dtype=dtype).reshape(shape)
-        self._pinned = getattr(self, "_pinned", {})
         self._pinned[a.ctypes.data] = p.value
         return a
 
     def host_free(self, a):
-        p = getattr(self, "_pinned", {}).pop(a.ctypes.data, None)
+        p = self._pinned.pop(a.ctypes.data, None)
         if p is not None:
             self._check(self._L.iqd_host_free(self._h, C.c_void_p(p)))
 
@@ -625,65 +614,38 @@ class Engine:
         self._check(self._L.iqd_dev_tile(self._h, C.c_void_p(dst), period, total))
 
 
-class Gatherer:
+class Gatherer(_EngineChild):
     """iqd_gather_*: this rank's PCM to row `rank` of a buffer on the root, over RCCL, on the engine's stream."""
 
     def __init__(self, engine, unique_id, rank, world, root=0):
-        self._e, self._L = engine, engine._L
         self.rank, self.world, self.root = rank, world, root
-        self._L.iqd_gather_create.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-        self._L.iqd_gather_pcm.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
-        self._L.iqd_gather_destroy.argtypes = [C.c_void_p]
-        self._L.iqd_gather_destroy.restype = None
-        h = C.c_void_p()
-        rc = self._L.iqd_gather_create(engine._h, bytes(unique_id), rank, world, root, C.byref(h))
-        if rc != 0:
-            raise IqdError(rc, "iqd_gather_create failed (is librccl.so there?)")
-        self._h = h
+        self._create(engine, "gather", bytes(unique_id), rank, world, root, failed="iqd_gather_create failed (is librccl.so there?)")
 
     @staticmethod
     def unique_id():
-        L = _lib()
         buf = (C.c_uint8 * 128)()
-        L.iqd_gather_unique_id.argtypes = [C.c_void_p]
-        rc = L.iqd_gather_unique_id(buf)
-        if rc != 0:
-            raise IqdError(rc, "iqd_gather_unique_id failed (is librccl.so there?)")
+        _ok(_lib().iqd_gather_unique_id(buf), "iqd_gather_unique_id failed (is librccl.so there?)")
         return bytes(buf)
 
     def gather(self, send_dev, bytes_per_rank, recv_dev, row_stride):
         arr = (C.c_size_t * self.world)(*[int(b) for b in bytes_per_rank])
-        rc = self._L.iqd_gather_pcm(self._h, C.c_void_p(send_dev), arr, _dev_ptr(recv_dev), int(row_stride))
-        if rc != 0:
-            raise IqdError(rc, "iqd_gather_pcm failed")
+        _ok(self._L.iqd_gather_pcm(self._h, C.c_void_p(send_dev), arr, _dev_ptr(recv_dev), int(row_stride)), "iqd_gather_pcm failed")
 
     def info(self):
         """{'version': RCCL's version code, 'ranks': what ncclCommCount says, 'library_reused': the process's own copy}"""
         v, n, r = C.c_int(), C.c_int(), C.c_int()
-        self._L.iqd_gather_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        rc = self._L.iqd_gather_info(self._h, C.byref(v), C.byref(n), C.byref(r))
-        if rc != 0:
-            raise IqdError(rc, "iqd_gather_info failed")
+        _ok(self._L.iqd_gather_info(self._h, C.byref(v), C.byref(n), C.byref(r)), "iqd_gather_info failed")
         return {"version": v.value, "ranks": n.value, "library_reused": bool(r.value)}
 
-    def close(self):
-        if self._h:
-            self._L.iqd_gather_destroy(self._h)
-            self._h = None
 
-
-class Resampler:
+class Resampler(_EngineChild):
     """Block-wise Decimator / Interpolator / Interpolator_int16 for n_channels streams (include/iqdemod.h)."""
     KINDS = {"decimate_f32": 0, "interpolate_f32": 1, "interpolate_i16": 2}
 
     def __init__(self, engine, kind, taps, factor, n_channels=1):
-        self._e, self._L = engine, engine._L
         self.kind, self.n_ch = self.KINDS[kind], n_channels
         taps = np.ascontiguousarray(taps, np.float32)
-        h = C.c_void_p()
-        engine._check(self._L.iqd_resampler_create(engine._h, self.kind, _np_ptr(taps), len(taps), int(factor),
-                                                   n_channels, C.byref(h)))
-        self._h = h
+        self._create(engine, "resampler", self.kind, _np_ptr(taps), len(taps), int(factor), n_channels)
         self.dtype = np.int16 if self.kind == 2 else np.float32
 
     def run(self, x):
@@ -695,29 +657,20 @@ class Resampler:
     def reset(self):
         self._e._check(self._L.iqd_resampler_reset(self._h))
 
-    def close(self):
-        if self._h:
-            self._L.iqd_resampler_destroy(self._h)
-            self._h = None
 
-class Filter:
+class Filter(_EngineChild):
     """Block-wise Decimator_int16 / FirFilter_int16 / FirFilter / IirFilter for n_channels streams (include/iqdemod.h:
     iqd_filter_*).  kind: "decimate_i16", "fir_i16", "fir_f32" or "iir_f32"; num: the taps (IIR: the numerator), den: the
     IIR's denominator without its leading 1 (None for the FIR kinds)."""
     KINDS = {"decimate_i16": 0, "fir_i16": 1, "fir_f32": 2, "iir_f32": 3}
 
     def __init__(self, engine, kind, num, den=None, factor=1, n_channels=1):
-        self._e, self._L = engine, engine._L
-        self._h = None
         self.kind, self.n_ch = self.KINDS.get(kind, kind), int(n_channels)
         self.dtype = np.int16 if self.kind in (0, 1) else np.float32
         num = None if num is None else np.ascontiguousarray(num, np.float32)
         den = None if den is None else np.ascontiguousarray(den, np.float32)
-        h = C.c_void_p()
-        engine._check(self._L.iqd_filter_create(engine._h, int(self.kind), _np_ptr(num), 0 if num is None else len(num),
-                                                _np_ptr(den), 0 if den is None else len(den), int(factor), self.n_ch,
-                                                C.byref(h)))
-        self._h = h
+        self._create(engine, "filter", int(self.kind), _np_ptr(num), 0 if num is None else len(num),
+                     _np_ptr(den), 0 if den is None else len(den), int(factor), self.n_ch)
 
     def out_count(self, n_in):
         return int(self._L.iqd_filter_out_count(self._h, int(n_in)))
@@ -726,9 +679,7 @@ class Filter:
         """[n_channels, n_in] host array (or one row) -> [n_channels, out_count(n_in)]"""
         x = np.ascontiguousarray(x, self.dtype).reshape(self.n_ch, -1)
         out = np.zeros((self.n_ch, self.out_count(x.shape[1])), self.dtype)
-        guard = out if out.size else np.zeros(8, self.dtype)    # (a call without output gets a valid pointer all the same)
-        xin = x if x.size else np.zeros(8, self.dtype)
-        self._e._check(self._L.iqd_filter_run(self._h, _np_ptr(xin), x.shape[1], _np_ptr(guard)))
+        self._e._check(self._L.iqd_filter_run(self._h, _ptr_or_placeholder(x), x.shape[1], _ptr_or_placeholder(out)))
         return out
 
     def run_device(self, in_dev, n_in, out_dev):
@@ -737,13 +688,6 @@ class Filter:
 
     def reset(self):
         self._e._check(self._L.iqd_filter_reset(self._h))
-
-    def close(self):
-        if self._h and self._e._h:
-            self._L.iqd_filter_destroy(self._h)
-        self._h = None
-
-    __del__ = close
 
 
 def filter_tile_samples(kind, n_num, n_den=0, factor=1):
@@ -760,27 +704,22 @@ def filter_clamp_free_taps(taps):
 def channelizer_phasor_table():
     """The channelizer's phasor table P[i] = (c, s), [4096, 2] int16 (host only, no GPU)."""
     out = np.zeros(8192, np.int16)
-    rc = _lib().iqd_channelizer_phasor_table(_np_ptr(out))
-    if rc != 0:
-        raise IqdError(rc, "iqd_channelizer_phasor_table")
+    _ok(_lib().iqd_channelizer_phasor_table(_np_ptr(out)), "iqd_channelizer_phasor_table")
     return out.reshape(4096, 2)
 
 
 def channelizer_default_taps(decimation, den=1):
     """The library's default Q15 prototype for decimation M, or for the fractional decimation / den (the prototype at
     the rate 256000 decimation, quantised per branch) (host only, no GPU)."""
-    L = _lib()
     if int(den) == 1:
-        n = L.iqd_channelizer_default_taps(int(decimation), None, 0)
+        ask, which = _lib().iqd_channelizer_default_taps, (int(decimation),)
     else:
-        n = L.iqd_channelizer_default_taps_q(int(decimation), int(den), None, 0)
+        ask, which = _lib().iqd_channelizer_default_taps_q, (int(decimation), int(den))
+    n = ask(*which, None, 0)
     if n < 0:
         raise IqdError(n, "no default taps for decimation %r / %r" % (decimation, den))
     out = np.zeros(n, np.int16)
-    if int(den) == 1:
-        L.iqd_channelizer_default_taps(int(decimation), _np_ptr(out), n)
-    else:
-        L.iqd_channelizer_default_taps_q(int(decimation), int(den), _np_ptr(out), n)
+    ask(*which, _np_ptr(out), n)
     return out
 
 
@@ -794,8 +733,7 @@ def channelizer_tuning(decimation, source_centre_hz, station_hz, rotation=1):
     rc = _lib().iqd_channelizer_tuning(int(decimation), int(source_centre_hz), int(station_hz), int(rotation), C.byref(inc))
     if rc == -1:
         return None
-    if rc != 0:
-        raise IqdError(rc, "iqd_channelizer_tuning")
+    _ok(rc, "iqd_channelizer_tuning")
     return inc.value
 
 
@@ -825,17 +763,35 @@ def channelizer_track_window_outputs(decimation, n_taps):
     return int(_lib().iqd_channelizer_track_window_outputs(int(decimation), int(n_taps)))
 
 
-class Channelizer(_EngineChild):
-    """iqd_channelizer_*: n_channels channels cut out of n_sources wideband captures at decimation / decimation_den x
-    256 kS/s (decimation_den 1, 2, 4 or 8; 2.4 MS/s is 75 / 8).  sample_format: what the captures hold - "u8" (offset
-    binary, the RTL-SDR's), "s8" (int8) or "s16" (little-endian int16); run and accept_wideband then take
-    [n_sources, 2 samples] arrays of that dtype."""
+class _CaptureChild(_EngineChild):
+    """An _EngineChild that reads n_sources wideband captures of one sample format; _what names it in messages."""
+    _what = None
 
-    def __init__(self, engine, decimation, n_channels, n_sources=1, taps=None, decimation_den=1, sample_format="u8"):
+    def _set_format(self, sample_format):
         if sample_format not in SAMPLE_FORMAT:
             raise ValueError("sample_format must be one of %s" % ", ".join(SAMPLE_FORMAT))
         self.sample_format = sample_format
         self._code, self._dtype = SAMPLE_FORMAT[sample_format]
+
+    def _capture(self, wide):
+        """One call's capture as [n_sources, bytes_per_source] bytes.  An array of another sample format's dtype is a
+        TypeError: a "u8" object refuses int8 / int16 arrays, "s8" and "s16" anything but their own dtype."""
+        dt = getattr(wide, "dtype", None)
+        if dt is not None and dt != self._dtype and (self._code != 0 or dt in (np.dtype(np.int8), np.dtype(np.int16))):
+            raise TypeError("a %s of sample_format %r takes %s arrays, not %s" % (self._what, self.sample_format, self._dtype, dt))
+        wide = np.ascontiguousarray(wide, dtype=self._dtype).reshape(self.n_sources, -1)
+        return wide.view(np.uint8)
+
+
+class Channelizer(_CaptureChild):
+    """iqd_channelizer_*: n_channels channels cut out of n_sources wideband captures at decimation / decimation_den x
+    256 kS/s (decimation_den 1, 2, 4 or 8; 2.4 MS/s is 75 / 8).  sample_format: what the captures hold - "u8" (offset
+    binary, the RTL-SDR's), "s8" (int8) or "s16" (little-endian int16); run and accept_wideband then take
+    [n_sources, 2 samples] arrays of that dtype."""
+    _what = "channelizer"
+
+    def __init__(self, engine, decimation, n_channels, n_sources=1, taps=None, decimation_den=1, sample_format="u8"):
+        self._set_format(sample_format)
         self.rail_bytes = self._dtype.itemsize
         self.decimation, self.n_channels, self.n_sources = int(decimation), int(n_channels), int(n_sources)
         self.decimation_den = int(decimation_den) or 1
@@ -844,7 +800,10 @@ class Channelizer(_EngineChild):
         cfg = ChannelizerConfig(self.n_sources, self.n_channels, self.decimation,
                                 0 if self._taps is None else len(self._taps),
                                 None if self._taps is None else self._taps.ctypes.data, int(decimation_den), self._code)
-        self._create(engine, "channelizer", cfg)
+        self._create(engine, "channelizer", C.byref(cfg))
+
+    def _range(self, first, n):
+        return int(first), (self.n_channels - int(first) if n is None else int(n))
 
     def set_channels(self, first=0, source=None, offset_hz=None, fs=None, phase_inc=None, gain_shift=None, n=None):
         """Retunes channels [first, first + n): offsets in Hz with the capture's rate fs, or raw increments; a field left
@@ -859,15 +818,6 @@ class Channelizer(_EngineChild):
         sh = None if arrs[2] is None else np.ascontiguousarray(np.broadcast_to(arrs[2], n), np.uint8)
         self._e._check(self._L.iqd_channelizer_set_channels(self._h, int(first), int(n), _np_ptr(src), _np_ptr(inc),
                                                             _np_ptr(sh)))
-
-    def _capture(self, wide):
-        """One call's capture as [n_sources, bytes_per_source] bytes.  An array of another sample format's dtype is a
-        TypeError: a "u8" channelizer refuses int8 / int16 arrays, "s8" and "s16" anything but their own dtype."""
-        dt = getattr(wide, "dtype", None)
-        if dt is not None and dt != self._dtype and (self._code != 0 or dt in (np.dtype(np.int8), np.dtype(np.int16))):
-            raise TypeError("a channelizer of sample_format %r takes %s arrays, not %s" % (self.sample_format, self._dtype, dt))
-        wide = np.ascontiguousarray(wide, dtype=self._dtype).reshape(self.n_sources, -1)
-        return wide.view(np.uint8)
 
     def run(self, wide_u8):
         """[n_sources, bytes_per_source] uint8 -> [n_channels, bytes_per_source decimation_den / decimation] uint8 (host
@@ -918,27 +868,21 @@ class Channelizer(_EngineChild):
 
     def follow_scanner(self, follow=True, first=0, n=None):
         """Channels [first, first + n) follow (or stop following) their engine channel's scanner."""
-        n = self.n_channels - int(first) if n is None else int(n)
-        self._e._check(self._L.iqd_channelizer_follow_scanner(self._h, int(first), n, 1 if follow else 0))
+        self._e._check(self._L.iqd_channelizer_follow_scanner(self._h, *self._range(first, n), 1 if follow else 0))
 
     def follow_gain(self, follow=True, first=0, n=None):
         """Channels [first, first + n) follow (or stop following) their engine channel's IF gain: the channelizer applies it,
         in dB and per engine block, in place of the channel's gain shift."""
-        n = self.n_channels - int(first) if n is None else int(n)
-        self._e._check(self._L.iqd_channelizer_follow_gain(self._h, int(first), n, 1 if follow else 0))
+        self._e._check(self._L.iqd_channelizer_follow_gain(self._h, *self._range(first, n), 1 if follow else 0))
 
     def follow_tracks(self, slot, first=0, n=None):
         """Channels [first, first + n) follow slot[i] of their source's track table row (one value: all the same slot);
         -1 or None: they stop following."""
-        if slot is None:
-            n = self.n_channels - int(first) if n is None else int(n)
-            self._e._check(self._L.iqd_channelizer_follow_tracks(self._h, int(first), n, None))
-            return
-        s = np.atleast_1d(np.asarray(slot, dtype=np.int64))
-        if n is None:
-            n = len(s) if np.ndim(slot) else self.n_channels - int(first)
-        s = np.ascontiguousarray(np.clip(np.broadcast_to(s, int(n)), -2 ** 31, 2 ** 31 - 1), np.int32)
-        self._e._check(self._L.iqd_channelizer_follow_tracks(self._h, int(first), int(n), _np_ptr(s)))
+        s = None if slot is None else np.atleast_1d(np.asarray(slot, dtype=np.int64))
+        first, n = self._range(first, len(s) if n is None and np.ndim(slot) else n)
+        if s is not None:
+            s = np.ascontiguousarray(np.clip(np.broadcast_to(s, n), -2 ** 31, 2 ** 31 - 1), np.int32)
+        self._e._check(self._L.iqd_channelizer_follow_tracks(self._h, first, n, _np_ptr(s)))
 
     def set_track_table(self, slots_dev, n_slots=0, n_blocks=0, block_bytes=0, lag=0, min_state=2, reserved=(0, 0, 0)):
         """The track table the followers read: slots_dev a device pointer (integer) to [n_sources][n_blocks][n_slots]
@@ -954,9 +898,7 @@ class Channelizer(_EngineChild):
 def spectrum_default_window(n_bins):
     """iqd_spectrum_default_window (host only, no GPU): the integer Hann window of n_bins entries, int16."""
     out = np.zeros(int(n_bins) if 0 < int(n_bins) <= 4096 else 1, np.int16)
-    rc = _lib().iqd_spectrum_default_window(int(n_bins) & 0xffffffff, _np_ptr(out))
-    if rc != 0:
-        raise IqdError(rc, "iqd_spectrum_default_window: n_bins %r" % (n_bins,))
+    _ok(_lib().iqd_spectrum_default_window(int(n_bins) & 0xffffffff, _np_ptr(out)), "iqd_spectrum_default_window: n_bins %r" % (n_bins,))
     return out
 
 
@@ -966,9 +908,8 @@ def spectrum_full_scale(n_bins, window=None):
     if w is not None and len(w) != int(n_bins):
         raise ValueError("the window must have n_bins (%d) entries, not %d" % (int(n_bins), len(w)))
     p = C.c_uint32()
-    rc = _lib().iqd_spectrum_full_scale(_np_ptr(w), int(n_bins) & 0xffffffff, C.byref(p))
-    if rc != 0:
-        raise IqdError(rc, "iqd_spectrum_full_scale: n_bins %r or the window out of range" % (n_bins,))
+    _ok(_lib().iqd_spectrum_full_scale(_np_ptr(w), int(n_bins) & 0xffffffff, C.byref(p)),
+        "iqd_spectrum_full_scale: n_bins %r or the window out of range" % (n_bins,))
     return p.value
 
 
@@ -977,32 +918,21 @@ def spectrum_dbfs(power, p_fs):
     return 10.0 * np.log10(np.maximum(np.asarray(power, np.float64), 1.0) / float(p_fs))
 
 
-class Spectrum(_EngineChild):
+class Spectrum(_CaptureChild):
     """iqd_spectrum_*: the integer periodogram of n_sources wideband captures, n_bins bins (64 .. 2048, a power of two) from
     low to high frequency, the centre frequency at bin n_bins / 2.  window: n_bins int16 values (None: the default Hann
     window); sample_format "u8" or "s8"."""
+    _what = "spectrum"
 
     def __init__(self, engine, n_bins, n_sources=1, window=None, sample_format="u8"):
-        if sample_format not in SAMPLE_FORMAT:
-            raise ValueError("sample_format must be one of %s" % ", ".join(SAMPLE_FORMAT))
-        self.sample_format = sample_format
-        self._code, self._dtype = SAMPLE_FORMAT[sample_format]
+        self._set_format(sample_format)
         self.n_bins, self.n_sources = int(n_bins), int(n_sources)
         self._window = None if window is None else np.ascontiguousarray(window, np.int16)
         if self._window is not None and self._window.shape != (self.n_bins,):
             raise ValueError("the window must have n_bins (%d) entries" % self.n_bins)
         cfg = SpectrumConfig(self.n_sources & 0xffffffff, self.n_bins & 0xffffffff,
                              None if self._window is None else self._window.ctypes.data, self._code)
-        self._create(engine, "spectrum", cfg)
-
-    def _capture(self, wide):
-        """One call's capture as [n_sources, bytes_per_source] bytes; an array of the other format's dtype is a TypeError
-        (as Channelizer._capture)."""
-        dt = getattr(wide, "dtype", None)
-        if dt is not None and dt != self._dtype and (self._code != 0 or dt in (np.dtype(np.int8), np.dtype(np.int16))):
-            raise TypeError("a spectrum of sample_format %r takes %s arrays, not %s" % (self.sample_format, self._dtype, dt))
-        wide = np.ascontiguousarray(wide, dtype=self._dtype).reshape(self.n_sources, -1)
-        return wide.view(np.uint8)
+        self._create(engine, "spectrum", C.byref(cfg))
 
     def run(self, wide, frames_per_block):
         """[n_sources, bytes_per_source] of the format's dtype -> [n_sources, n_blocks, n_bins] uint32 (host arrays),
@@ -1023,11 +953,8 @@ class Spectrum(_EngineChild):
 def detect_offset_hz(n_bins, rate_hz, centroid_q8):
     """iqd_detect_offset_hz (host only, no GPU): a detection's centroid as the offset in Hz from the capture's centre,
     floor(((centroid_q8 - 128 N) rate + 128 N) / (256 N)) - what channelizer_tuning takes as station - centre."""
-    hz = C.c_int64()
-    args = [int(v) for v in (n_bins, rate_hz, centroid_q8)]
-    if any(v < 0 or v > 0xffffffff for v in args) or _lib().iqd_detect_offset_hz(*args, C.byref(hz)) != 0:
-        raise IqdError(-1, "iqd_detect_offset_hz: n_bins %r, rate_hz %r or centroid_q8 %r out of range" % (n_bins, rate_hz, centroid_q8))
-    return hz.value
+    return _u32_function("iqd_detect_offset_hz", C.c_int64(), (n_bins, rate_hz, centroid_q8),
+                         "iqd_detect_offset_hz: n_bins %r, rate_hz %r or centroid_q8 %r out of range" % (n_bins, rate_hz, centroid_q8))
 
 
 class Detector(_EngineChild):
@@ -1039,8 +966,8 @@ class Detector(_EngineChild):
     def __init__(self, engine, n_bins, floor_rank=None, ratio_q8=2048, dc_guard=1, bridge=8, min_width=3, max_detections=16):
         self.n_bins, self.max_detections = int(n_bins), int(max_detections)
         rank = self.n_bins // 2 if floor_rank is None else int(floor_rank)
-        cfg = DetectConfig(*[int(v) & 0xffffffff for v in (n_bins, rank, ratio_q8, dc_guard, bridge, min_width, max_detections)])
-        self._create(engine, "detect", cfg)
+        cfg = _u32_config(DetectConfig, (n_bins, rank, ratio_q8, dc_guard, bridge, min_width, max_detections))
+        self._create(engine, "detect", C.byref(cfg))
 
     def run(self, power):
         """[..., n_bins] uint32 (host array; a Spectrum.run result as it is) -> (rows [n_rows] DETECT_ROW,
@@ -1065,11 +992,8 @@ class Detector(_EngineChild):
 def track_phase_inc(n_bins, centroid_q8, inc_bias=0):
     """iqd_track_phase_inc (host only, no GPU): the channelizer phase_inc of a centre in 1/256 bins,
     (uint32)((centroid_q8 - 128 N) 2^(24 - log2 N)) + inc_bias mod 2^32 - what Channelizer.set_channels takes."""
-    inc = C.c_uint32()
-    args = [int(v) for v in (n_bins, centroid_q8, inc_bias)]
-    if any(v < 0 or v > 0xffffffff for v in args) or _lib().iqd_track_phase_inc(*args, C.byref(inc)) != 0:
-        raise IqdError(-1, "iqd_track_phase_inc: n_bins %r or centroid_q8 %r out of range" % (n_bins, centroid_q8))
-    return inc.value
+    return _u32_function("iqd_track_phase_inc", C.c_uint32(), (n_bins, centroid_q8, inc_bias),
+                         "iqd_track_phase_inc: n_bins %r or centroid_q8 %r out of range" % (n_bins, centroid_q8))
 
 
 def track_default_edges(n_bins):
@@ -1090,11 +1014,9 @@ class Tracker(_EngineChild):
         edges = track_default_edges(n_bins) if class_edge is None else tuple(int(v) for v in class_edge)
         if len(edges) != 3:
             raise ValueError("class_edge must have three entries")
-        cfg = TrackConfig(*[int(v) & 0xffffffff for v in (n_sources, n_bins, max_detections, n_slots, gate_q8, open_hits, hold_blocks,
-                                                          alpha_q8, inc_bias)])
-        for i in range(3):
-            cfg.class_edge[i] = edges[i] & 0xffffffff
-        self._create(engine, "track", cfg)
+        cfg = _u32_config(TrackConfig, (n_sources, n_bins, max_detections, n_slots, gate_q8, open_hits, hold_blocks, alpha_q8, inc_bias),
+                          class_edge=edges)
+        self._create(engine, "track", C.byref(cfg))
 
     def run(self, rows, det):
         """rows [n_sources, n_blocks] DETECT_ROW and det [n_sources, n_blocks, max_detections] DETECTION (host arrays; a
@@ -1149,11 +1071,9 @@ class Measure(_EngineChild):
         given = dict(margin=margin, obw_tail_q16=obw_tail_q16, carrier_half=carrier_half, min_sum=min_sum,
                      carrier_min_q8=carrier_min_q8, wide_bins=wide_bins)
         v = dict(measure_defaults(n_bins), **{k: x for k, x in given.items() if x is not None})
-        cfg = MeasureConfig(*[int(x) & 0xffffffff for x in (n_sources, n_bins, n_slots, dc_guard, v["margin"], v["obw_tail_q16"],
-                                                            v["carrier_half"], v["min_sum"], v["carrier_min_q8"], v["wide_bins"])])
-        for i in range(2):
-            cfg.reserved[i] = int(reserved[i]) & 0xffffffff
-        self._create(engine, "measure", cfg)
+        cfg = _u32_config(MeasureConfig, (n_sources, n_bins, n_slots, dc_guard, v["margin"], v["obw_tail_q16"], v["carrier_half"],
+                                          v["min_sum"], v["carrier_min_q8"], v["wide_bins"]), reserved=reserved)
+        self._create(engine, "measure", C.byref(cfg))
 
     def run(self, power, rows, slots):
         """power [n_sources, n_blocks, n_bins] uint32, rows [n_sources, n_blocks] DETECT_ROW, slots [n_sources, n_blocks,
@@ -1185,11 +1105,8 @@ def tracklog_defaults():
 def tracklog_mean_centre(sum_centre_q8, n_active):
     """iqd_tracklog_mean_centre (host only, no GPU): floor(sum_centre_q8 / n_active), a track's mean centre in 1/256 bins -
     what detect_offset_hz and track_phase_inc take."""
-    out = C.c_uint32()
-    a, n = int(sum_centre_q8), int(n_active)
-    if not (0 <= a < 2 ** 64 and 0 <= n < 2 ** 32) or _lib().iqd_tracklog_mean_centre(a, n, C.byref(out)) != 0:
-        raise IqdError(-1, "iqd_tracklog_mean_centre: sum_centre_q8 %r or n_active %r out of range" % (sum_centre_q8, n_active))
-    return out.value
+    return _u32_function("iqd_tracklog_mean_centre", C.c_uint32(), (sum_centre_q8, n_active),
+                         "iqd_tracklog_mean_centre: sum_centre_q8 %r or n_active %r out of range" % (sum_centre_q8, n_active), bits=64)
 
 
 class TrackLog(_EngineChild):
@@ -1203,10 +1120,8 @@ class TrackLog(_EngineChild):
         given = dict(max_events=max_events, min_active=min_active, vote_min=vote_min)
         v = dict(tracklog_defaults(), **{k: x for k, x in given.items() if x is not None})
         self.max_events = int(v["max_events"])
-        cfg = TrackLogConfig(*[int(x) & 0xffffffff for x in (n_sources, n_slots, v["max_events"], v["min_active"], v["vote_min"])])
-        for i in range(3):
-            cfg.reserved[i] = int(reserved[i]) & 0xffffffff
-        self._create(engine, "tracklog", cfg)
+        cfg = _u32_config(TrackLogConfig, (n_sources, n_slots, v["max_events"], v["min_active"], v["vote_min"]), reserved=reserved)
+        self._create(engine, "tracklog", C.byref(cfg))
 
     def run(self, slots, meas):
         """slots [n_sources, n_blocks, n_slots] TRACK_SLOT and meas [n_sources, n_blocks, n_slots] TRACK_MEASURE (host arrays:
