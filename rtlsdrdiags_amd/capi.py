@@ -251,9 +251,10 @@ EXPORTS = list(PROTOTYPES)
 _LIB = None
 
 
-def _bind(L):
-    """Gives every function of `L` its prototype (a library without one of them raises); returns L."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
+def _bind(L, table=None):
+    """Gives every function of `L` its prototype (a library without one of them raises); returns L.  `table`: an add-on's
+    table (tones.PROTOTYPES) instead of this module's."""
+    for name, (restype, argtypes) in (PROTOTYPES if table is None else table).items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     return L

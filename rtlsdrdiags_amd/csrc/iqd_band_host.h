@@ -1,8 +1,9 @@
 // What the host code of the five band objects shares (iqd_spectrum.cpp, iqd_detect.cpp, iqd_track.cpp, iqd_measure.cpp,
-// iqd_tracklog.cpp; nothing else includes this): one description of a call's pointer arguments, which drives the NULL
-// refusals, the alignment refusals and the staged host call; the refusals with one text for all; destroy; and the tracker's
-// and the log's state block.  A run refuses before it queues: NULLs in argument order, then the counts, then (run_device) the
-// alignment.  Every text is ABI behaviour (tests/golden/band_refusals.json has each, and which wins).  No allocation per call.
+// iqd_tracklog.cpp; the tone bank, iqd_tones.cpp, borrows BandArg, the create and reserved checks and destroy): one
+// description of a call's pointer arguments, which drives the NULL refusals, the alignment refusals and the staged host call;
+// the refusals with one text for all; destroy; and the tracker's and the log's state block.  A run refuses before it queues:
+// NULLs in argument order, then the counts, then (run_device) the alignment.  Every text is ABI behaviour
+// (tests/golden/band_refusals.json has each, and which wins).  No allocation per call.
 #pragma once
 #include "iqd_engine_impl.h"
 
