@@ -12,7 +12,7 @@ def needs_build():
         return True
     t = os.path.getmtime(LIB)
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-    srcs += [os.path.join(HERE, "..", "include", h) for h in ("iqdemod.h", "iqdemod_tones.h")]
+    srcs += [os.path.join(HERE, "..", "include", h) for h in ("iqdemod.h", "iqdemod_tones.h", "iqdemod_fsk.h")]
     return any(os.path.getmtime(s) > t for s in srcs if os.path.isfile(s))
 
 
