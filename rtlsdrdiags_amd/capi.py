@@ -334,6 +334,56 @@ class _EngineChild:
     __del__ = close
 
 
+# ---- PCM add-ons (tones.py, fsk.py): an add-on's functions have their own table in its module; this module's is iqdemod.h alone
+_ADDONS_BOUND = set()
+
+
+def _addon_lib(prototypes):
+    """_lib() with an add-on's PROTOTYPES set on it (once per table)"""
+    if id(prototypes) not in _ADDONS_BOUND:
+        _bind(_lib(), prototypes)
+        _ADDONS_BOUND.add(id(prototypes))
+    return _lib()
+
+
+def _addon_phase_inc(prototypes, kind, freq_mhz, rate_hz):
+    """iqd_<kind>_phase_inc (host only): a phase increment from a frequency in millihertz and the PCM rate in Hz"""
+    _addon_lib(prototypes)
+    return _u32_function("iqd_%s_phase_inc" % kind, C.c_uint32(), (freq_mhz, rate_hz),
+                         "iqd_%s_phase_inc: freq_mhz %r must be below 500 rate_hz (%r), rate_hz not 0" % (kind, freq_mhz, rate_hz), bits=64)
+
+
+class _PcmChild(_EngineChild):
+    """An add-on on [n_channels, row_stride] int16 rows with state per channel.  A subclass names _State, the ctypes mirror of
+    its get_state record, and sets n_channels before _create."""
+    _State = None
+
+    def _fn(self, name):
+        return getattr(self._L, "iqd_%s_%s" % (self._kind, name))
+
+    def _rows(self, pcm, n, count):
+        """run's first arguments as the library takes them: (pcm [n_channels, row_stride] int16, row_stride, n, count or None)"""
+        pcm = np.ascontiguousarray(pcm, np.int16).reshape(self.n_channels, -1)
+        stride = pcm.shape[1]
+        return pcm, stride, stride if n is None else int(n), None if count is None else np.ascontiguousarray(count, np.uint32)
+
+    def _run_device(self, engine, *args):
+        """iqd_<kind>_run_device on `engine` or the object's own; a refusal's text is the object's engine's"""
+        self._e._check(self._fn("run_device")((self._e if engine is None else engine)._h, self._h, *args))
+
+    def reset(self):
+        """iqd_<kind>_reset: every channel's carried state cleared."""
+        self._e._check(self._fn("reset")(self._h))
+
+    def state(self, channel=0):
+        """iqd_<kind>_get_state: one channel's record as a dict of integers (without `reserved`); synchronises."""
+        s = self._State()
+        if not 0 <= int(channel) <= 0xffffffff:
+            raise IqdError(-1, "iqd_%s_get_state: channel %r out of range" % (self._kind, channel))
+        self._e._check(self._fn("get_state")(self._h, int(channel), C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in self._State._fields_ if k != "reserved"}
+
+
 class Engine:
     """N independent channels, each one reference IqDataProcessor + its four demodulators."""
 

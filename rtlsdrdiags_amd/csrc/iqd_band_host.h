@@ -1,99 +1,29 @@
-// What the host code of the five band objects shares (iqd_spectrum.cpp, iqd_detect.cpp, iqd_track.cpp, iqd_measure.cpp,
-// iqd_tracklog.cpp; the tone bank, iqd_tones.cpp, borrows BandArg, the create and reserved checks and destroy): one
-// description of a call's pointer arguments, which drives the NULL refusals, the alignment refusals and the staged host call;
-// the refusals with one text for all; destroy; and the tracker's and the log's state block.  A run refuses before it queues:
-// NULLs in argument order, then the counts, then (run_device) the alignment.  Every text is ABI behaviour
-// (tests/golden/band_refusals.json has each, and which wins).  No allocation per call.
+// What the host code of the five band objects shares beyond iqd_obj_host.h (iqd_spectrum.cpp, iqd_detect.cpp, iqd_track.cpp,
+// iqd_measure.cpp, iqd_tracklog.cpp): the bin counts and their refusal, a run's NULL and block-count refusals, and the tracker's
+// and the log's state block.  Every text is ABI behaviour (tests/golden/band_refusals.json has each, and which wins).
 #pragma once
-#include "iqd_engine_impl.h"
+#include "iqd_obj_host.h"
 
 namespace iqd {
-
-// One pointer argument of run / run_device.  run_device reads name and ptr only.
-struct BandArg {
-    const char *name;    // as the messages spell it
-    const void *ptr;     // the caller's array: on the host for run, on the device for run_device
-    size_t bytes;        // of the whole array, for run's copies
-    DevBuf *stage;       // where run keeps its device copy
-    bool out;            // run copies it back, not in
-};
-template <size_t K> struct BandArgs { BandArg a[K]; };
-constexpr bool BAND_IN = false, BAND_OUT = true;
 
 constexpr uint32_t BAND_MIN_BINS = 64, BAND_MAX_BINS = 2048;
 constexpr size_t BAND_MAX_ROWS = 0x7fffffffull;      // n_sources x n_blocks of one call
 
 inline bool band_bins_ok(uint32_t n) { return n >= BAND_MIN_BINS && n <= BAND_MAX_BINS && (n & (n - 1)) == 0; }
 
-// create's first refusals; without an engine there is nowhere to leave a text
-inline int band_create_check(iqd_t *e, const void *cfg, const void *out, const char *who)
-{
-    if (!e) return IQD_EINVAL;
-    if (!out) return e->fail(IQD_EINVAL, "%s: out is NULL", who);
-    if (!cfg) return e->fail(IQD_EINVAL, "%s: cfg is NULL", who);
-    return IQD_OK;
-}
-
 inline int band_bins_check(iqd_t *e, uint32_t n, const char *who)
 {
     return band_bins_ok(n) ? IQD_OK : e->fail(IQD_EINVAL, "%s: n_bins (%u) must be 64, 128, 256, 512, 1024 or 2048", who, n);
 }
 
-template <int K> int band_reserved_check(iqd_t *e, const uint32_t (&reserved)[K], const char *who)
-{
-    for (int i = 0; i < K; i++)
-        if (reserved[i]) return e->fail(IQD_EINVAL, "%s: reserved[%d] is not 0", who, i);
-    return IQD_OK;
-}
-
-// what the object has queued on the engine's stream is done before its buffers go
-template <class T> void band_destroy(T *o)
-{
-    if (!o) return;
-    (void)hipSetDevice(o->e->device);
-    (void)hipStreamSynchronize(o->e->stream);
-    delete o;
-}
-
-template <size_t K> int band_null_check(iqd_t *e, const BandArgs<K> &args, const char *who)
-{
-    for (const BandArg &x : args.a)
-        if (!x.ptr) return e->fail(IQD_EINVAL, "%s: %s is NULL", who, x.name);
-    return IQD_OK;
-}
-
 // a run of n_blocks blocks of n_sources sources: the NULLs, then the count
-template <size_t K> int band_run_check(iqd_t *e, const BandArgs<K> &args, size_t n_blocks, uint32_t n_sources, const char *who)
+template <size_t K> int band_run_check(iqd_t *e, const ObjArgs<K> &args, size_t n_blocks, uint32_t n_sources, const char *who)
 {
-    int rc = band_null_check(e, args, who);
+    int rc = obj_null_check(e, args, who);
     if (rc != IQD_OK) return rc;
     if (n_blocks == 0) return e->fail(IQD_EINVAL, "%s: n_blocks is 0", who);
     if (n_blocks > BAND_MAX_ROWS / n_sources)
         return e->fail(IQD_EINVAL, "%s: n_blocks (%zu) times n_sources (%u) is more than one call covers (2^31 - 1)", who, n_blocks, n_sources);
-    return IQD_OK;
-}
-
-template <size_t K> int band_align_check(iqd_t *e, const BandArgs<K> &args, const char *who)
-{
-    for (const BandArg &x : args.a)
-        if ((uintptr_t)x.ptr % 16) return e->fail(IQD_EINVAL, "%s: %s_dev is not 16-byte aligned", who, x.name);
-    return IQD_OK;
-}
-
-// The host form of a run whose args have passed its checks.  Every staging buffer is there before the first copy, so a failed
-// allocation queues nothing; then the inputs go in, run_device() - the object's own, on the staging buffers - queues its
-// launch, the outputs come back, and the call waits for them.
-template <size_t K, class RunDevice> int band_staged_run(iqd_t *e, const BandArgs<K> &args, RunDevice run_device)
-{
-    (void)hipSetDevice(e->device);
-    for (const BandArg &x : args.a) HIP_TRY(e, x.stage->ensure(x.bytes));
-    for (const BandArg &x : args.a)
-        if (!x.out) HIP_COPY(e, hipMemcpyAsync(x.stage->p, x.ptr, x.bytes, hipMemcpyHostToDevice, e->stream));
-    int rc = run_device();
-    if (rc != IQD_OK) return rc;
-    for (const BandArg &x : args.a)
-        if (x.out) HIP_COPY(e, hipMemcpyAsync(const_cast<void *>(x.ptr), x.stage->p, x.bytes, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
     return IQD_OK;
 }
 

@@ -25,7 +25,7 @@ int iqd_detect_offset_hz(uint32_t n_bins, uint32_t rate_hz, uint32_t centroid_q8
 
 int iqd_detect_create(iqd_t *e, const iqd_detect_config *cfg, iqd_detect_t **out)
 {
-    int rc = band_create_check(e, cfg, out, __func__);
+    int rc = obj_create_check(e, cfg, out, __func__);
     if (rc != IQD_OK) return rc;
     const uint32_t n = cfg->n_bins;
     if ((rc = band_bins_check(e, n, __func__)) != IQD_OK) return rc;
@@ -38,7 +38,7 @@ int iqd_detect_create(iqd_t *e, const iqd_detect_config *cfg, iqd_detect_t **out
         return e->fail(IQD_EINVAL, "iqd_detect_create: min_width (%u) must be 1 .. n_bins (%u)", cfg->min_width, n);
     if (cfg->max_detections == 0 || cfg->max_detections > n / 2)
         return e->fail(IQD_EINVAL, "iqd_detect_create: max_detections (%u) must be 1 .. n_bins / 2 (%u)", cfg->max_detections, n / 2);
-    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
+    if ((rc = obj_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
     iqd_detect *d = new (std::nothrow) iqd_detect;
     if (!d) return IQD_ENOMEM;
     d->e = e;
@@ -47,21 +47,21 @@ int iqd_detect_create(iqd_t *e, const iqd_detect_config *cfg, iqd_detect_t **out
     return IQD_OK;
 }
 
-void iqd_detect_destroy(iqd_detect_t *d) { band_destroy(d); }
+void iqd_detect_destroy(iqd_detect_t *d) { obj_destroy(d); }
 
 // the call's arrays, as run stages them
-static BandArgs<3> detect_args(iqd_detect_t *d, const void *power, size_t n_rows, void *rows, void *det)
+static ObjArgs<3> detect_args(iqd_detect_t *d, const void *power, size_t n_rows, void *rows, void *det)
 {
-    return {{{"power", power, n_rows * d->cfg.n_bins * sizeof(uint32_t), &d->st_in, BAND_IN},
-             {"rows", rows, n_rows * sizeof(iqd_detect_row), &d->st_rows, BAND_OUT},
-             {"det", det, n_rows * d->cfg.max_detections * sizeof(iqd_detection), &d->st_det, BAND_OUT}}};
+    return {{{"power", power, n_rows * d->cfg.n_bins * sizeof(uint32_t), &d->st_in, ARG_IN},
+             {"rows", rows, n_rows * sizeof(iqd_detect_row), &d->st_rows, ARG_OUT},
+             {"det", det, n_rows * d->cfg.max_detections * sizeof(iqd_detection), &d->st_det, ARG_OUT}}};
 }
 
 // rows have no sources: the count's refusals are the detector's own
-static int detect_run_check(iqd_detect_t *d, const BandArgs<3> &args, size_t n_rows, const char *who)
+static int detect_run_check(iqd_detect_t *d, const ObjArgs<3> &args, size_t n_rows, const char *who)
 {
     iqd_t *e = d->e;
-    int rc = band_null_check(e, args, who);
+    int rc = obj_null_check(e, args, who);
     if (rc != IQD_OK) return rc;
     if (n_rows == 0) return e->fail(IQD_EINVAL, "%s: n_rows is 0", who);
     if (n_rows > DET_MAX_ROWS) return e->fail(IQD_EINVAL, "%s: n_rows (%zu) is more than one launch covers (2^31 - 1)", who, n_rows);
@@ -72,9 +72,9 @@ int iqd_detect_run_device(iqd_detect_t *d, const uint32_t *power_dev, size_t n_r
 {
     if (!d) return IQD_EINVAL;
     iqd_t *e = d->e;
-    const BandArgs<3> args = detect_args(d, power_dev, n_rows, rows_dev, det_dev);
+    const ObjArgs<3> args = detect_args(d, power_dev, n_rows, rows_dev, det_dev);
     int rc = detect_run_check(d, args, n_rows, __func__);
-    if (rc == IQD_OK) rc = band_align_check(e, args, __func__);
+    if (rc == IQD_OK) rc = obj_align_check(e, args, __func__);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(e->device);
     const iqd_detect_config &c = d->cfg;
@@ -89,10 +89,10 @@ int iqd_detect_run_device(iqd_detect_t *d, const uint32_t *power_dev, size_t n_r
 int iqd_detect_run(iqd_detect_t *d, const uint32_t *power, size_t n_rows, iqd_detect_row *rows, iqd_detection *det)
 {
     if (!d) return IQD_EINVAL;
-    const BandArgs<3> args = detect_args(d, power, n_rows, rows, det);
+    const ObjArgs<3> args = detect_args(d, power, n_rows, rows, det);
     int rc = detect_run_check(d, args, n_rows, __func__);
     if (rc != IQD_OK) return rc;
-    return band_staged_run(d->e, args, [&] {
+    return obj_staged_run(d->e, args, [&] {
         return iqd_detect_run_device(d, d->st_in.as<const uint32_t>(), n_rows, d->st_rows.as<iqd_detect_row>(), d->st_det.as<iqd_detection>());
     });
 }

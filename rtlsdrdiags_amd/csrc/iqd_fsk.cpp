@@ -1,13 +1,14 @@
 // PCM packet decoder of libiqdemod.so (include/iqdemod_fsk.h: iqd_fsk_*), on the engine's stream.  Kernels: iqd_fsk.hip.
 // Here: the config's ranges, the correlators' coefficients, the call's sizes and arrays and the two launches, the host-only
-// helpers; the skeleton around them is iqd_band_host.h's, as the tone bank uses it.
-#include "iqd_band_host.h"
+// helpers; the skeleton around them is iqd_obj_host.h and its PCM part.
+#include "iqd_obj_host.h"
 #include "iqd_chan.h"
 #include "iqd_fsk.h"
 #include "iqdemod_fsk.h"
 
 static_assert(sizeof(iqd_fsk_frame) == iqd::FSK_RECORD_BYTES && sizeof(iqd_fsk_state) == iqd::FSK_STATE_BYTES &&
               sizeof(iqd::FskState) == iqd::FSK_STATE_BYTES && sizeof(iqd_fsk_config) == 64, "the ABI's records");
+static_assert(iqd::FSK_MAX_N == iqd::PCM_MAX_N, "the kernels' limit of n and row_stride");
 
 struct iqd_fsk {
     iqd_t *e = nullptr;
@@ -27,31 +28,15 @@ FskSizes fsk_sizes(const iqd_fsk *t, size_t n)
     return {(size_t)(mb / (8 * t->launch.min_len + 8) + 1), (size_t)((mb + 31) / 32), (size_t)((t->launch.max_len + mb / 8 + 15) / 16 * 16)};
 }
 
-// run's and run_device's refusals up to the counts: the engine, the NULLs in argument order, then n and row_stride
-template <size_t K>
-int fsk_run_check(iqd_t *e, iqd_fsk_t *t, const BandArgs<K> &args, size_t row_stride, size_t n, const char *who)
-{
-    if (e != t->e) return t->e->fail(IQD_EINVAL, "%s: t belongs to another engine", who);
-    for (const BandArg &x : args.a)
-        if (!x.ptr && x.stage) return e->fail(IQD_EINVAL, "%s: %s is NULL", who, x.name);
-    if (n > row_stride) return e->fail(IQD_EINVAL, "%s: n (%zu) is more than row_stride (%zu)", who, n, row_stride);
-    if (row_stride > FSK_MAX_N) return e->fail(IQD_EINVAL, "%s: row_stride (%zu) is more than 2^31 - 1", who, row_stride);
-    return IQD_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int iqd_fsk_create(iqd_t *e, const iqd_fsk_config *cfg, iqd_fsk_t **out)
 {
-    int rc = band_create_check(e, cfg, out, __func__);
+    int rc = pcm_create_check(e, cfg, out, IQD_FSK_ABI_VERSION, __func__);
     if (rc != IQD_OK) return rc;
     const uint32_t W = cfg->corr_len;
-    if (cfg->abi_version != IQD_FSK_ABI_VERSION)
-        return e->fail(IQD_EINVAL, "iqd_fsk_create: abi_version (%u) must be %u", cfg->abi_version, IQD_FSK_ABI_VERSION);
-    if (cfg->n_channels == 0 || cfg->n_channels > (1u << 20))
-        return e->fail(IQD_EINVAL, "iqd_fsk_create: n_channels (%u) must be 1 .. 2^20", cfg->n_channels);
     if (W < FSK_MIN_W || W > FSK_MAX_W) return e->fail(IQD_EINVAL, "iqd_fsk_create: corr_len (%u) must be 2 .. 64", W);
     if (cfg->baud_inc < (1u << 20) || cfg->baud_inc >= (1u << 31))
         return e->fail(IQD_EINVAL, "iqd_fsk_create: baud_inc (%u) must be 2^20 .. 2^31 - 1", cfg->baud_inc);
@@ -63,7 +48,7 @@ int iqd_fsk_create(iqd_t *e, const iqd_fsk_config *cfg, iqd_fsk_t **out)
     if (cfg->min_len < 3 || cfg->min_len > cfg->max_len)
         return e->fail(IQD_EINVAL, "iqd_fsk_create: min_len (%u) must be 3 .. max_len (%u)", cfg->min_len, cfg->max_len);
     if (cfg->max_len > FSK_MAX_LEN) return e->fail(IQD_EINVAL, "iqd_fsk_create: max_len (%u) must be 1024 at most", cfg->max_len);
-    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
+    if ((rc = obj_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
 
     iqd_fsk *t = new (std::nothrow) iqd_fsk;
     if (!t) return IQD_ENOMEM;
@@ -98,7 +83,7 @@ int iqd_fsk_create(iqd_t *e, const iqd_fsk_config *cfg, iqd_fsk_t **out)
     return IQD_OK;
 }
 
-void iqd_fsk_destroy(iqd_fsk_t *t) { band_destroy(t); }
+void iqd_fsk_destroy(iqd_fsk_t *t) { obj_destroy(t); }
 
 // the cleared state is all zeros: the clock, NRZI, the deframer, the counters and the carried samples (x[j] = 0 for j < 0);
 // the bit buffer needs no clearing: nbits = 0
@@ -112,49 +97,38 @@ int iqd_fsk_reset(iqd_fsk_t *t)
     return IQD_OK;
 }
 
-size_t iqd_fsk_max_frames(const iqd_fsk_t *t, size_t n) { return t && n <= FSK_MAX_N ? fsk_sizes(t, n).F : 0; }
-size_t iqd_fsk_max_bit_words(const iqd_fsk_t *t, size_t n) { return t && n <= FSK_MAX_N ? fsk_sizes(t, n).Bw : 0; }
-size_t iqd_fsk_max_bytes(const iqd_fsk_t *t, size_t n) { return t && n <= FSK_MAX_N ? fsk_sizes(t, n).Bc : 0; }
+size_t iqd_fsk_max_frames(const iqd_fsk_t *t, size_t n) { return t && n <= PCM_MAX_N ? fsk_sizes(t, n).F : 0; }
+size_t iqd_fsk_max_bit_words(const iqd_fsk_t *t, size_t n) { return t && n <= PCM_MAX_N ? fsk_sizes(t, n).Bw : 0; }
+size_t iqd_fsk_max_bytes(const iqd_fsk_t *t, size_t n) { return t && n <= PCM_MAX_N ? fsk_sizes(t, n).Bc : 0; }
 
 int iqd_fsk_get_state(iqd_fsk_t *t, uint32_t channel, iqd_fsk_state *state)
 {
-    if (!t) return IQD_EINVAL;
-    iqd_t *e = t->e;
-    if (!state) return e->fail(IQD_EINVAL, "iqd_fsk_get_state: state is NULL");
-    if (channel >= t->launch.n_channels)
-        return e->fail(IQD_EINVAL, "iqd_fsk_get_state: channel (%u) must be below n_channels (%u)", channel, t->launch.n_channels);
-    (void)hipSetDevice(e->device);
-    HIP_COPY(e, hipMemcpyAsync(state, t->state.as<FskState>() + channel, sizeof(FskState), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return IQD_OK;
+    return t ? pcm_get_state(t->e, t->state.as<FskState>(), t->launch.n_channels, channel, state, __func__) : IQD_EINVAL;
 }
 
-// the call's arrays, as run stages them; count and bits may be NULL (no staging buffer named: not checked, not copied)
-static BandArgs<7> fsk_args(iqd_fsk_t *t, const void *pcm, size_t row_stride, const void *count, size_t n, void *n_bits, void *bits,
-                            void *n_frames, void *frames, void *bytes)
+// the call's arrays, as run stages them and run_device wants them aligned; count and bits may be left out
+static ObjArgs<7> fsk_args(iqd_fsk_t *t, const void *pcm, size_t row_stride, const void *count, size_t n, void *n_bits, void *bits,
+                           void *n_frames, void *frames, void *bytes)
 {
     const size_t C = t->launch.n_channels;
-    const FskSizes z = n <= FSK_MAX_N ? fsk_sizes(t, n) : FskSizes{0, 0, 0};
-    return {{{"pcm", pcm, C * row_stride * sizeof(int16_t), &t->st_pcm, BAND_IN},
-             {"count", count, C * sizeof(uint32_t), count ? &t->st_count : nullptr, BAND_IN},
-             {"n_bits", n_bits, C * sizeof(uint32_t), &t->st_nbits, BAND_OUT},
-             {"bits", bits, C * z.Bw * sizeof(uint32_t), bits ? &t->st_bits : nullptr, BAND_OUT},
-             {"n_frames", n_frames, C * sizeof(uint32_t), &t->st_nframes, BAND_OUT},
-             {"frames", frames, C * z.F * sizeof(iqd_fsk_frame), &t->st_frames, BAND_OUT},
-             {"bytes", bytes, C * z.Bc, &t->st_bytes, BAND_OUT}}};
+    const FskSizes z = n <= PCM_MAX_N ? fsk_sizes(t, n) : FskSizes{0, 0, 0};
+    return {{{"pcm", pcm, C * row_stride * sizeof(int16_t), &t->st_pcm, ARG_IN, 2},
+             {"count", count, C * sizeof(uint32_t), &t->st_count, ARG_IN, 4, ARG_OPTIONAL},
+             {"n_bits", n_bits, C * sizeof(uint32_t), &t->st_nbits, ARG_OUT, 4},
+             {"bits", bits, C * z.Bw * sizeof(uint32_t), &t->st_bits, ARG_OUT, 4, ARG_OPTIONAL},
+             {"n_frames", n_frames, C * sizeof(uint32_t), &t->st_nframes, ARG_OUT, 4},
+             {"frames", frames, C * z.F * sizeof(iqd_fsk_frame), &t->st_frames, ARG_OUT, 8},
+             {"bytes", bytes, C * z.Bc, &t->st_bytes, ARG_OUT}}};
 }
 
 int iqd_fsk_run_device(iqd_t *e, iqd_fsk_t *t, const int16_t *pcm_dev, size_t row_stride, const uint32_t *count_dev, size_t n,
                        uint32_t *n_bits_dev, uint32_t *bits_dev, uint32_t *n_frames_dev, iqd_fsk_frame *frames_dev, uint8_t *bytes_dev)
 {
     if (!t) return IQD_EINVAL;
-    const BandArgs<7> args = fsk_args(t, pcm_dev, row_stride, count_dev, n, n_bits_dev, bits_dev, n_frames_dev, frames_dev, bytes_dev);
-    int rc = fsk_run_check(e, t, args, row_stride, n, __func__);
+    const ObjArgs<7> args = fsk_args(t, pcm_dev, row_stride, count_dev, n, n_bits_dev, bits_dev, n_frames_dev, frames_dev, bytes_dev);
+    int rc = pcm_run_check(e, t->e, args, row_stride, n, __func__);
+    if (rc == IQD_OK) rc = obj_align_check(e, args, __func__);
     if (rc != IQD_OK) return rc;
-    const size_t align[7] = {2, 4, 4, 4, 4, 8, 16};
-    for (size_t i = 0; i < 7; i++)
-        if ((uintptr_t)args.a[i].ptr % align[i])
-            return e->fail(IQD_EINVAL, "iqd_fsk_run_device: %s_dev is not %zu-byte aligned", args.a[i].name, align[i]);
     (void)hipSetDevice(e->device);
     const FskSizes z = fsk_sizes(t, n);
     FskLaunch a = t->launch;
@@ -175,33 +149,17 @@ int iqd_fsk_run(iqd_t *e, iqd_fsk_t *t, const int16_t *pcm, size_t row_stride, c
                 uint32_t *bits, uint32_t *n_frames, iqd_fsk_frame *frames, uint8_t *bytes)
 {
     if (!t) return IQD_EINVAL;
-    const BandArgs<7> args = fsk_args(t, pcm, row_stride, count, n, n_bits, bits, n_frames, frames, bytes);
-    int rc = fsk_run_check(e, t, args, row_stride, n, __func__);
+    const ObjArgs<7> args = fsk_args(t, pcm, row_stride, count, n, n_bits, bits, n_frames, frames, bytes);
+    int rc = pcm_run_check(e, t->e, args, row_stride, n, __func__);
     if (rc != IQD_OK) return rc;
-    // band_staged_run's order with the arrays the caller leaves out skipped: every staging buffer first (an empty array's too,
-    // so that run_device gets a pointer), the inputs, the launches, the outputs, the wait
-    (void)hipSetDevice(e->device);
-    for (const BandArg &x : args.a)
-        if (x.stage) HIP_TRY(e, x.stage->ensure(std::max<size_t>(x.bytes, 16)));
-    for (const BandArg &x : args.a)
-        if (x.stage && !x.out && x.bytes) HIP_COPY(e, hipMemcpyAsync(x.stage->p, x.ptr, x.bytes, hipMemcpyHostToDevice, e->stream));
-    rc = iqd_fsk_run_device(e, t, t->st_pcm.as<const int16_t>(), row_stride, count ? t->st_count.as<const uint32_t>() : nullptr, n,
-                            t->st_nbits.as<uint32_t>(), bits ? t->st_bits.as<uint32_t>() : nullptr, t->st_nframes.as<uint32_t>(),
-                            t->st_frames.as<iqd_fsk_frame>(), t->st_bytes.as<uint8_t>());
-    if (rc != IQD_OK) return rc;
-    for (const BandArg &x : args.a)
-        if (x.stage && x.out && x.bytes) HIP_COPY(e, hipMemcpyAsync(const_cast<void *>(x.ptr), x.stage->p, x.bytes, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return IQD_OK;
+    return obj_staged_run(e, args, [&] {
+        return iqd_fsk_run_device(e, t, t->st_pcm.as<const int16_t>(), row_stride, count ? t->st_count.as<const uint32_t>() : nullptr, n,
+                                  t->st_nbits.as<uint32_t>(), bits ? t->st_bits.as<uint32_t>() : nullptr, t->st_nframes.as<uint32_t>(),
+                                  t->st_frames.as<iqd_fsk_frame>(), t->st_bytes.as<uint8_t>());
+    });
 }
 
-int iqd_fsk_phase_inc(uint64_t freq_mhz, uint32_t rate_hz, uint32_t *d)
-{
-    if (!d || rate_hz == 0 || freq_mhz >= 500ull * rate_hz) return IQD_EINVAL;
-    const unsigned __int128 num = ((unsigned __int128)freq_mhz << 32) + 500ull * rate_hz;
-    *d = (uint32_t)(num / (1000ull * rate_hz));
-    return IQD_OK;
-}
+int iqd_fsk_phase_inc(uint64_t freq_mhz, uint32_t rate_hz, uint32_t *d) { return pcm_phase_inc(freq_mhz, rate_hz, d); }
 
 int iqd_fsk_afsk1200(uint32_t rate_hz, iqd_fsk_config *cfg)
 {

@@ -17,7 +17,7 @@ extern "C" {
 
 int iqd_measure_create(iqd_t *e, const iqd_measure_config *cfg, iqd_measure_t **out)
 {
-    int rc = band_create_check(e, cfg, out, __func__);
+    int rc = obj_create_check(e, cfg, out, __func__);
     if (rc != IQD_OK) return rc;
     const uint32_t n = cfg->n_bins;
     if (cfg->n_sources == 0) return e->fail(IQD_EINVAL, "iqd_measure_create: n_sources is 0");
@@ -31,7 +31,7 @@ int iqd_measure_create(iqd_t *e, const iqd_measure_config *cfg, iqd_measure_t **
         return e->fail(IQD_EINVAL, "iqd_measure_create: carrier_min_q8 (%u) must be 0 .. 256", cfg->carrier_min_q8);
     if (cfg->wide_bins == 0 || cfg->wide_bins > n + 1)
         return e->fail(IQD_EINVAL, "iqd_measure_create: wide_bins (%u) must be 1 .. n_bins + 1 (%u)", cfg->wide_bins, n + 1);
-    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
+    if ((rc = obj_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
     iqd_measure *m = new (std::nothrow) iqd_measure;
     if (!m) return IQD_ENOMEM;
     m->e = e;
@@ -40,16 +40,16 @@ int iqd_measure_create(iqd_t *e, const iqd_measure_config *cfg, iqd_measure_t **
     return IQD_OK;
 }
 
-void iqd_measure_destroy(iqd_measure_t *m) { band_destroy(m); }
+void iqd_measure_destroy(iqd_measure_t *m) { obj_destroy(m); }
 
 // the call's arrays, as run stages them ([n_sources][n_blocks] rows throughout)
-static BandArgs<4> measure_args(iqd_measure_t *m, const void *power, const void *rows, const void *slots, size_t n_blocks, void *meas)
+static ObjArgs<4> measure_args(iqd_measure_t *m, const void *power, const void *rows, const void *slots, size_t n_blocks, void *meas)
 {
     const size_t n_rows = n_blocks * m->cfg.n_sources;
-    return {{{"power", power, n_rows * m->cfg.n_bins * sizeof(uint32_t), &m->st_power, BAND_IN},
-             {"rows", rows, n_rows * sizeof(iqd_detect_row), &m->st_rows, BAND_IN},
-             {"slots", slots, n_rows * m->cfg.n_slots * sizeof(iqd_track_slot), &m->st_slots, BAND_IN},
-             {"meas", meas, n_rows * m->cfg.n_slots * sizeof(iqd_track_measure), &m->st_meas, BAND_OUT}}};
+    return {{{"power", power, n_rows * m->cfg.n_bins * sizeof(uint32_t), &m->st_power, ARG_IN},
+             {"rows", rows, n_rows * sizeof(iqd_detect_row), &m->st_rows, ARG_IN},
+             {"slots", slots, n_rows * m->cfg.n_slots * sizeof(iqd_track_slot), &m->st_slots, ARG_IN},
+             {"meas", meas, n_rows * m->cfg.n_slots * sizeof(iqd_track_measure), &m->st_meas, ARG_OUT}}};
 }
 
 int iqd_measure_run_device(iqd_measure_t *m, const uint32_t *power_dev, const iqd_detect_row *rows_dev, const iqd_track_slot *slots_dev,
@@ -57,9 +57,9 @@ int iqd_measure_run_device(iqd_measure_t *m, const uint32_t *power_dev, const iq
 {
     if (!m) return IQD_EINVAL;
     iqd_t *e = m->e;
-    const BandArgs<4> args = measure_args(m, power_dev, rows_dev, slots_dev, n_blocks, meas_dev);
+    const ObjArgs<4> args = measure_args(m, power_dev, rows_dev, slots_dev, n_blocks, meas_dev);
     int rc = band_run_check(m->e, args, n_blocks, m->cfg.n_sources, __func__);
-    if (rc == IQD_OK) rc = band_align_check(e, args, __func__);
+    if (rc == IQD_OK) rc = obj_align_check(e, args, __func__);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(e->device);
     const iqd_measure_config &c = m->cfg;
@@ -76,10 +76,10 @@ int iqd_measure_run(iqd_measure_t *m, const uint32_t *power, const iqd_detect_ro
                     iqd_track_measure *meas)
 {
     if (!m) return IQD_EINVAL;
-    const BandArgs<4> args = measure_args(m, power, rows, slots, n_blocks, meas);
+    const ObjArgs<4> args = measure_args(m, power, rows, slots, n_blocks, meas);
     int rc = band_run_check(m->e, args, n_blocks, m->cfg.n_sources, __func__);
     if (rc != IQD_OK) return rc;
-    return band_staged_run(m->e, args, [&] {
+    return obj_staged_run(m->e, args, [&] {
         return iqd_measure_run_device(m, m->st_power.as<const uint32_t>(), m->st_rows.as<const iqd_detect_row>(),
                                       m->st_slots.as<const iqd_track_slot>(), n_blocks, m->st_meas.as<iqd_track_measure>());
     });

@@ -92,7 +92,7 @@ int iqd_spectrum_full_scale(const int16_t *window, uint32_t n_bins, uint32_t *p_
 
 int iqd_spectrum_create(iqd_t *e, const iqd_spectrum_config *cfg, iqd_spectrum_t **out)
 {
-    int rc = band_create_check(e, cfg, out, __func__);
+    int rc = obj_create_check(e, cfg, out, __func__);
     if (rc != IQD_OK) return rc;
     if (cfg->n_sources == 0) return e->fail(IQD_EINVAL, "iqd_spectrum_create: n_sources is 0");
     if ((rc = band_bins_check(e, cfg->n_bins, __func__)) != IQD_OK) return rc;
@@ -100,7 +100,7 @@ int iqd_spectrum_create(iqd_t *e, const iqd_spectrum_config *cfg, iqd_spectrum_t
         return e->fail(IQD_EINVAL, "iqd_spectrum_create: sample_format IQD_WIDE_S16 is not supported (IQD_WIDE_U8 or IQD_WIDE_S8)");
     if (cfg->sample_format > IQD_WIDE_S16)
         return e->fail(IQD_EINVAL, "iqd_spectrum_create: sample_format (%u) is none of IQD_WIDE_U8, IQD_WIDE_S8", cfg->sample_format);
-    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
+    if ((rc = obj_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
     const uint32_t n = cfg->n_bins;
     if (cfg->window) {
         const int64_t bad = spectrum_window_bad(cfg->window, n);
@@ -124,21 +124,21 @@ int iqd_spectrum_create(iqd_t *e, const iqd_spectrum_config *cfg, iqd_spectrum_t
     return IQD_OK;
 }
 
-void iqd_spectrum_destroy(iqd_spectrum_t *s) { band_destroy(s); }
+void iqd_spectrum_destroy(iqd_spectrum_t *s) { obj_destroy(s); }
 
 // the call's arrays, as run stages them: [n_sources] captures in, [n_sources][n_blocks][n_bins] powers out
-static BandArgs<2> spectrum_args(iqd_spectrum_t *s, const void *wide, size_t bytes_per_source, uint32_t frames, void *power)
+static ObjArgs<2> spectrum_args(iqd_spectrum_t *s, const void *wide, size_t bytes_per_source, uint32_t frames, void *power)
 {
     const size_t n_blocks = frames ? bytes_per_source / ((size_t)2 * s->n * frames) : 0;
-    return {{{"wide", wide, (size_t)s->n_src * bytes_per_source, &s->st_in, BAND_IN},
-             {"power", power, (size_t)s->n_src * n_blocks * s->n * sizeof(uint32_t), &s->st_out, BAND_OUT}}};
+    return {{{"wide", wide, (size_t)s->n_src * bytes_per_source, &s->st_in, ARG_IN},
+             {"power", power, (size_t)s->n_src * n_blocks * s->n * sizeof(uint32_t), &s->st_out, ARG_OUT}}};
 }
 
 // a call is whole blocks of frames_per_block frames: the lengths' refusals are the spectrum's own
-static int spectrum_run_check(iqd_spectrum_t *s, const BandArgs<2> &args, size_t bytes_per_source, uint32_t frames, const char *who)
+static int spectrum_run_check(iqd_spectrum_t *s, const ObjArgs<2> &args, size_t bytes_per_source, uint32_t frames, const char *who)
 {
     iqd_t *e = s->e;
-    int rc = band_null_check(e, args, who);
+    int rc = obj_null_check(e, args, who);
     if (rc != IQD_OK) return rc;
     if (frames == 0 || frames > SPC_MAX_FRAMES) return e->fail(IQD_EINVAL, "%s: frames_per_block (%u) must be 1 .. 2^24", who, frames);
     const size_t blk = (size_t)2 * s->n * frames;
@@ -157,9 +157,9 @@ int iqd_spectrum_run_device(iqd_spectrum_t *s, const void *wide_dev, size_t byte
 {
     if (!s) return IQD_EINVAL;
     iqd_t *e = s->e;
-    const BandArgs<2> args = spectrum_args(s, wide_dev, bytes_per_source, frames_per_block, power_dev);
+    const ObjArgs<2> args = spectrum_args(s, wide_dev, bytes_per_source, frames_per_block, power_dev);
     int rc = spectrum_run_check(s, args, bytes_per_source, frames_per_block, __func__);
-    if (rc == IQD_OK) rc = band_align_check(e, args, __func__);
+    if (rc == IQD_OK) rc = obj_align_check(e, args, __func__);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(e->device);
     SpcLaunch a{};
@@ -174,10 +174,10 @@ int iqd_spectrum_run_device(iqd_spectrum_t *s, const void *wide_dev, size_t byte
 int iqd_spectrum_run(iqd_spectrum_t *s, const void *wide, size_t bytes_per_source, uint32_t frames_per_block, uint32_t *power)
 {
     if (!s) return IQD_EINVAL;
-    const BandArgs<2> args = spectrum_args(s, wide, bytes_per_source, frames_per_block, power);
+    const ObjArgs<2> args = spectrum_args(s, wide, bytes_per_source, frames_per_block, power);
     int rc = spectrum_run_check(s, args, bytes_per_source, frames_per_block, __func__);
     if (rc != IQD_OK) return rc;
-    return band_staged_run(s->e, args, [&] {
+    return obj_staged_run(s->e, args, [&] {
         return iqd_spectrum_run_device(s, s->st_in.p, bytes_per_source, frames_per_block, s->st_out.as<uint32_t>());
     });
 }

@@ -1,14 +1,14 @@
 // PCM tone bank of libiqdemod.so (include/iqdemod_tones.h: iqd_tones_*), on the engine's stream.  Kernels: iqd_tones.hip.
 // Here: the config's ranges, the coefficient tables as MFMA operands, the call's arrays and the two launches, the host-only
-// helpers; the skeleton around them is iqd_band_host.h (its argument description, create and reserved checks and destroy: the tone
-// bank is no band object, the helpers fit as they are).
-#include "iqd_band_host.h"
+// helpers; the skeleton around them is iqd_obj_host.h and its PCM part.
+#include "iqd_obj_host.h"
 #include "iqd_chan.h"
 #include "iqd_tones.h"
 #include "iqdemod_tones.h"
 
 static_assert(sizeof(iqd_tones_frame) == iqd::TON_RECORD_BYTES && sizeof(iqd_tones_state) == iqd::TON_STATE_BYTES &&
               sizeof(iqd::TonState) == iqd::TON_STATE_BYTES && sizeof(iqd_tones_config) == 72, "the ABI's records");
+static_assert(iqd::TON_MAX_N == iqd::PCM_MAX_N, "the kernels' limit of n and row_stride");
 
 struct iqd_tones {
     iqd_t *e = nullptr;
@@ -57,31 +57,15 @@ int ton_upload(iqd_t *e, DevBuf &b, const void *src, size_t bytes, const char *w
 
 size_t ton_frames(const iqd_tones *t, size_t n) { return (n + t->L - 1) / t->L; }
 
-// run's and run_device's refusals up to the counts: the engine, the NULLs in argument order, then n and row_stride
-template <size_t K>
-int ton_run_check(iqd_t *e, iqd_tones_t *t, const BandArgs<K> &args, size_t row_stride, size_t n, const char *who)
-{
-    if (e != t->e) return t->e->fail(IQD_EINVAL, "%s: t belongs to another engine", who);
-    for (const BandArg &x : args.a)
-        if (!x.ptr && x.stage) return e->fail(IQD_EINVAL, "%s: %s is NULL", who, x.name);
-    if (n > row_stride) return e->fail(IQD_EINVAL, "%s: n (%zu) is more than row_stride (%zu)", who, n, row_stride);
-    if (row_stride > TON_MAX_N) return e->fail(IQD_EINVAL, "%s: row_stride (%zu) is more than 2^31 - 1", who, row_stride);
-    return IQD_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int iqd_tones_create(iqd_t *e, const iqd_tones_config *cfg, iqd_tones_t **out)
 {
-    int rc = band_create_check(e, cfg, out, __func__);
+    int rc = pcm_create_check(e, cfg, out, IQD_TONES_ABI_VERSION, __func__);
     if (rc != IQD_OK) return rc;
     const uint32_t L = cfg->frame_len, T = cfg->n_tones;
-    if (cfg->abi_version != IQD_TONES_ABI_VERSION)
-        return e->fail(IQD_EINVAL, "iqd_tones_create: abi_version (%u) must be %u", cfg->abi_version, IQD_TONES_ABI_VERSION);
-    if (cfg->n_channels == 0 || cfg->n_channels > (1u << 20))
-        return e->fail(IQD_EINVAL, "iqd_tones_create: n_channels (%u) must be 1 .. 2^20", cfg->n_channels);
     if (L < TON_MIN_L || L > TON_MAX_L || L % 32) return e->fail(IQD_EINVAL, "iqd_tones_create: frame_len (%u) must be a multiple of 32, 32 .. 8192", L);
     if (T == 0 || T > TON_MAX_T) return e->fail(IQD_EINVAL, "iqd_tones_create: n_tones (%u) must be 1 .. 64", T);
     if (!cfg->phase_inc) return e->fail(IQD_EINVAL, "iqd_tones_create: phase_inc is NULL");
@@ -91,7 +75,7 @@ int iqd_tones_create(iqd_t *e, const iqd_tones_config *cfg, iqd_tones_t **out)
     if (cfg->energy_q8 > (1u << 20)) return e->fail(IQD_EINVAL, "iqd_tones_create: energy_q8 (%u) must be 0 .. 2^20", cfg->energy_q8);
     if (cfg->open < 1 || cfg->open > 255) return e->fail(IQD_EINVAL, "iqd_tones_create: open (%u) must be 1 .. 255", cfg->open);
     if (cfg->hold > 255) return e->fail(IQD_EINVAL, "iqd_tones_create: hold (%u) must be 0 .. 255", cfg->hold);
-    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
+    if ((rc = obj_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
 
     std::vector<int16_t> phasor(8192), w(L);
     chz_phasor_table(phasor.data());
@@ -123,7 +107,7 @@ int iqd_tones_create(iqd_t *e, const iqd_tones_config *cfg, iqd_tones_t **out)
     return IQD_OK;
 }
 
-void iqd_tones_destroy(iqd_tones_t *t) { band_destroy(t); }
+void iqd_tones_destroy(iqd_tones_t *t) { obj_destroy(t); }
 
 // the cleared state: tone = cand = -1, the rest 0 (the open frame's samples need no clearing: fill = 0)
 int iqd_tones_reset(iqd_tones_t *t)
@@ -139,39 +123,29 @@ size_t iqd_tones_max_frames(const iqd_tones_t *t, size_t n) { return t ? ton_fra
 
 int iqd_tones_get_state(iqd_tones_t *t, uint32_t channel, iqd_tones_state *state)
 {
-    if (!t) return IQD_EINVAL;
-    iqd_t *e = t->e;
-    if (!state) return e->fail(IQD_EINVAL, "iqd_tones_get_state: state is NULL");
-    if (channel >= t->n_channels) return e->fail(IQD_EINVAL, "iqd_tones_get_state: channel (%u) must be below n_channels (%u)", channel, t->n_channels);
-    (void)hipSetDevice(e->device);
-    HIP_COPY(e, hipMemcpyAsync(state, t->state.as<TonState>() + channel, sizeof(TonState), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return IQD_OK;
+    return t ? pcm_get_state(t->e, t->state.as<TonState>(), t->n_channels, channel, state, __func__) : IQD_EINVAL;
 }
 
-// the call's arrays, as run stages them; count and power may be NULL (no staging buffer named: not checked, not copied)
-static BandArgs<5> tones_args(iqd_tones_t *t, const void *pcm, size_t row_stride, const void *count, size_t n, void *n_frames, void *frames,
-                              void *power)
+// the call's arrays, as run stages them and run_device wants them aligned; count and power may be left out
+static ObjArgs<5> tones_args(iqd_tones_t *t, const void *pcm, size_t row_stride, const void *count, size_t n, void *n_frames, void *frames,
+                             void *power)
 {
     const size_t C = t->n_channels, F = ton_frames(t, n);
-    return {{{"pcm", pcm, C * row_stride * sizeof(int16_t), &t->st_pcm, BAND_IN},
-             {"count", count, C * sizeof(uint32_t), count ? &t->st_count : nullptr, BAND_IN},
-             {"n_frames", n_frames, C * sizeof(uint32_t), &t->st_nframes, BAND_OUT},
-             {"frames", frames, C * F * sizeof(iqd_tones_frame), &t->st_frames, BAND_OUT},
-             {"power", power, C * F * t->T * sizeof(uint64_t), power ? &t->st_power : nullptr, BAND_OUT}}};
+    return {{{"pcm", pcm, C * row_stride * sizeof(int16_t), &t->st_pcm, ARG_IN, 2},
+             {"count", count, C * sizeof(uint32_t), &t->st_count, ARG_IN, 4, ARG_OPTIONAL},
+             {"n_frames", n_frames, C * sizeof(uint32_t), &t->st_nframes, ARG_OUT, 4},
+             {"frames", frames, C * F * sizeof(iqd_tones_frame), &t->st_frames, ARG_OUT},
+             {"power", power, C * F * t->T * sizeof(uint64_t), &t->st_power, ARG_OUT, 16, ARG_OPTIONAL}}};
 }
 
 int iqd_tones_run_device(iqd_t *e, iqd_tones_t *t, const int16_t *pcm_dev, size_t row_stride, const uint32_t *count_dev, size_t n,
                          uint32_t *n_frames_dev, iqd_tones_frame *frames_dev, uint64_t *power_dev)
 {
     if (!t) return IQD_EINVAL;
-    const BandArgs<5> args = tones_args(t, pcm_dev, row_stride, count_dev, n, n_frames_dev, frames_dev, power_dev);
-    int rc = ton_run_check(e, t, args, row_stride, n, __func__);
+    const ObjArgs<5> args = tones_args(t, pcm_dev, row_stride, count_dev, n, n_frames_dev, frames_dev, power_dev);
+    int rc = pcm_run_check(e, t->e, args, row_stride, n, __func__);
+    if (rc == IQD_OK) rc = obj_align_check(e, args, __func__);
     if (rc != IQD_OK) return rc;
-    const size_t align[5] = {2, 4, 4, 16, 16};
-    for (size_t i = 0; i < 5; i++)
-        if ((uintptr_t)args.a[i].ptr % align[i])
-            return e->fail(IQD_EINVAL, "iqd_tones_run_device: %s_dev is not %zu-byte aligned", args.a[i].name, align[i]);
     (void)hipSetDevice(e->device);
     TonLaunch a{};
     a.amat = t->amat.as<const uint4>(); a.gsum = t->gsum.as<const int32_t>(); a.state = t->state.as<TonState>(); a.open = t->frame.as<int16_t>();
@@ -188,32 +162,16 @@ int iqd_tones_run(iqd_t *e, iqd_tones_t *t, const int16_t *pcm, size_t row_strid
                   iqd_tones_frame *frames, uint64_t *power)
 {
     if (!t) return IQD_EINVAL;
-    const BandArgs<5> args = tones_args(t, pcm, row_stride, count, n, n_frames, frames, power);
-    int rc = ton_run_check(e, t, args, row_stride, n, __func__);
+    const ObjArgs<5> args = tones_args(t, pcm, row_stride, count, n, n_frames, frames, power);
+    int rc = pcm_run_check(e, t->e, args, row_stride, n, __func__);
     if (rc != IQD_OK) return rc;
-    // band_staged_run's order with the arrays the caller leaves out skipped: every staging buffer first (an empty array's too,
-    // so that run_device gets a pointer), the inputs, the launches, the outputs, the wait
-    (void)hipSetDevice(e->device);
-    for (const BandArg &x : args.a)
-        if (x.stage) HIP_TRY(e, x.stage->ensure(std::max<size_t>(x.bytes, 16)));
-    for (const BandArg &x : args.a)
-        if (x.stage && !x.out && x.bytes) HIP_COPY(e, hipMemcpyAsync(x.stage->p, x.ptr, x.bytes, hipMemcpyHostToDevice, e->stream));
-    rc = iqd_tones_run_device(e, t, t->st_pcm.as<const int16_t>(), row_stride, count ? t->st_count.as<const uint32_t>() : nullptr, n,
-                              t->st_nframes.as<uint32_t>(), t->st_frames.as<iqd_tones_frame>(), power ? t->st_power.as<uint64_t>() : nullptr);
-    if (rc != IQD_OK) return rc;
-    for (const BandArg &x : args.a)
-        if (x.stage && x.out && x.bytes) HIP_COPY(e, hipMemcpyAsync(const_cast<void *>(x.ptr), x.stage->p, x.bytes, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return IQD_OK;
+    return obj_staged_run(e, args, [&] {
+        return iqd_tones_run_device(e, t, t->st_pcm.as<const int16_t>(), row_stride, count ? t->st_count.as<const uint32_t>() : nullptr, n,
+                                    t->st_nframes.as<uint32_t>(), t->st_frames.as<iqd_tones_frame>(), power ? t->st_power.as<uint64_t>() : nullptr);
+    });
 }
 
-int iqd_tones_phase_inc(uint64_t freq_mhz, uint32_t rate_hz, uint32_t *d)
-{
-    if (!d || rate_hz == 0 || freq_mhz >= 500ull * rate_hz) return IQD_EINVAL;
-    const unsigned __int128 num = ((unsigned __int128)freq_mhz << 32) + 500ull * rate_hz;
-    *d = (uint32_t)(num / (1000ull * rate_hz));
-    return IQD_OK;
-}
+int iqd_tones_phase_inc(uint64_t freq_mhz, uint32_t rate_hz, uint32_t *d) { return pcm_phase_inc(freq_mhz, rate_hz, d); }
 
 int iqd_tones_default_window(uint32_t frame_len, int16_t *window)
 {

@@ -1,7 +1,7 @@
 // iqd_tool_chain.h — what the command-line tools share of their dealings with the library (the C ABI only): owning handles,
 // so that every way out of a tool destroys what it made, in reverse order; and the band chain - spectrum, detector, tracker,
-// measurements, track log - with its device arrays and one call's run_device sequence.  A new band object is one member of
-// BandChain.
+// measurements, track log - with its device arrays and one call's run_device sequence (a new band object is one member of
+// BandChain); and what the tools behind a demodulator share: their engine, their PCM input and their tail.
 #pragma once
 #include "iqd_tool.h"
 
@@ -28,6 +28,57 @@ inline int createEngine(Engine &e, uint32_t n_channels, uint32_t block_bytes = 0
   cfg.block_bytes = block_bytes;
   cfg.device = -1;
   return iqd_create(&cfg, &e.p);
+}
+
+// ... as the tools that take PCM make it (iqdemod_tones, iqdemod_fsk), with their line where there is no device
+inline bool createPcmEngine(Engine &e, const char *tool)
+{
+  const int rc = createEngine(e, 1);
+  if (rc != IQD_OK) fprintf(stderr, "%s: iqd_create: %s\n", tool, iqd_strerror(rc));
+  return rc == IQD_OK;
+}
+
+// The PCM those tools read: from stdin (channels = 0) or from the files of a pattern with one %d, chunk samples per channel and call
+struct PcmInput {
+  std::vector<FILE *> fin;
+  std::vector<int16_t> pcm;
+  std::vector<uint32_t> count;
+  size_t chunk = 0;
+  bool more = true;
+
+  // also(c) opens what else the tool keeps per channel, right behind the channel's input; false: Files has said what did not open
+  template <class Also> bool open(Files &files, const std::string &pattern, uint32_t channels, size_t chunkSamples, Also also)
+  {
+    const uint32_t n = channels ? channels : 1;
+    chunk = chunkSamples;
+    for (uint32_t c = 0; c < n; c++) {
+      fin.push_back(channels ? files.open(channelName(pattern, c), "rb", Files::Named) : stdin);
+      if (!fin.back() || !also(c)) return false;
+    }
+    pcm.resize((size_t)n * chunk);
+    count.resize(n);
+    return true;
+  }
+  // every channel gives what it has: a channel that has ended counts 0 from then on; got, the call's n, is the longest read.
+  // False: nothing is left (a short call was the last)
+  bool read(size_t &got)
+  {
+    got = 0;
+    for (size_t c = 0; more && c < fin.size(); c++) {
+      const size_t r = fread(pcm.data() + c * chunk, sizeof(int16_t), chunk, fin[c]);
+      count[c] = (uint32_t)r;
+      if (r > got) got = r;
+    }
+    more = got == chunk;
+    return got != 0;
+  }
+};
+
+// the tail of those tools: what went to stdout or to the files is out, or the status, if still 0, is 1
+inline int closeOutputs(Files &files, int status)
+{
+  const bool flushed = fflush(stdout) == 0;
+  return (!files.close() || !flushed) && status == 0 ? 1 : status;
 }
 
 // n elements of T in device memory (Free = iqd_dev_free) or in page-locked host memory (iqd_host_free)

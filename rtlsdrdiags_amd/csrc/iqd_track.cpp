@@ -27,7 +27,7 @@ int iqd_track_phase_inc(uint32_t n_bins, uint32_t centroid_q8, uint32_t inc_bias
 
 int iqd_track_create(iqd_t *e, const iqd_track_config *cfg, iqd_track_t **out)
 {
-    int rc = band_create_check(e, cfg, out, __func__);
+    int rc = obj_create_check(e, cfg, out, __func__);
     if (rc != IQD_OK) return rc;
     const uint32_t n = cfg->n_bins;
     if (cfg->n_sources == 0) return e->fail(IQD_EINVAL, "iqd_track_create: n_sources is 0");
@@ -42,7 +42,7 @@ int iqd_track_create(iqd_t *e, const iqd_track_config *cfg, iqd_track_t **out)
     const uint32_t *ce = cfg->class_edge;
     if (ce[0] < 1 || ce[0] > ce[1] || ce[1] > ce[2] || ce[2] > n + 1)
         return e->fail(IQD_EINVAL, "iqd_track_create: class_edge (%u, %u, %u) must be 1 <= e0 <= e1 <= e2 <= n_bins + 1 (%u)", ce[0], ce[1], ce[2], n + 1);
-    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
+    if ((rc = obj_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
     iqd_track *t = new (std::nothrow) iqd_track;
     if (!t) return IQD_ENOMEM;
     t->e = e;
@@ -52,18 +52,18 @@ int iqd_track_create(iqd_t *e, const iqd_track_config *cfg, iqd_track_t **out)
     return rc;
 }
 
-void iqd_track_destroy(iqd_track_t *t) { band_destroy(t); }
+void iqd_track_destroy(iqd_track_t *t) { obj_destroy(t); }
 
 int iqd_track_reset(iqd_track_t *t) { return t ? t->state.reset(t->e) : IQD_EINVAL; }
 
 // the call's arrays, as run stages them ([n_sources][n_blocks] rows throughout)
-static BandArgs<4> track_args(iqd_track_t *t, const void *rows, const void *det, size_t n_blocks, void *slots, void *blocks)
+static ObjArgs<4> track_args(iqd_track_t *t, const void *rows, const void *det, size_t n_blocks, void *slots, void *blocks)
 {
     const size_t n_rows = n_blocks * t->cfg.n_sources;
-    return {{{"rows", rows, n_rows * sizeof(iqd_detect_row), &t->st_rows, BAND_IN},
-             {"det", det, n_rows * t->cfg.max_detections * sizeof(iqd_detection), &t->st_det, BAND_IN},
-             {"slots", slots, n_rows * t->cfg.n_slots * sizeof(iqd_track_slot), &t->st_slots, BAND_OUT},
-             {"blocks", blocks, n_rows * sizeof(iqd_track_block), &t->st_blocks, BAND_OUT}}};
+    return {{{"rows", rows, n_rows * sizeof(iqd_detect_row), &t->st_rows, ARG_IN},
+             {"det", det, n_rows * t->cfg.max_detections * sizeof(iqd_detection), &t->st_det, ARG_IN},
+             {"slots", slots, n_rows * t->cfg.n_slots * sizeof(iqd_track_slot), &t->st_slots, ARG_OUT},
+             {"blocks", blocks, n_rows * sizeof(iqd_track_block), &t->st_blocks, ARG_OUT}}};
 }
 
 int iqd_track_run_device(iqd_track_t *t, const iqd_detect_row *rows_dev, const iqd_detection *det_dev, size_t n_blocks,
@@ -71,9 +71,9 @@ int iqd_track_run_device(iqd_track_t *t, const iqd_detect_row *rows_dev, const i
 {
     if (!t) return IQD_EINVAL;
     iqd_t *e = t->e;
-    const BandArgs<4> args = track_args(t, rows_dev, det_dev, n_blocks, slots_dev, blocks_dev);
+    const ObjArgs<4> args = track_args(t, rows_dev, det_dev, n_blocks, slots_dev, blocks_dev);
     int rc = band_run_check(t->e, args, n_blocks, t->cfg.n_sources, __func__);
-    if (rc == IQD_OK) rc = band_align_check(e, args, __func__);
+    if (rc == IQD_OK) rc = obj_align_check(e, args, __func__);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(e->device);
     const iqd_track_config &c = t->cfg;
@@ -91,10 +91,10 @@ int iqd_track_run(iqd_track_t *t, const iqd_detect_row *rows, const iqd_detectio
                   iqd_track_block *blocks)
 {
     if (!t) return IQD_EINVAL;
-    const BandArgs<4> args = track_args(t, rows, det, n_blocks, slots, blocks);
+    const ObjArgs<4> args = track_args(t, rows, det, n_blocks, slots, blocks);
     int rc = band_run_check(t->e, args, n_blocks, t->cfg.n_sources, __func__);
     if (rc != IQD_OK) return rc;
-    return band_staged_run(t->e, args, [&] {
+    return obj_staged_run(t->e, args, [&] {
         return iqd_track_run_device(t, t->st_rows.as<const iqd_detect_row>(), t->st_det.as<const iqd_detection>(), n_blocks,
                                     t->st_slots.as<iqd_track_slot>(), t->st_blocks.as<iqd_track_block>());
     });

@@ -25,7 +25,7 @@ int iqd_tracklog_mean_centre(uint64_t sum_centre_q8, uint32_t n_active, uint32_t
 
 int iqd_tracklog_create(iqd_t *e, const iqd_tracklog_config *cfg, iqd_tracklog_t **out)
 {
-    int rc = band_create_check(e, cfg, out, __func__);
+    int rc = obj_create_check(e, cfg, out, __func__);
     if (rc != IQD_OK) return rc;
     if (cfg->n_sources == 0) return e->fail(IQD_EINVAL, "iqd_tracklog_create: n_sources is 0");
     if (cfg->n_slots == 0 || cfg->n_slots > TLG_MAX_SLOTS) return e->fail(IQD_EINVAL, "iqd_tracklog_create: n_slots (%u) must be 1 .. 64", cfg->n_slots);
@@ -35,7 +35,7 @@ int iqd_tracklog_create(iqd_t *e, const iqd_tracklog_config *cfg, iqd_tracklog_t
         return e->fail(IQD_EINVAL, "iqd_tracklog_create: min_active (%u) must be 1 .. 65535", cfg->min_active);
     if (cfg->vote_min == 0 || cfg->vote_min > TLG_MAX_VOTE_MIN)
         return e->fail(IQD_EINVAL, "iqd_tracklog_create: vote_min (%u) must be 1 .. 65535", cfg->vote_min);
-    if ((rc = band_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
+    if ((rc = obj_reserved_check(e, cfg->reserved, __func__)) != IQD_OK) return rc;
     iqd_tracklog *t = new (std::nothrow) iqd_tracklog;
     if (!t) return IQD_ENOMEM;
     t->e = e;
@@ -45,20 +45,20 @@ int iqd_tracklog_create(iqd_t *e, const iqd_tracklog_config *cfg, iqd_tracklog_t
     return rc;
 }
 
-void iqd_tracklog_destroy(iqd_tracklog_t *t) { band_destroy(t); }
+void iqd_tracklog_destroy(iqd_tracklog_t *t) { obj_destroy(t); }
 
 int iqd_tracklog_reset(iqd_tracklog_t *t) { return t ? t->state.reset(t->e) : IQD_EINVAL; }
 
 // the call's arrays, as run stages them: [n_sources][n_blocks][S] entries in and out, the events and counts per source
-static BandArgs<5> tracklog_args(iqd_tracklog_t *t, const void *slots, const void *meas, size_t n_blocks, void *summary, void *events, void *counts)
+static ObjArgs<5> tracklog_args(iqd_tracklog_t *t, const void *slots, const void *meas, size_t n_blocks, void *summary, void *events, void *counts)
 {
     const iqd_tracklog_config &c = t->cfg;
     const size_t n_entries = n_blocks * c.n_sources * c.n_slots;
-    return {{{"slots", slots, n_entries * sizeof(iqd_track_slot), &t->st_slots, BAND_IN},
-             {"meas", meas, n_entries * sizeof(iqd_track_measure), &t->st_meas, BAND_IN},
-             {"summary", summary, n_entries * sizeof(iqd_track_summary), &t->st_summary, BAND_OUT},
-             {"events", events, (size_t)c.n_sources * c.max_events * sizeof(iqd_track_summary), &t->st_events, BAND_OUT},
-             {"counts", counts, (size_t)c.n_sources * sizeof(iqd_tracklog_counts), &t->st_counts, BAND_OUT}}};
+    return {{{"slots", slots, n_entries * sizeof(iqd_track_slot), &t->st_slots, ARG_IN},
+             {"meas", meas, n_entries * sizeof(iqd_track_measure), &t->st_meas, ARG_IN},
+             {"summary", summary, n_entries * sizeof(iqd_track_summary), &t->st_summary, ARG_OUT},
+             {"events", events, (size_t)c.n_sources * c.max_events * sizeof(iqd_track_summary), &t->st_events, ARG_OUT},
+             {"counts", counts, (size_t)c.n_sources * sizeof(iqd_tracklog_counts), &t->st_counts, ARG_OUT}}};
 }
 
 int iqd_tracklog_run_device(iqd_tracklog_t *t, const iqd_track_slot *slots_dev, const iqd_track_measure *meas_dev, size_t n_blocks,
@@ -66,9 +66,9 @@ int iqd_tracklog_run_device(iqd_tracklog_t *t, const iqd_track_slot *slots_dev, 
 {
     if (!t) return IQD_EINVAL;
     iqd_t *e = t->e;
-    const BandArgs<5> args = tracklog_args(t, slots_dev, meas_dev, n_blocks, summary_dev, events_dev, counts_dev);
+    const ObjArgs<5> args = tracklog_args(t, slots_dev, meas_dev, n_blocks, summary_dev, events_dev, counts_dev);
     int rc = band_run_check(t->e, args, n_blocks, t->cfg.n_sources, __func__);
-    if (rc == IQD_OK) rc = band_align_check(e, args, __func__);
+    if (rc == IQD_OK) rc = obj_align_check(e, args, __func__);
     if (rc != IQD_OK) return rc;
     (void)hipSetDevice(e->device);
     const iqd_tracklog_config &c = t->cfg;
@@ -85,10 +85,10 @@ int iqd_tracklog_run(iqd_tracklog_t *t, const iqd_track_slot *slots, const iqd_t
                      iqd_track_summary *events, iqd_tracklog_counts *counts)
 {
     if (!t) return IQD_EINVAL;
-    const BandArgs<5> args = tracklog_args(t, slots, meas, n_blocks, summary, events, counts);
+    const ObjArgs<5> args = tracklog_args(t, slots, meas, n_blocks, summary, events, counts);
     int rc = band_run_check(t->e, args, n_blocks, t->cfg.n_sources, __func__);
     if (rc != IQD_OK) return rc;
-    return band_staged_run(t->e, args, [&] {
+    return obj_staged_run(t->e, args, [&] {
         return iqd_tracklog_run_device(t, t->st_slots.as<const iqd_track_slot>(), t->st_meas.as<const iqd_track_measure>(), n_blocks,
                                        t->st_summary.as<iqd_track_summary>(), t->st_events.as<iqd_track_summary>(),
                                        t->st_counts.as<iqd_tracklog_counts>());

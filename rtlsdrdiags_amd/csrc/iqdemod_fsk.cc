@@ -92,20 +92,17 @@ int main(int argc, char **argv)
   const uint32_t n = fromFiles ? channels : 1;
 
   Files files(TOOL);
-  std::vector<FILE *> fin(n, nullptr), fbits(n, nullptr);
-  for (uint32_t c = 0; c < n; c++) {
-    if (!(fin[c] = fromFiles ? files.open(channelName(in, c), "rb", Files::Named) : stdin)) return 1;
-    if (!bitsName.empty() && !(fbits[c] = files.open(fromFiles ? channelName(bitsName, c) : bitsName, "w", Files::Named))) return 1;
-  }
+  std::vector<FILE *> fbits(n, nullptr);
+  PcmInput input;
+  if (!input.open(files, in, channels, chunk, [&](uint32_t c) {
+        return bitsName.empty() || (fbits[c] = files.open(fromFiles ? channelName(bitsName, c) : bitsName, "w", Files::Named));
+      }))
+    return 1;
   FILE *out = log.empty() ? stdout : files.open(log, "w", Files::Named);
   if (!out) return 1;
 
   Engine e;
-  int rc = createEngine(e, 1);
-  if (rc != IQD_OK) {
-    fprintf(stderr, "iqdemod_fsk: iqd_create: %s\n", iqd_strerror(rc));
-    return 1;
-  }
+  if (!createPcmEngine(e, TOOL)) return 1;
   cfg.abi_version = IQD_FSK_ABI_VERSION;
   cfg.n_channels = n;
   cfg.corr_len = corr;
@@ -114,30 +111,20 @@ int main(int argc, char **argv)
   cfg.min_len = minlen;
   cfg.max_len = maxlen;
   Handle<iqd_fsk_t, iqd_fsk_destroy> modem;
-  rc = iqd_fsk_create(e, &cfg, &modem.p);
+  int rc = iqd_fsk_create(e, &cfg, &modem.p);
   if (rc != IQD_OK) {
     fprintf(stderr, "iqdemod_fsk: iqd_fsk_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
     return 1;
   }
 
-  std::vector<int16_t> pcm((size_t)n * chunk);
-  std::vector<uint32_t> count(n), nBits(n), nFrames(n);
+  std::vector<uint32_t> nBits(n), nFrames(n);
   std::vector<uint32_t> bits((size_t)n * iqd_fsk_max_bit_words(modem, chunk));
   std::vector<iqd_fsk_frame> frames((size_t)n * iqd_fsk_max_frames(modem, chunk));
   std::vector<uint8_t> bytes((size_t)n * iqd_fsk_max_bytes(modem, chunk));
   int status = 0;
-  for (bool more = true; more && status == 0;) {
-    // every channel gives what it has: a channel that has ended counts 0 from then on; the call's n is the longest read
-    size_t got = 0;
-    for (uint32_t c = 0; c < n; c++) {
-      const size_t r = fread(pcm.data() + (size_t)c * chunk, sizeof(int16_t), chunk, fin[c]);
-      count[c] = (uint32_t)r;
-      if (r > got) got = r;
-    }
-    if (got == 0) break;
-    more = got == chunk;
+  for (size_t got; status == 0 && input.read(got);) {
     const size_t F = iqd_fsk_max_frames(modem, got), Bw = iqd_fsk_max_bit_words(modem, got), Bc = iqd_fsk_max_bytes(modem, got);
-    rc = iqd_fsk_run(e, modem, pcm.data(), chunk, count.data(), got, nBits.data(), bitsName.empty() ? nullptr : bits.data(), nFrames.data(),
+    rc = iqd_fsk_run(e, modem, input.pcm.data(), chunk, input.count.data(), got, nBits.data(), bitsName.empty() ? nullptr : bits.data(), nFrames.data(),
                      frames.data(), bytes.data());
     if (rc != IQD_OK) {
       fprintf(stderr, "iqdemod_fsk: iqd_fsk_run: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
@@ -156,7 +143,5 @@ int main(int argc, char **argv)
       }
     }
   }
-  const bool flushed = fflush(stdout) == 0;
-  if ((!files.close() || !flushed) && status == 0) status = 1;
-  return status;
+  return closeOutputs(files, status);
 }

@@ -71,48 +71,33 @@ int main(int argc, char **argv)
   const uint32_t n = fromFiles ? channels : 1;
 
   Files files(TOOL);
-  std::vector<FILE *> fin(n, nullptr);
-  for (uint32_t c = 0; c < n; c++)
-    if (!(fin[c] = fromFiles ? files.open(channelName(in, c), "rb", Files::Named) : stdin)) return 1;
+  PcmInput input;
+  if (!input.open(files, in, channels, chunk, [](uint32_t) { return true; })) return 1;
   FILE *out = log.empty() ? stdout : files.open(log, "w", Files::Named);
   if (!out) return 1;
 
   Engine e;
-  int rc = createEngine(e, 1);
-  if (rc != IQD_OK) {
-    fprintf(stderr, "iqdemod_tones: iqd_create: %s\n", iqd_strerror(rc));
-    return 1;
-  }
+  if (!createPcmEngine(e, TOOL)) return 1;
   cfg.abi_version = IQD_TONES_ABI_VERSION;
   cfg.n_channels = n;
   cfg.n_tones = (uint32_t)inc.size();
   cfg.phase_inc = inc.data();
   Handle<iqd_tones_t, iqd_tones_destroy> bank;
-  rc = iqd_tones_create(e, &cfg, &bank.p);
+  int rc = iqd_tones_create(e, &cfg, &bank.p);
   if (rc != IQD_OK) {
     fprintf(stderr, "iqdemod_tones: iqd_tones_create: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
     return 1;
   }
 
   const size_t maxFrames = iqd_tones_max_frames(bank, chunk);
-  std::vector<int16_t> pcm((size_t)n * chunk);
-  std::vector<uint32_t> count(n), done(n);
+  std::vector<uint32_t> done(n);
   std::vector<iqd_tones_frame> frames((size_t)n * (maxFrames ? maxFrames : 1));
   std::vector<uint64_t> seen(n, 0);      // frames of the channel so far
   std::vector<int32_t> tone(n, -1);      // the tone in force
   int status = 0;
-  for (bool more = true; more && status == 0;) {
-    // every channel gives what it has: a channel that has ended counts 0 from then on; the call's n is the longest read
-    size_t got = 0;
-    for (uint32_t c = 0; c < n; c++) {
-      const size_t r = fread(pcm.data() + (size_t)c * chunk, sizeof(int16_t), chunk, fin[c]);
-      count[c] = (uint32_t)r;
-      if (r > got) got = r;
-    }
-    if (got == 0) break;
-    more = got == chunk;
+  for (size_t got; status == 0 && input.read(got);) {
     const size_t F = iqd_tones_max_frames(bank, got);
-    rc = iqd_tones_run(e, bank, pcm.data(), chunk, count.data(), got, done.data(), frames.data(), nullptr);
+    rc = iqd_tones_run(e, bank, input.pcm.data(), chunk, input.count.data(), got, done.data(), frames.data(), nullptr);
     if (rc != IQD_OK) {
       fprintf(stderr, "iqdemod_tones: iqd_tones_run: %s: %s\n", iqd_strerror(rc), iqd_last_error(e));
       status = 3;
@@ -132,6 +117,5 @@ int main(int argc, char **argv)
         tone[c] = r.tone;
       }
   }
-  if ((log.empty() ? fflush(stdout) != 0 : !files.close()) && status == 0) status = 1;
-  return status;
+  return closeOutputs(files, status);
 }

@@ -43,23 +43,16 @@ PROTOTYPES = {
     "iqd_fsk_afsk1200": (_int, (_u32, _P(FskConfig))),
 }
 
-_BOUND = None
-
 
 def _lib():
     """capi's library with this table's prototypes set (once)"""
-    global _BOUND
-    if _BOUND is None:
-        _BOUND = capi._bind(capi._lib(), PROTOTYPES)
-    return _BOUND
+    return capi._addon_lib(PROTOTYPES)
 
 
 def phase_inc(freq_mhz, rate_hz):
     """iqd_fsk_phase_inc (host only): a tone's phase increment from its frequency in millihertz (a bit clock's from the baud
     rate in thousandths) and the PCM rate in Hz"""
-    _lib()
-    return capi._u32_function("iqd_fsk_phase_inc", C.c_uint32(), (freq_mhz, rate_hz),
-                              "iqd_fsk_phase_inc: freq_mhz %r must be below 500 rate_hz (%r), rate_hz not 0" % (freq_mhz, rate_hz), bits=64)
+    return capi._addon_phase_inc(PROTOTYPES, "fsk", freq_mhz, rate_hz)
 
 
 def afsk1200(rate_hz):
@@ -73,10 +66,12 @@ def afsk1200(rate_hz):
                 flags=cfg.flags, min_len=cfg.min_len, max_len=cfg.max_len)
 
 
-class Fsk(capi._EngineChild):
+class Fsk(capi._PcmChild):
     """iqd_fsk_*: per channel the decisions of two corr_len-tap tone correlators, a bit clock that follows their transitions,
     NRZI and an HDLC deframer with the CRC-16/X.25 check; a call gives the bits and the good frames it completed.  State is
-    carried from call to call until reset()."""
+    carried from call to call until reset().  state(channel): dict(samples, ph, prev, last, ones, in_frame, nbits, bad_fcs,
+    frames_total)."""
+    _State = FskState
 
     def __init__(self, engine, n_channels, mark_inc, space_inc, baud_inc, corr_len=8, loop_shift=3, flags=NRZI, window=None, min_len=17,
                  max_len=512, reserved=(0, 0, 0, 0), abi_version=ABI_VERSION):
@@ -107,11 +102,8 @@ class Fsk(capi._EngineChild):
         """pcm [n_channels, row_stride] int16 (a host array), the first n samples of each row (count: [n_channels] uint32, fewer
         for some) -> (n_bits [n_channels] uint32, bits [n_channels, Bw] uint32 or None, n_frames [n_channels] uint32,
         frames [n_channels, F] FSK_FRAME, bytes [n_channels, Bc] uint8); synchronises."""
-        pcm = np.ascontiguousarray(pcm, np.int16).reshape(self.n_channels, -1)
-        stride = pcm.shape[1]
-        n = stride if n is None else int(n)
+        pcm, stride, n, count = self._rows(pcm, n, count)
         F, Bw, Bc = self.max_frames(max(n, 0)), self.max_bit_words(max(n, 0)), self.max_bytes(max(n, 0))
-        count = None if count is None else np.ascontiguousarray(count, np.uint32)
         nb, nf = np.zeros(self.n_channels, np.uint32), np.zeros(self.n_channels, np.uint32)
         bits = np.zeros((self.n_channels, Bw), np.uint32) if want_bits else None
         frames = np.zeros((self.n_channels, F), FSK_FRAME)
@@ -123,23 +115,8 @@ class Fsk(capi._EngineChild):
 
     def run_device(self, pcm_dev, row_stride, n, n_bits_dev, n_frames_dev, frames_dev, bytes_dev, bits_dev=0, count_dev=0, engine=None):
         """iqd_fsk_run_device: device pointers (integers), queued on the engine's stream."""
-        e = self._e if engine is None else engine
-        self._e._check(self._L.iqd_fsk_run_device(e._h, self._h, _dev_ptr(pcm_dev), int(row_stride), _dev_ptr(count_dev), int(n),
-                                                  _dev_ptr(n_bits_dev), _dev_ptr(bits_dev), _dev_ptr(n_frames_dev), _dev_ptr(frames_dev),
-                                                  _dev_ptr(bytes_dev)))
-
-    def reset(self):
-        """iqd_fsk_reset: every channel's carried samples, clock, deframer and counters cleared."""
-        self._e._check(self._L.iqd_fsk_reset(self._h))
-
-    def state(self, channel=0):
-        """iqd_fsk_get_state: dict(samples, ph, prev, last, ones, in_frame, nbits, bad_fcs, frames_total) of one channel;
-        synchronises."""
-        s = FskState()
-        if not 0 <= int(channel) <= 0xffffffff:
-            raise IqdError(-1, "iqd_fsk_get_state: channel %r out of range" % (channel,))
-        self._e._check(self._L.iqd_fsk_get_state(self._h, int(channel), C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in FskState._fields_}
+        self._run_device(engine, _dev_ptr(pcm_dev), int(row_stride), _dev_ptr(count_dev), int(n), _dev_ptr(n_bits_dev), _dev_ptr(bits_dev),
+                         _dev_ptr(n_frames_dev), _dev_ptr(frames_dev), _dev_ptr(bytes_dev))
 
 
 def frames_of(n_frames, frames, data):

@@ -45,22 +45,15 @@ PROTOTYPES = {
     "iqd_tones_dtmf": (_int, (_vp,)),
 }
 
-_BOUND = None
-
 
 def _lib():
     """capi's library with this table's prototypes set (once)"""
-    global _BOUND
-    if _BOUND is None:
-        _BOUND = capi._bind(capi._lib(), PROTOTYPES)
-    return _BOUND
+    return capi._addon_lib(PROTOTYPES)
 
 
 def phase_inc(freq_mhz, rate_hz):
     """iqd_tones_phase_inc (host only): a tone's phase increment from its frequency in millihertz and the PCM rate in Hz"""
-    _lib()
-    return capi._u32_function("iqd_tones_phase_inc", C.c_uint32(), (freq_mhz, rate_hz),
-                              "iqd_tones_phase_inc: freq_mhz %r must be below 500 rate_hz (%r), rate_hz not 0" % (freq_mhz, rate_hz), bits=64)
+    return capi._addon_phase_inc(PROTOTYPES, "tones", freq_mhz, rate_hz)
 
 
 def default_window(frame_len):
@@ -88,10 +81,12 @@ def dtmf_mhz():
 CTCSS_DEFAULTS = dict(frame_len=4096, ratio_q8=512, open=2, hold=1, energy_q8=0, min_power=0)   # DESIGN 4.17 has the why
 
 
-class Tones(capi._EngineChild):
+class Tones(capi._PcmChild):
     """iqd_tones_*: per channel and frame of frame_len PCM samples the power of each of the tones (phase_inc: one uint32 each),
     the best and the second, a hit by min_power, ratio_q8 and energy_q8, and a tone in force with hysteresis (open hits to
-    open, more than hold misses to close).  Frames straddle calls; state is carried from call to call until reset()."""
+    open, more than hold misses to close).  Frames straddle calls; state is carried from call to call until reset().
+    state(channel): dict(tone, cand, run, miss, fill)."""
+    _State = TonesState
 
     def __init__(self, engine, n_channels, phase_inc, frame_len=4096, window=None, min_power=0, ratio_q8=512, energy_q8=0, open=2,
                  hold=1, reserved=(0, 0, 0, 0), abi_version=ABI_VERSION):
@@ -115,11 +110,8 @@ class Tones(capi._EngineChild):
         """pcm [n_channels, row_stride] int16 (a host array), the first n samples of each row (count: [n_channels] uint32, fewer
         for some) -> (n_frames [n_channels] uint32, frames [n_channels, F] TONES_FRAME, power [n_channels, F, n_tones] uint64 or
         None); synchronises."""
-        pcm = np.ascontiguousarray(pcm, np.int16).reshape(self.n_channels, -1)
-        stride = pcm.shape[1]
-        n = stride if n is None else int(n)
+        pcm, stride, n, count = self._rows(pcm, n, count)
         F = self.max_frames(max(n, 0))
-        count = None if count is None else np.ascontiguousarray(count, np.uint32)
         nf = np.zeros(self.n_channels, np.uint32)
         frames = np.zeros((self.n_channels, F), TONES_FRAME)
         power = np.zeros((self.n_channels, F, self.n_tones), np.uint64) if want_power else None
@@ -129,18 +121,5 @@ class Tones(capi._EngineChild):
 
     def run_device(self, pcm_dev, row_stride, n, n_frames_dev, frames_dev, power_dev=0, count_dev=0, engine=None):
         """iqd_tones_run_device: device pointers (integers), queued on the engine's stream."""
-        e = self._e if engine is None else engine
-        self._e._check(self._L.iqd_tones_run_device(e._h, self._h, _dev_ptr(pcm_dev), int(row_stride), _dev_ptr(count_dev), int(n),
-                                                    _dev_ptr(n_frames_dev), _dev_ptr(frames_dev), _dev_ptr(power_dev)))
-
-    def reset(self):
-        """iqd_tones_reset: every channel's open frame and decision state cleared."""
-        self._e._check(self._L.iqd_tones_reset(self._h))
-
-    def state(self, channel=0):
-        """iqd_tones_get_state: dict(tone, cand, run, miss, fill) of one channel; synchronises."""
-        s = TonesState()
-        if not 0 <= int(channel) <= 0xffffffff:
-            raise IqdError(-1, "iqd_tones_get_state: channel %r out of range" % (channel,))
-        self._e._check(self._L.iqd_tones_get_state(self._h, int(channel), C.byref(s)))
-        return dict(tone=s.tone, cand=s.cand, run=s.run, miss=s.miss, fill=s.fill)
+        self._run_device(engine, _dev_ptr(pcm_dev), int(row_stride), _dev_ptr(count_dev), int(n), _dev_ptr(n_frames_dev), _dev_ptr(frames_dev),
+                         _dev_ptr(power_dev))

@@ -2,22 +2,16 @@
 tests/fsk_model.py; the shapes and events the corpus must cover; the host-only helpers against Python integers; the add-on
 header against the binding's own prototype table and struct mirrors; the chain test's signal on the oracle alone.
 No GPU: the library is loaded for its host-only functions."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from rtlsdrdiags_amd import capi, fsk
+from tests import addon_checks as ac
 from tests import fsk_cases as fc
 from tests import fsk_model as fm
 from tests.test_abi_layout import mirror_layout
-from tests.test_abi_prototypes import ctypes_class
-from tests import test_tones_host as tth          # its header parser, pointed at this header
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "iqdemod_fsk.h")
 
 
 @pytest.fixture(scope="module")
@@ -139,34 +133,15 @@ def test_the_models_sizes_follow_the_header(phasor):
 
 # ---- the add-on header against the binding ----
 
-def header_prototypes():
-    """tests/test_tones_host.py's parser on this header"""
-    old = tth.HEADER
-    tth.HEADER = HEADER
-    try:
-        return tth.header_prototypes(), tth.header_text()
-    finally:
-        tth.HEADER = old
-
-
 def test_the_add_on_table_is_the_add_on_header():
-    header, _ = header_prototypes()
-    assert len(header) == 11 and list(header) == list(fsk.PROTOTYPES)
-    assert not set(header) & set(capi.PROTOTYPES)
-    for name, (ret, params) in header.items():
-        restype, argtypes = fsk.PROTOTYPES[name]
-        assert (ctypes_class(restype, returned=True), [ctypes_class(t) for t in argtypes]) == (ret, params), name
-    text = open(HEADER).read()
+    ac.check_table_is_header("fsk", fsk, 11)
+    text = open(ac.header_path("fsk")).read()
     assert re.search(r"#define IQD_FSK_ABI_VERSION (\d+)", text).group(1) == str(fsk.ABI_VERSION)
     assert re.search(r"#define IQD_FSK_NRZI (\d+)u", text).group(1) == str(fsk.NRZI)
 
 
 def test_the_library_exports_the_add_on_and_binds_it_from_its_own_table():
-    lib = fsk._lib()
-    assert lib is capi._lib()
-    for name, (restype, argtypes) in fsk.PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is restype and fn.argtypes == list(argtypes), name
+    ac.check_library_binding(fsk)
 
 
 MIRROR = {"iqd_fsk_config": fsk.FskConfig, "iqd_fsk_frame": fsk.FSK_FRAME, "iqd_fsk_state": fsk.FskState}
@@ -174,28 +149,7 @@ MIRROR = {"iqd_fsk_config": fsk.FskConfig, "iqd_fsk_frame": fsk.FSK_FRAME, "iqd_
 
 def test_every_struct_of_the_add_on_matches_its_mirror(tmp_path):
     """a stand-alone C program, compiled with the address and undefined-behaviour sanitizers, prints the layouts"""
-    structs = {}
-    for name, body in re.findall(r"typedef\s+struct\s+(iqd_\w+)\s*\{(.*?)\}", header_prototypes()[1], flags=re.S):
-        structs[name] = [re.search(r"(\w+)\s*(\[\d+\])?\s*$", d.strip()).group(1) for d in body.split(";") if d.strip()]
-    assert set(structs) == set(MIRROR)
-    exe = str(tmp_path / "fsk_layout_check")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "abi_layout", "fsk_layout_check.c"), "-o", exe],
-                   check=True)
-    run = subprocess.run([exe], stdout=subprocess.PIPE, check=True, text=True)
-    compiled = {}
-    for line in run.stdout.splitlines():
-        what, a, b = line.split()
-        if what == "struct":
-            compiled[a] = (int(b), [])
-        else:
-            name, field = what.split(".")
-            compiled[name][1].append((field, int(a), int(b)))
-    assert list(compiled) == list(structs)
-    for name, fields in structs.items():
-        size, lines = compiled[name]
-        assert [f for f, _, _ in lines] == fields, name
-        assert mirror_layout(MIRROR[name]) == (size, lines), name
+    compiled = ac.compiled_layouts("fsk", MIRROR, tmp_path)
     assert mirror_layout(fm.FRAME) == mirror_layout(fsk.FSK_FRAME) and compiled["iqd_fsk_frame"][0] == 24
     assert compiled["iqd_fsk_config"][0] == 64 and compiled["iqd_fsk_state"][0] == 40
 

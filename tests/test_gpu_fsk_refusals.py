@@ -8,31 +8,12 @@ import pytest
 from rtlsdrdiags_amd import capi, fsk
 from tests import fsk_cases as fc
 from tests import fsk_model as fm
+from tests.addon_checks import EINVAL, eng, refused          # noqa: F401 (eng: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 CH = 5
 GOOD = dict(fc.T8)
-
-
-@pytest.fixture(scope="module")
-def eng():
-    e = capi.Engine(n_channels=1)
-    yield e
-    e.close()
-
-
-def refused(eng, fn, *words):
-    """fn() raises IQD_EINVAL with every word in its message and queues nothing"""
-    before = eng.stats()
-    with pytest.raises(capi.IqdError) as err:
-        fn()
-    assert err.value.status == EINVAL, err.value
-    for w in words:
-        assert w in str(err.value), (w, str(err.value))
-    after = eng.stats()
-    assert (after["device_launches"], after["device_copies"]) == (before["device_launches"], before["device_copies"])
 
 
 CREATE = [

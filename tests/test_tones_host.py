@@ -2,22 +2,16 @@
 tests/tones_model.py; the CTCSS defaults with the library's phasor table; the host-only helpers against Python integers; the
 add-on header against the binding's own prototype table and struct mirrors; the chain test's signal on the oracle alone.
 No GPU: the library is loaded for its host-only functions."""
-import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from rtlsdrdiags_amd import capi, tones
+from tests import addon_checks as ac
 from tests import tones_cases as tc
 from tests import tones_model as tm
 from tests.test_abi_layout import mirror_layout
-from tests.test_abi_prototypes import C_RETURN, c_param_class, ctypes_class
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "iqdemod_tones.h")
 
 
 @pytest.fixture(scope="module")
@@ -133,46 +127,14 @@ def test_default_window_and_tone_lists(phasor):
 
 # ---- the add-on header against the binding ----
 
-def header_text():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return re.sub(r"//[^\n]*", " ", text)
-
-
-def header_prototypes():
-    """{name: (return class, [parameter classes])} of every function include/iqdemod_tones.h declares (the parser of
-    tests/test_abi_prototypes.py on this header)"""
-    text = "\n".join(l for l in header_text().splitlines() if not l.lstrip().startswith("#") and 'extern "C"' not in l)
-    text = re.sub(r"\{[^{}]*\}", " ", text)
-    out = {}
-    for stmt in (" ".join(s.split()) for s in text.split(";")):
-        m = re.fullmatch(r"(.*?)\b(iqd_\w+) ?\((.*)\)", stmt)
-        if not m:
-            assert "(" not in stmt, "a declaration this parser cannot read: %r" % stmt
-            continue
-        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
-        assert name not in out, name
-        out[name] = ("pointer" if "*" in ret else C_RETURN[ret.replace("const ", "")],
-                     [] if params == "void" else [c_param_class(p.strip()) for p in params.split(",")])
-    return out
-
-
 def test_the_add_on_table_is_the_add_on_header():
-    header = header_prototypes()
-    assert len(header) == 11 and list(header) == list(tones.PROTOTYPES)
-    assert not set(header) & set(capi.PROTOTYPES)
-    for name, (ret, params) in header.items():
-        restype, argtypes = tones.PROTOTYPES[name]
-        assert (ctypes_class(restype, returned=True), [ctypes_class(t) for t in argtypes]) == (ret, params), name
-    assert re.search(r"#define IQD_TONES_ABI_VERSION (\d+)", open(HEADER).read()).group(1) == str(tones.ABI_VERSION)
+    ac.check_table_is_header("tones", tones, 11)
+    assert re.search(r"#define IQD_TONES_ABI_VERSION (\d+)", open(ac.header_path("tones")).read()).group(1) == str(tones.ABI_VERSION)
     assert (tones.F_OPENED, tones.F_CLOSED, tones.NONE) == (tm.F_OPENED, tm.F_CLOSED, tm.NONE) == (1, 2, 0xffffffff)
 
 
 def test_the_library_exports_the_add_on_and_binds_it_from_its_own_table():
-    lib = tones._lib()
-    assert lib is capi._lib()
-    for name, (restype, argtypes) in tones.PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is restype and fn.argtypes == list(argtypes), name
+    ac.check_library_binding(tones)
 
 
 MIRROR = {"iqd_tones_config": tones.TonesConfig, "iqd_tones_frame": tones.TONES_FRAME, "iqd_tones_state": tones.TonesState}
@@ -180,28 +142,7 @@ MIRROR = {"iqd_tones_config": tones.TonesConfig, "iqd_tones_frame": tones.TONES_
 
 def test_every_struct_of_the_add_on_matches_its_mirror(tmp_path):
     """a stand-alone C program, compiled with the address and undefined-behaviour sanitizers, prints the layouts"""
-    structs = {}
-    for name, body in re.findall(r"typedef\s+struct\s+(iqd_\w+)\s*\{(.*?)\}", header_text(), flags=re.S):
-        structs[name] = [re.search(r"(\w+)\s*(\[\d+\])?\s*$", d.strip()).group(1) for d in body.split(";") if d.strip()]
-    assert set(structs) == set(MIRROR)
-    exe = str(tmp_path / "tones_layout_check")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "abi_layout", "tones_layout_check.c"), "-o", exe],
-                   check=True)
-    run = subprocess.run([exe], stdout=subprocess.PIPE, check=True, text=True)
-    compiled = {}
-    for line in run.stdout.splitlines():
-        what, a, b = line.split()
-        if what == "struct":
-            compiled[a] = (int(b), [])
-        else:
-            name, field = what.split(".")
-            compiled[name][1].append((field, int(a), int(b)))
-    assert list(compiled) == list(structs)
-    for name, fields in structs.items():
-        size, lines = compiled[name]
-        assert [f for f, _, _ in lines] == fields, name
-        assert mirror_layout(MIRROR[name]) == (size, lines), name
+    compiled = ac.compiled_layouts("tones", MIRROR, tmp_path)
     assert mirror_layout(tm.FRAME) == mirror_layout(tones.TONES_FRAME) and compiled["iqd_tones_frame"][0] == 40
     assert compiled["iqd_tones_config"][0] == 72 and compiled["iqd_tones_state"][0] == 32
 

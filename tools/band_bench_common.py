@@ -109,6 +109,26 @@ class Chain:
             self.eng.dev_free(p)
 
 
+def fm_accept_rig(n_ch=4096, nbytes=131072, n_pcm=2048):
+    """What tools/tones_bench.py and fsk_bench.py stand on: (eng, d_iq, d_pcm, d_cnt, accept) - an FM engine of n_ch channels, a
+    tone's capture for each on the device, and accept(), the call that leaves n_pcm samples per channel in d_pcm and the counts
+    in d_cnt (run once here, and checked)"""
+    from rtlsdrdiags_amd import capi, synth
+    eng = capi.Engine(n_ch)
+    eng.set_mode("fm")
+    d_iq, d_pcm, d_cnt = eng.dev_alloc(n_ch * nbytes), eng.dev_alloc(n_ch * n_pcm * 2), eng.dev_alloc(n_ch * 4)
+    eng.dev_upload(d_iq, synth.fm_tone(nbytes // 2, seed=3, deviation=2500.0))
+    eng.dev_tile(d_iq, nbytes, n_ch * nbytes)
+
+    def accept():
+        eng.accept_device(d_iq, nbytes, d_pcm, d_cnt)
+
+    accept()
+    eng.synchronize()
+    assert (eng.dev_download(d_cnt, n_ch * 4, np.uint32) == n_pcm).all()
+    return eng, d_iq, d_pcm, d_cnt, accept
+
+
 def alternate(calls, eng, args, after=None):
     """The calls one after the other, three times over -> ({key: [each round's median ms]}, {key: the median of those});
     after(key) runs behind a call's timing."""

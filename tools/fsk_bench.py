@@ -21,7 +21,7 @@ import numpy as np
 
 import band_bench_common as bb
 
-N_CH, BYTES, N_PCM = 4096, 131072, 2048
+N_CH, N_PCM = 4096, 2048
 
 
 def afsk_row(phasor, cfg):
@@ -38,20 +38,13 @@ def afsk_row(phasor, cfg):
 
 def main():
     args = bb.arguments(sizes=False)
-    from rtlsdrdiags_amd import capi, fsk, synth, tones
+    from rtlsdrdiags_amd import capi, fsk, tones
 
-    eng = capi.Engine(N_CH)
-    eng.set_mode("fm")
-    d_iq, d_pcm, d_cnt = eng.dev_alloc(N_CH * BYTES), eng.dev_alloc(N_CH * N_PCM * 2), eng.dev_alloc(N_CH * 4)
-    eng.dev_upload(d_iq, synth.fm_tone(BYTES // 2, seed=3, deviation=2500.0))
-    eng.dev_tile(d_iq, BYTES, N_CH * BYTES)
+    eng, d_iq, d_pcm, d_cnt, accept = bb.fm_accept_rig(N_CH, n_pcm=N_PCM)
     cfg = fsk.afsk1200(8000)
     rows = {"afsk_ms": afsk_row(capi.channelizer_phasor_table(), cfg), "silence_ms": np.zeros(N_PCM, np.int16),
             "noise_ms": np.random.default_rng(6).integers(-32768, 32768, N_PCM).astype(np.int16)}
-    objs, arrays, calls = {}, [d_iq, d_pcm, d_cnt], {"accept_ms": lambda: eng.accept_device(d_iq, BYTES, d_pcm, d_cnt)}
-    calls["accept_ms"]()
-    eng.synchronize()
-    assert (eng.dev_download(d_cnt, N_CH * 4, np.uint32) == N_PCM).all()
+    objs, arrays, calls = {}, [d_iq, d_pcm, d_cnt], {"accept_ms": accept}
 
     ctcss = np.array([tones.phase_inc(f, 8000) for f in tones.ctcss_mhz()], np.uint32)
     bank = objs["tones_l256_ms"] = tones.Tones(eng, N_CH, ctcss, frame_len=256, **{k: v for k, v in tones.CTCSS_DEFAULTS.items() if k != "frame_len"})

@@ -16,29 +16,21 @@ parameter comes from a list of edges, the rest at random, all inside the ranges 
   calls     one to five, n from {0, 1, W - 1, W, 31, 32, 33, 64, 65, 255, 256, 257} or at random, row_stride >= n, rows 2-byte
             aligned only; counts (0 and above n among them) or none; bits or none; the host form or the device form; a reset
             in between"""
-import argparse
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np                                     # noqa: E402
-from rtlsdrdiags_amd import capi, fsk                  # noqa: E402
+from rtlsdrdiags_amd import fsk                        # noqa: E402
 from tests import fsk_model as fm                      # noqa: E402
+import pcm_fuzz_common as pf                           # noqa: E402
+from pcm_fuzz_common import Buffers, case_rng, pick    # noqa: E402,F401 (Buffers: the tests' rig)
 
 W_EDGES = (2, 7, 8, 63, 64)
 C_EDGES = (1, 2, 63, 64, 65)
 N_EDGES = (0, 1, 31, 32, 33, 64, 65, 255, 256, 257)
 SLICE = (9402, 300)            # (seed, cases): tests/test_gpu_fsk_fuzz.py's
 FLAG = [0, 1, 1, 1, 1, 1, 1, 0]
-
-
-def case_rng(seed, index):
-    return np.random.default_rng([int(seed), int(index)])
-
-
-def pick(rng, seq):
-    return seq[int(rng.integers(len(seq)))]
 
 
 def line_bits(rng, cfg):
@@ -121,35 +113,10 @@ def draw(seed, index, phasor):
     return dict(seed=seed, index=index, C=C, cfg=cfg, window=window, steps=steps)
 
 
-class Buffers:
-    """device arrays that grow and are reused from call to call uncleared"""
-
-    def __init__(self, eng):
-        self.eng, self.ptr, self.cap = eng, {}, {}
-
-    def get(self, name, nbytes):
-        if self.cap.get(name, 0) < nbytes:
-            if name in self.ptr:
-                self.eng.dev_free(self.ptr[name])
-            self.cap[name] = 2 * nbytes + 64
-            self.ptr[name] = self.eng.dev_alloc(self.cap[name])
-        return self.ptr[name]
-
-    def close(self):
-        for p in self.ptr.values():
-            self.eng.dev_free(p)
-        self.ptr, self.cap = {}, {}
-
-
 def run_device(eng, bufs, t, pcm, n, count, want_bits):
     C, stride = pcm.shape
     F, Bw, Bc = t.max_frames(n), t.max_bit_words(n), t.max_bytes(n)
-    p_pcm = bufs.get("pcm", pcm.nbytes + 16) + 2                    # rows from 2 bytes behind an aligned address on
-    eng.dev_upload(p_pcm - 2, np.concatenate([np.zeros(1, np.int16), pcm.reshape(-1)]))
-    p_cnt = 0
-    if count is not None:
-        p_cnt = bufs.get("count", C * 4)
-        eng.dev_upload(p_cnt, count)
+    p_pcm, p_cnt = pf.upload_rows(eng, bufs, pcm, count)
     p_nb, p_nf = bufs.get("nb", C * 4), bufs.get("nf", C * 4)
     p_bits, p_fr, p_by = bufs.get("bits", C * Bw * 4 + 16), bufs.get("frames", C * F * 24 + 16), bufs.get("bytes", C * Bc + 16)
     t.run_device(p_pcm, stride, n, p_nb, p_nf, p_fr, p_by, bits_dev=p_bits if want_bits else 0, count_dev=p_cnt)
@@ -166,55 +133,14 @@ def run_device(eng, bufs, t, pcm, n, count, want_bits):
 
 
 def run_case(case, phasor, eng=None, bufs=None, gpu=True):
-    """the model's results; with gpu, the library's held against them (AssertionError names the case and the step)"""
-    who = "seed %d case %d" % (case["seed"], case["index"])
+    """the model's results and every channel's state; with gpu, the library's held against them (AssertionError names the case
+    and the step)"""
     m = fm.Model(case["C"], phasor, window=case["window"], **case["cfg"])
-    t = fsk.Fsk(eng, case["C"], window=case["window"], **case["cfg"]) if gpu else None
-    out = []
-    try:
-        for i, s in enumerate(case["steps"]):
-            if s[0] == "reset":
-                m.reset()
-                if gpu:
-                    t.reset()
-                continue
-            _, pcm, n, count, want_bits, form = s
-            want = m.run(pcm, n, count)
-            out.append(want)
-            if not gpu:
-                continue
-            got = t.run(pcm, n, count, want_bits=want_bits) if form == "host" else run_device(eng, bufs, t, pcm, n, count, want_bits)
-            assert np.array_equal(got[0], want[0]), (who, i, "n_bits", got[0], want[0])
-            assert (got[1] is None) == (not want_bits) and (got[1] is None or np.array_equal(got[1], want[1])), (who, i, "bits")
-            assert np.array_equal(got[2], want[2]), (who, i, "n_frames", got[2], want[2])
-            assert got[3].tobytes() == want[3].tobytes(), (who, i, "frames", [k for k in fm.FRAME.names if not np.array_equal(got[3][k], want[3][k])])
-            assert np.array_equal(got[4], want[4]), (who, i, "bytes")
-        if gpu:
-            for c in sorted({0, case["C"] // 2, case["C"] - 1}):
-                assert t.state(c) == m.state(c), (who, "state", c, t.state(c), m.state(c))
-    finally:
-        if t is not None:
-            t.close()
+    out = pf.run_case(case, m, lambda: fsk.Fsk(eng, case["C"], window=case["window"], **case["cfg"]),
+                      lambda t, *step: run_device(eng, bufs, t, *step), "want_bits",
+                      [("n_bits", pf.equal), ("bits", None), ("n_frames", pf.equal), ("frames", pf.records), ("bytes", pf.equal)], gpu)
     return out, [m.state(c) for c in range(case["C"])]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seed", type=int, default=SLICE[0])
-    ap.add_argument("--cases", type=int, default=SLICE[1])
-    ap.add_argument("--case", type=int, default=None)
-    a = ap.parse_args()
-    phasor = capi.channelizer_phasor_table()
-    eng = capi.Engine(n_channels=1)
-    bufs = Buffers(eng)
-    t0 = time.time()
-    todo = [a.case] if a.case is not None else range(a.cases)
-    for i in todo:
-        run_case(draw(a.seed, i, phasor), phasor, eng, bufs)
-    bufs.close()
-    eng.close()
-    print("fsk_fuzz: seed %d, %d case(s) identical to the model in %.1f s" % (a.seed, len(todo), time.time() - t0))
-
-
 if __name__ == "__main__":
-    main()
+    pf.main("fsk_fuzz", SLICE, draw, run_case)

@@ -20,25 +20,21 @@ import numpy as np
 
 import band_bench_common as bb
 
-N_CH, BYTES, N_PCM = 4096, 131072, 2048
+N_CH, N_PCM = 4096, 2048
 
 
 def main():
     args = bb.arguments(sizes=False)
     from chan_bench import timed
-    from rtlsdrdiags_amd import capi, synth, tones
+    from rtlsdrdiags_amd import tones
 
-    eng = capi.Engine(N_CH)
-    eng.set_mode("fm")
-    d_iq, d_pcm, d_cnt = eng.dev_alloc(N_CH * BYTES), eng.dev_alloc(N_CH * N_PCM * 2), eng.dev_alloc(N_CH * 4)
-    eng.dev_upload(d_iq, synth.fm_tone(BYTES // 2, seed=3, deviation=2500.0))
-    eng.dev_tile(d_iq, BYTES, N_CH * BYTES)
+    eng, d_iq, d_pcm, d_cnt, accept = bb.fm_accept_rig(N_CH, n_pcm=N_PCM)
     ctcss = [tones.phase_inc(f, 8000) for f in tones.ctcss_mhz()]
     rng = np.random.default_rng(1)
     banks = {"l4096_t50_ms": (4096, ctcss, True), "l256_t50_ms": (256, ctcss, True),
              "l4096_t64_ms": (4096, ctcss + [int(v) for v in rng.integers(0, 2 ** 32, 14)], True),
              "l4096_t50_nopower_ms": (4096, ctcss, False)}
-    objs, arrays, calls = {}, [d_iq, d_pcm, d_cnt], {"accept_ms": lambda: eng.accept_device(d_iq, BYTES, d_pcm, d_cnt)}
+    objs, arrays, calls = {}, [d_iq, d_pcm, d_cnt], {"accept_ms": accept}
     for key, (L, incs, power) in banks.items():
         t = objs[key] = tones.Tones(eng, N_CH, np.array(incs, np.uint32), frame_len=L, **{k: v for k, v in tones.CTCSS_DEFAULTS.items() if k != "frame_len"})
         F = t.max_frames(N_PCM)
@@ -49,8 +45,6 @@ def main():
     d_small = [eng.dev_alloc(64), eng.dev_alloc(16 * 40)]
     arrays += d_small
     calls["launch_ms"] = lambda: small.run_device(d_pcm, 32, 32, d_small[0], d_small[1])
-    calls["accept_ms"]()
-    eng.synchronize()
 
     ms, med = bb.alternate(calls, eng, args)
     # the two kinds of call at L = 4096, apart: the state alternates, so every second call is of one kind

@@ -14,28 +14,20 @@ parameter comes from a list of edges, the rest at random, all inside the ranges 
   samples   per channel and frame: noise, one of the tones in noise, two tones, silence, +-32767 alternating, -32768
   calls     one to five, n from {0, 1, L - 1, L, L + 1, 3 L + 5} or at random, row_stride >= n, rows 2-byte aligned only;
             counts (0 and above n among them) or none; power or none; the host form or the device form; a reset in between"""
-import argparse
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np                                     # noqa: E402
-from rtlsdrdiags_amd import capi, tones                # noqa: E402
+from rtlsdrdiags_amd import tones                      # noqa: E402
 from tests import tones_model as tm                    # noqa: E402
+import pcm_fuzz_common as pf                           # noqa: E402
+from pcm_fuzz_common import Buffers, case_rng, pick    # noqa: E402,F401 (Buffers: the tests' rig)
 
 L_EDGES = (32, 64, 96, 128, 160, 256)
 T_EDGES = (1, 2, 7, 8, 9, 15, 16, 17, 33, 64)
 C_EDGES = (1, 2, 15, 16, 17, 33)
 SLICE = (9401, 300)            # (seed, cases): tests/test_gpu_tones_fuzz.py's
-
-
-def case_rng(seed, index):
-    return np.random.default_rng([int(seed), int(index)])
-
-
-def pick(rng, seq):
-    return seq[int(rng.integers(len(seq)))]
 
 
 def draw(seed, index, phasor):
@@ -90,35 +82,10 @@ def draw(seed, index, phasor):
     return dict(seed=seed, index=index, C=C, L=L, incs=incs, window=window, cfg=cfg, steps=steps)
 
 
-class Buffers:
-    """device arrays that grow and are reused from call to call uncleared"""
-
-    def __init__(self, eng):
-        self.eng, self.ptr, self.cap = eng, {}, {}
-
-    def get(self, name, nbytes):
-        if self.cap.get(name, 0) < nbytes:
-            if name in self.ptr:
-                self.eng.dev_free(self.ptr[name])
-            self.cap[name] = 2 * nbytes + 64
-            self.ptr[name] = self.eng.dev_alloc(self.cap[name])
-        return self.ptr[name]
-
-    def close(self):
-        for p in self.ptr.values():
-            self.eng.dev_free(p)
-        self.ptr, self.cap = {}, {}
-
-
 def run_device(eng, bufs, t, pcm, n, count, want_power):
     C, stride = pcm.shape
     F, T = t.max_frames(n), t.n_tones
-    p_pcm = bufs.get("pcm", pcm.nbytes + 16) + 2                    # rows from 2 bytes behind an aligned address on
-    eng.dev_upload(p_pcm - 2, np.concatenate([np.zeros(1, np.int16), pcm.reshape(-1)]))
-    p_cnt = 0
-    if count is not None:
-        p_cnt = bufs.get("count", C * 4)
-        eng.dev_upload(p_cnt, count)
+    p_pcm, p_cnt = pf.upload_rows(eng, bufs, pcm, count)
     p_nf, p_fr, p_pw = bufs.get("nf", C * 4), bufs.get("frames", C * F * 40 + 16), bufs.get("power", C * F * T * 8 + 16)
     t.run_device(p_pcm, stride, n, p_nf, p_fr, power_dev=p_pw if want_power else 0, count_dev=p_cnt)
     eng.synchronize()
@@ -133,52 +100,12 @@ def run_device(eng, bufs, t, pcm, n, count, want_power):
 
 def run_case(case, phasor, eng=None, bufs=None, gpu=True):
     """the model's results; with gpu, the library's held against them (AssertionError names the case and the step)"""
-    who = "seed %d case %d" % (case["seed"], case["index"])
     m = tm.Model(case["C"], case["L"], case["incs"], phasor, window=case["window"], **case["cfg"])
-    t = tones.Tones(eng, case["C"], np.array(case["incs"], np.uint32), frame_len=case["L"], window=case["window"], **case["cfg"]) if gpu else None
-    out = []
-    try:
-        for i, s in enumerate(case["steps"]):
-            if s[0] == "reset":
-                m.reset()
-                if gpu:
-                    t.reset()
-                continue
-            _, pcm, n, count, want_power, form = s
-            want = m.run(pcm, n, count)
-            out.append(want)
-            if not gpu:
-                continue
-            got = t.run(pcm, n, count, want_power=want_power) if form == "host" else run_device(eng, bufs, t, pcm, n, count, want_power)
-            assert np.array_equal(got[0], want[0]), (who, i, "n_frames", got[0], want[0])
-            assert got[1].tobytes() == want[1].tobytes(), (who, i, "frames", [k for k in tm.FRAME.names if not np.array_equal(got[1][k], want[1][k])])
-            assert (got[2] is None) == (not want_power) and (got[2] is None or np.array_equal(got[2], want[2])), (who, i, "power")
-        if gpu:
-            for c in sorted({0, case["C"] // 2, case["C"] - 1}):
-                assert t.state(c) == m.state(c), (who, "state", c, t.state(c), m.state(c))
-    finally:
-        if t is not None:
-            t.close()
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seed", type=int, default=SLICE[0])
-    ap.add_argument("--cases", type=int, default=SLICE[1])
-    ap.add_argument("--case", type=int, default=None)
-    a = ap.parse_args()
-    phasor = capi.channelizer_phasor_table()
-    eng = capi.Engine(n_channels=1)
-    bufs = Buffers(eng)
-    t0 = time.time()
-    todo = [a.case] if a.case is not None else range(a.cases)
-    for i in todo:
-        run_case(draw(a.seed, i, phasor), phasor, eng, bufs)
-    bufs.close()
-    eng.close()
-    print("tones_fuzz: seed %d, %d case(s) identical to the model in %.1f s" % (a.seed, len(todo), time.time() - t0))
+    return pf.run_case(case, m, lambda: tones.Tones(eng, case["C"], np.array(case["incs"], np.uint32), frame_len=case["L"],
+                                                    window=case["window"], **case["cfg"]),
+                       lambda t, *step: run_device(eng, bufs, t, *step), "want_power",
+                       [("n_frames", pf.equal), ("frames", pf.records), ("power", None)], gpu)
 
 
 if __name__ == "__main__":
-    main()
+    pf.main("tones_fuzz", SLICE, draw, run_case)
